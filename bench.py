@@ -1,9 +1,9 @@
 #!/usr/bin/env python3
 """Headline benchmark: spectra clustered / second through the whole hot path
 (vectorise -> buckets -> IVF/flat cosine scan -> top-k -> filter -> DBSCAN -> refine ->
-medoids/labels) on synthetic peak lists, plus the cosine kernel's roofline fraction.
+medoids/labels) on synthetic peak lists; with `--full` also the cosine kernel's roofline fraction and the rest below.
 
-    python bench.py --gpus 1 --steps 100 --warmup 2
+    python bench.py --gpus 1 --steps 100 --warmup 2 [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -25,10 +25,16 @@ N GPUs.  A "step" = one pass of the whole hot path over that dataset:
     global sparse graph and the globally unique labels (rank-major offsets like falcon.py:189-193), which the
     rank copies to the host.  At N = 1 there is nothing to exchange and the step is the single-GPU pipeline.
 
-Inputs are resident in HBM before the timed region (`value`); `value_host_to_host` is the throughput of the same steps
+Inputs are resident in HBM before the timed region (`value`).  A plain run does only what the headline needs: it builds
+the dataset, primes the pools, runs the W warmup steps, times the K steps and prints rank 0's ONE JSON line (`metric`,
+`value`, `unit`, `higher_is_better`, `dtype`, `ms_per_step`, the configuration).  `--dump-outputs DIR` then writes what the
+last timed step returned (labels, medoids) as DIR/<name>.npy, so that two builds can be compared output for output.
+
+Everything else is measured only with `--full`: the cold pass, the per-stage `roofline` / `stage_ms`, the host-to-host legs
+and `--with-strong`.  `value_host_to_host` is the throughput of the same steps
 with the peak arrays starting in pinned host memory: the upload of step i + 1 travels on a copy stream under
-the kernels of step i (`ms_per_step_host_to_host_latency` = one step alone, upload then compute).  Rank 0 prints ONE JSON
-line; at N = 1 it also carries `configs`: the 10 M-spectra float32 run (BASELINE configs[2]'s dataset on one GPU = the
+the kernels of step i (`ms_per_step_host_to_host_latency` = one step alone, upload then compute).  With `--full` the line
+at N = 1 also carries `configs`: the 10 M-spectra float32 run (BASELINE configs[2]'s dataset on one GPU = the
 north star's target size; repeated as the top-level `north_star` object), the 10 M / low_dim 800 / float16 run
 (configs[4]), the configs[3] bucket regime at 10 M, SURVEY 8d's C4 row as written (batch_size 65536: n_list 1,024), a
 skewed 2 M workload (log-normal window occupancy, 5..50 peaks per spectrum) and configs[3] itself (50 M spectra, n_probe
@@ -152,6 +158,30 @@ def pmc_traffic(workload):
     return None, None
 
 
+DUMP_BUDGET_BYTES = 63_000_000     # all of --dump-outputs' files together stay under 64 MB (npy headers included)
+
+
+def dump_outputs(dirname, arrays, budget=DUMP_BUDGET_BYTES):
+    """--dump-outputs: every array as DIR/<name>.npy in float64 (the labels and row indices it holds are exact).  If all of them
+    do not fit the budget, an array longer than its share is replaced by a fixed, seeded sample of its elements (ascending
+    positions, the same for the same length) and the positions go to DIR/<name>_index.npy.  -> what was written, per name"""
+    os.makedirs(dirname, exist_ok=True)
+    total = sum(8 * a.size for a in arrays.values())
+    cap = budget // (16 * len(arrays))                   # a sampled array writes values + positions, 8 bytes each
+    written = {}
+    for name, a in arrays.items():
+        a = np.asarray(a).reshape(-1)
+        entry = {"n": int(a.size), "sampled": False}
+        if total > budget and a.size > cap:
+            idx = np.sort(np.random.default_rng(20240601).choice(a.size, size=cap, replace=False))
+            np.save(os.path.join(dirname, f"{name}_index.npy"), idx.astype(np.float64))
+            a = a[idx]
+            entry.update(sampled=True, kept=int(cap))
+        np.save(os.path.join(dirname, f"{name}.npy"), a.astype(np.float64))
+        written[name] = entry
+    return written
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -193,6 +223,12 @@ def main():
                     help="collective self-check: run ONLY the exchange step (SparseGraphExchange: sizes all-gather + one padded "
                          "payload all-gather over RCCL) with synthetic ragged payloads on the N ranks, verify every rank's received "
                          "bytes, print one JSON line and exit (0 = ok)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beyond the headline: cold pass, per-stage roofline, host-to-host legs, the "
+                         "`configs` array, the CPU baselines (the --no-* switches below and --with-strong act within --full)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned as DIR/<name>.npy (float64; arrays of "
+                         "more elements than the 64 MB budget allows are a fixed, seeded sample, their positions in <name>_index.npy)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-cold", action="store_true",
                     help="skip the cold-pass measurement (tools/cold_pass.py in fresh child processes, before this process touches the GPU)")
@@ -217,11 +253,13 @@ def main():
                     help="run the charge partitions strictly one after the other (default: software-pipelined, "
                          "ClusterPipeline.run_many)")
     args = ap.parse_args()
+    if args.with_strong and not args.full:
+        ap.error("--with-strong is a --full measurement: pass --full as well")
 
     # ---- what falcon.main() pays: ONE pass per charge in a fresh process.  Measured in fresh child processes BEFORE this process
     # touches the GPU (tools/cold_pass.py: library load, first pass incl. fal_ctx_plan, the following passes) -----------------
     cold = None
-    if int(os.environ.get("WORLD_SIZE", "1")) == 1 and not args.no_cold and not args.exchange_only:
+    if args.full and int(os.environ.get("WORLD_SIZE", "1")) == 1 and not args.no_cold and not args.exchange_only:
         import subprocess
         cold = {}
         for n_cold in (1_000_000, 10_000_000):
@@ -343,6 +381,7 @@ def main():
 
     concurrent = {"on": False}
     runner = None
+    last = {}                                                    # the last step's outputs (step / timed)
 
     def step(parts, run_args, collect=None, chunks=1):
         """one pass of the hot path over the dataset; `collect` != None: serial, per-stage timing, no exchange"""
@@ -371,6 +410,7 @@ def main():
                     lasts.append(dict(pipe.last))
                 if collect is not None:
                     collect.append(collect_stages(int(outs[-1][0].numel())))
+        last["outs"] = outs                                      # (labels, medoids) per partition, for --dump-outputs
         if not exchanging or collect is not None or chunks > 1:
             labels_all, current = [], 0
             for labels, medoids in outs:
@@ -407,11 +447,13 @@ def main():
         finish_pending()
         barrier()
         t0 = time.perf_counter()
+        res = None
         for _ in range(steps):
-            step(parts, run_args, chunks=chunks)
-        finish_pending()                                         # the last exchange lands inside the timed region
+            res = step(parts, run_args, chunks=chunks)
+        fin = finish_pending()                                   # the last exchange lands inside the timed region
         barrier()
         dt = time.perf_counter() - t0
+        last["labels"] = fin if fin is not None else res         # what the caller of the last timed step received
         if world > 1:
             t = torch.tensor([dt], dtype=torch.float64, device=dev)
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -453,12 +495,18 @@ def main():
         runner = PartitionRunner(local_rank, 2)
         concurrent["on"] = True
     dt = timed(parts, run_args, args.steps, args.warmup)
-    stages = staged(parts, run_args)
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        outputs = {"labels": last["labels"].numpy()}
+        if shard is None:                                        # every partition whole: medoids as rows of the dataset
+            outputs["medoids"] = np.concatenate([m.cpu().numpy() + job["part_off"][j] for j, (_, m) in enumerate(last["outs"])])
+        dumped = dump_outputs(args.dump_outputs, outputs)
+    stages = staged(parts, run_args) if args.full else None
 
     # ---- N > 1, weak mode: the FIXED dataset (BASELINE configs[2]) on the same ranks as well, so that the line also carries the
     # window-by-window deal of one shared dataset (the weak workload deals whole partitions) -------------------------
     strong_extra = None
-    if world > 1 and not strong and args.with_strong:
+    if args.full and world > 1 and not strong and args.with_strong:
         try:
             del parts
             torch.cuda.empty_cache()
@@ -480,7 +528,7 @@ def main():
     # ---- host-to-host: the peak arrays start in pinned host memory, labels end on the host -------
     h2h = h2h_latency = None
     h2h_multi = None
-    if world > 1 and concurrent["on"]:
+    if args.full and world > 1 and concurrent["on"]:
         # N ranks: every rank holds the job's partitions in pinned HOST memory; per step it uploads the precursor columns (the
         # deal needs them: 4 bytes per spectrum) and the peaks of ITS windows only (PartitionRunner.run -> take_rows)
         try:
@@ -514,7 +562,7 @@ def main():
             del host_parts
         except Exception as e:                                    # pragma: no cover -- reported, never hidden
             h2h_multi = {"error": repr(e)[:300]}
-    if world == 1:
+    if args.full and world == 1:
         pinned = [[t.cpu().pin_memory() for t in (x.precursor_mz, x.retention_time, x.mz, x.intensity, x.indptr)] for x in parts]
         copy_stream = torch.cuda.Stream(device=dev)
 
@@ -632,7 +680,7 @@ def main():
 
     # ---- the larger configurations on ONE GPU (north star target size; BASELINE configs[2] dataset / [3] / [4]) --------
     extra = []
-    if world == 1 and not args.no_configs and rank == 0:
+    if args.full and world == 1 and not args.no_configs and rank == 0:
         del parts
         torch.cuda.empty_cache()
         was_concurrent = concurrent["on"]
@@ -786,28 +834,30 @@ def main():
     if rank == 0:
         d = args.low_dim
         elem = 2 if args.dtype == "f16" else 4
-        s = summarize(stages, d, p, elem)
-        if args.dtype == "f16" or args.scan == "f16x3":
-            # issued matrix work: 3 f16 MFMAs per k-step for the split, 1 for plain float16 rows
-            roof = roofline_of(s, "scan16_kernel (f16 MFMA 32x32x16, LDS-staged) + dense_kernel for buckets < 64",
-                               PEAK_MFMA_F16_TFLOPS, "f16 MFMA 2.5 PFLOP/s dense", None,
-                               issued_factor=3.0 if (args.scan == "f16x3" and args.dtype == "f32") else 1.0)
-        elif ivf_regime and not args.no_ivf_prefilter:
-            roof = roofline_of(s, "list16s_kernel<25> (f16 MFMA 32x32x16, list-major)", PEAK_MFMA_F16_TFLOPS,
-                               "f16 MFMA 2.5 PFLOP/s dense", "10M_f32" if n_total == 10_000_000 and world == 1 else None)
-        else:
-            default = (n_total == 1_000_000 and world == 1 and d == 400 and args.n_neighbors_ann == 128 and args.mz_interval == 1.0
-                       and args.batch_size == 2 ** 15 and not args.prefilter)
-            roof = roofline_of(s, "dense4_kernel<50> (flat buckets of more than 32 rows, symmetric, four tiles per workgroup share one "
-                                  "candidate stream through LDS): cosine scan, fp32 MFMA 32x32x2",
-                               PEAK_MFMA_F32_TFLOPS, "fp32 MFMA 157.3 TFLOP/s", "headline" if default else None)
-            # the kernel computes each bucket's similarity matrix on/above the diagonal only (bit-identical by symmetry):
-            # `issued` = machine flops actually run through the matrix pipe, tile padding included
-            roof.update({"issued_tflops": s["issued_tflops"], "issued_frac": s["issued_tflops"] / PEAK_MFMA_F32_TFLOPS})
-        roof["profile"] = ("avg_launch_ms comes from a serial per-stage pass (HIP events); it agrees with the kernel's average in "
-                           "profiles/r6_bench_1M_pipelined_kernel_stats.csv (rocprofv3 --kernel-trace --stats of `python3 bench.py "
-                           "--partitions pipelined --no-configs --no-cpu-baseline --no-cold`: one stream); in the default two-stream run "
-                           "(round 5's trace: profiles/r5_bench_1M_kernel_stats.csv) the two partitions' kernels overlap and stretch each other")
+        roof = s = None
+        if stages is not None:                                   # (--full: the serial per-stage pass ran)
+            s = summarize(stages, d, p, elem)
+            if args.dtype == "f16" or args.scan == "f16x3":
+                # issued matrix work: 3 f16 MFMAs per k-step for the split, 1 for plain float16 rows
+                roof = roofline_of(s, "scan16_kernel (f16 MFMA 32x32x16, LDS-staged) + dense_kernel for buckets < 64",
+                                   PEAK_MFMA_F16_TFLOPS, "f16 MFMA 2.5 PFLOP/s dense", None,
+                                   issued_factor=3.0 if (args.scan == "f16x3" and args.dtype == "f32") else 1.0)
+            elif ivf_regime and not args.no_ivf_prefilter:
+                roof = roofline_of(s, "list16s_kernel<25> (f16 MFMA 32x32x16, list-major)", PEAK_MFMA_F16_TFLOPS,
+                                   "f16 MFMA 2.5 PFLOP/s dense", "10M_f32" if n_total == 10_000_000 and world == 1 else None)
+            else:
+                default = (n_total == 1_000_000 and world == 1 and d == 400 and args.n_neighbors_ann == 128 and args.mz_interval == 1.0
+                           and args.batch_size == 2 ** 15 and not args.prefilter)
+                roof = roofline_of(s, "dense4_kernel<50> (flat buckets of more than 32 rows, symmetric, four tiles per workgroup share one "
+                                      "candidate stream through LDS): cosine scan, fp32 MFMA 32x32x2",
+                                   PEAK_MFMA_F32_TFLOPS, "fp32 MFMA 157.3 TFLOP/s", "headline" if default else None)
+                # the kernel computes each bucket's similarity matrix on/above the diagonal only (bit-identical by symmetry):
+                # `issued` = machine flops actually run through the matrix pipe, tile padding included
+                roof.update({"issued_tflops": s["issued_tflops"], "issued_frac": s["issued_tflops"] / PEAK_MFMA_F32_TFLOPS})
+            roof["profile"] = ("avg_launch_ms comes from a serial per-stage pass (HIP events); it agrees with the kernel's average in "
+                               "profiles/r6_bench_1M_pipelined_kernel_stats.csv (rocprofv3 --kernel-trace --stats of `python3 bench.py --full "
+                               "--partitions pipelined --no-configs --no-cpu-baseline --no-cold`: one stream); in the default two-stream run "
+                               "(round 5's trace: profiles/r5_bench_1M_kernel_stats.csv) the two partitions' kernels overlap and stretch each other")
         out = {
             "metric": "spectra clustered/sec @1/2/4/8 GPU; cosine-kernel HBM GB/s vs roofline",
             "value": n_total * args.steps / dt,
@@ -846,10 +896,13 @@ def main():
                                       "configs[1] workload (same precursor range), block k's charges relabelled (2, 3) -> (2 + 2k, "
                                       f"3 + 2k): {2 * world} charge partitions, per-GPU work fixed by construction")
                                 if world > 1 else None)},
-            "roofline": roof,
-            "stage_ms": s["stage_ms"],
             "rccl": rccl_info(),
         }
+        if s is not None:
+            out["roofline"] = roof
+            out["stage_ms"] = s["stage_ms"]
+        if dumped is not None:
+            out["outputs"] = dumped
         if h2h is not None:
             # SURVEY 8d's contractual timing: peak arrays in pinned host memory -> labels on the host.  `value_host_to_host` is ONE
             # step alone (with two partition streams the runner uploads partition by partition and starts a partition's kernels
@@ -898,7 +951,7 @@ def main():
                                       "frac_of_f16_mfma_peak": r["frac_of_mfma_peak"], "frac_of_hbm_roof": r["frac_of_hbm_roof"],
                                       "traffic": r["traffic"]},
                     "index_build_ms": ns["stage_ms"]["build"], "coarse_ms": ns["stage_ms"]["coarse"]}
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             hosts = [{k: getattr(x, k).cpu().numpy() for k in ("precursor_mz", "retention_time", "mz", "intensity", "indptr")}
                      for x in parts]
             try:

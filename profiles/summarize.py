@@ -52,7 +52,7 @@ def _counter(db_path, counter):
     return out
 
 
-def pmc(fetch_db, write_db, passes, out_json, cmd="python3 bench.py --steps 3 --warmup 1 --no-cpu-baseline"):
+def pmc(fetch_db, write_db, passes, out_json, cmd="python3 bench.py --full --steps 3 --warmup 1 --no-cpu-baseline"):
     fetch = _counter(fetch_db, "FETCH_SIZE")
     write = _counter(write_db, "WRITE_SIZE")
     res = {"_note": f"rocprofv3 --kernel-trace --pmc FETCH_SIZE / --pmc WRITE_SIZE in separate passes over `{cmd}` "

@@ -4,14 +4,14 @@
 cd $GRAFT_REPO_ROOT
 export TMPDIR=/tmp
 O=gpurun_out
-timeout 1200 python bench.py > $O/r4_bench.txt 2>&1
+timeout 1200 python bench.py --full > $O/r4_bench.txt 2>&1
 grep '^{' $O/r4_bench.txt | tail -1 > $O/r4_bench_1M.json
 rm -rf $O/p_trace
-rocprofv3 --kernel-trace --stats -d $O/p_trace -o t -- python3 bench.py --partitions pipelined --no-configs --no-cpu-baseline > $O/r4_bench_pipelined_under_rocprof.txt 2>&1
+rocprofv3 --kernel-trace --stats -d $O/p_trace -o t -- python3 bench.py --full --partitions pipelined --no-configs --no-cpu-baseline > $O/r4_bench_pipelined_under_rocprof.txt 2>&1
 python3 profiles/summarize.py stats $O/p_trace/t_results.db $O/r4_bench_1M_pipelined_kernel_stats.csv
 grep '^{' $O/r4_bench_pipelined_under_rocprof.txt | tail -1 > $O/r4_bench_1M_pipelined_under_rocprof.json
 rm -rf $O/p_trace
-rocprofv3 --kernel-trace --stats -d $O/p_trace -o t -- python3 bench.py --no-configs --no-cpu-baseline > $O/r4_bench_under_rocprof.txt 2>&1
+rocprofv3 --kernel-trace --stats -d $O/p_trace -o t -- python3 bench.py --full --no-configs --no-cpu-baseline > $O/r4_bench_under_rocprof.txt 2>&1
 python3 profiles/summarize.py stats $O/p_trace/t_results.db $O/r4_bench_1M_kernel_stats.csv
 grep '^{' $O/r4_bench_under_rocprof.txt | tail -1 > $O/r4_bench_1M_under_rocprof.json
 rm -rf $O/p_trace

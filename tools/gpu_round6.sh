@@ -1,6 +1,6 @@
 #!/bin/bash
 # Round 6 measurements on the GPU box -> gpurun_out/r6_* (copied to profiles/ by the builder).
-#   bash tools/gpu_round6.sh bench    the default bench line (+ cold pass, configs)
+#   bash tools/gpu_round6.sh bench    the full bench line (--full: + cold pass, roofline, configs)
 #   bash tools/gpu_round6.sh traces   rocprofv3 --kernel-trace --stats of the headline (one stream) and the 10 M configurations
 #   bash tools/gpu_round6.sh pmc      HBM traffic per launch of the cosine kernels (FETCH_SIZE / WRITE_SIZE, separate passes)
 #   bash tools/gpu_round6.sh parity   GPU suite (plain + under FALCON_DEBUG_POISON=1), fuzz, stress
@@ -10,7 +10,7 @@ O=gpurun_out
 mkdir -p $O
 what=${1:-bench}
 if [ "$what" = bench ]; then
-  python bench.py > $O/r6_bench_1M.json 2> $O/r6_bench_1M.err; tail -2 $O/r6_bench_1M.err; python3 - <<'PY'
+  python bench.py --full > $O/r6_bench_1M.json 2> $O/r6_bench_1M.err; tail -2 $O/r6_bench_1M.err; python3 - <<'PY'
 import json
 d = json.loads(open("gpurun_out/r6_bench_1M.json").read().strip().splitlines()[-1])
 print("value", round(d["value"] / 1e6, 1), "M/s", round(d["ms_per_step"], 3), "ms; h2h", round(d.get("ms_per_step_host_to_host", 0), 2), "cold", d.get("cold_ms"))
@@ -29,9 +29,9 @@ tr() {  # name, scale_run args...
   rm -rf /tmp/p_trace
 }
 if [ "$what" = traces ]; then
-  rm -rf /tmp/p_trace
-  rocprofv3 --kernel-trace --stats -d /tmp/p_trace -o t -- python3 bench.py --partitions pipelined --no-configs --no-cpu-baseline --no-cold > $O/r6_bench_1M_pipelined_under_rocprof.json 2> /dev/null
-  python3 profiles/summarize.py stats /tmp/p_trace/t_results.db $O/r6_bench_1M_pipelined_kernel_stats.csv
+  rm -rf "$TMPDIR"/p_trace
+  rocprofv3 --kernel-trace --stats -d "$TMPDIR"/p_trace -o t -- python3 bench.py --full --partitions pipelined --no-configs --no-cpu-baseline --no-cold > $O/r6_bench_1M_pipelined_under_rocprof.json 2> /dev/null
+  python3 profiles/summarize.py stats "$TMPDIR"/p_trace/t_results.db $O/r6_bench_1M_pipelined_kernel_stats.csv
   head -4 $O/r6_bench_1M_pipelined_kernel_stats.csv | cut -c1-160
   tr 10M_f32 10000000
   tr 10M_f16_800 10000000 f32 16 f16 800

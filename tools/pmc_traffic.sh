@@ -13,7 +13,7 @@ run() {   # name, program args...
     rocprofv3 --kernel-trace --pmc WRITE_SIZE -d /tmp/pw_$name -o w -- python3 "$@" > /tmp/ow_$name.txt 2>&1
     tail -1 /tmp/of_$name.txt | cut -c1-200
 }
-run headline $R/bench.py --steps 5 --warmup 1 --no-configs --no-cpu-baseline --no-cold --partitions pipelined
+run headline $R/bench.py --full --steps 5 --warmup 1 --no-configs --no-cpu-baseline --no-cold --partitions pipelined
 run 10M_f32 $R/tools/scale_run.py 10000000
 run 10M_f32_dense $R/tools/scale_run.py 10000000 f32 32 f32 400 400 600
 run 10M_f16 $R/tools/scale_run.py 10000000 f32 16 f16 800
