@@ -88,6 +88,13 @@ _SIGNATURES = {
     "fal_cluster_graph_linkage": ([c_void_p, c_void_p, c_void_p, c_int64, c_int, c_float, c_int, c_void_p, c_void_p, c_double, c_int,
                                    c_double, c_void_p, c_void_p, c_void_p, c_void_p, P(c_int64), P(c_int64)], c_int),
     "fal_linkage_cluster": ([c_void_p, c_void_p, c_void_p, c_int64, c_int, c_float, c_int, c_void_p, P(c_int64)], c_int),
+    "fal_exact_edges": ([c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_double, c_int, c_double,
+                         c_void_p, c_void_p, c_void_p, c_int64, P(c_int64)], c_int),
+    "fal_linkage_cluster_csr": ([c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_double, c_int, c_void_p, c_void_p, c_void_p,
+                                 c_void_p, c_double, c_int, c_void_p, P(c_int64)], c_int),
+    "fal_cluster_exact": ([c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_double, c_int, c_double,
+                           c_int, c_void_p, c_void_p, c_double, c_int, c_double, c_void_p, c_void_p, c_void_p, P(c_int64),
+                           P(c_int64)], c_int),
     "fal_sort_by_precursor": ([c_void_p, c_void_p, c_int64, c_void_p, c_void_p], c_int),
     "fal_gather_f32": ([c_void_p, c_void_p, c_void_p, c_int64, c_void_p], c_int),
 }

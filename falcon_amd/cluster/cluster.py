@@ -27,6 +27,11 @@ MIN_PTS_PER_LIST = 39    # [SURVEY App. A] Faiss' minimum points per centroid
 MAX_N_LIST = 1 << 17
 
 
+class _DefaultClustering(str):
+    """AnnParams.clustering's default "dbscan" -- equal to the string, but distinguishable from an explicit choice
+    (exact mode turns the default into "hierarchical" and refuses an explicit "dbscan")"""
+
+
 @dataclass
 class AnnParams:
     """The README's nearest-neighbour options (README.md:73-79, 107-117) plus the build's."""
@@ -63,9 +68,12 @@ class AnnParams:
     rescore: bool = False         # re-score the ANN neighbours with the reference's matched-peak cosine
                                   # (similarity.py:17-80) before DBSCAN; uses fragment_tol and min_matches
     min_matches: int = 0          # (set from generate_clusters' `min_matches` when rescore is on)
-    clustering: str = "dbscan"    # "dbscan" (README.md:143-146) or "hierarchical": the snapshot's linkage + fcluster at
-                                  # the distance threshold (cluster.py:283-290) on the re-scored neighbour graph
+    clustering: str = _DefaultClustering("dbscan")    # "dbscan" (README.md:143-146) or "hierarchical": the snapshot's linkage +
+                                  # fcluster at the distance threshold (cluster.py:283-290) on the re-scored neighbour graph
     linkage: str = "complete"     # (set from generate_clusters' `linkage` when clustering == "hierarchical")
+    exact: bool = False           # exact mode: the matched-peak cosine of EVERY pair of each bucket (the snapshot's own
+                                  # condensed matrix, cluster.py:593-639), hierarchical clustering on it; no vectors, index
+                                  # or search (fal_cluster_exact).  Implies clustering "hierarchical".
 
 
 def n_list_rule(sizes: np.ndarray, n_probe: int) -> np.ndarray:
@@ -171,6 +179,8 @@ class ClusterPipeline:
         """`fal_ctx_plan` for a pass over `n` spectra: the kernels' code objects loaded, the shape-dependent scratch sized.  The
         reference calls generate_clusters ONCE per charge in a fresh process (falcon.py:153-193): the first pass is the only
         one, so it should not stop for either between its kernels.  Cheap when there is nothing left to do (every `run` calls it)."""
+        if p.exact:
+            return                       # exact mode sizes its own scratch (no vectors, index or search)
         key = (int(n), int(batch_size), p.low_dim, p.n_neighbors_ann, p.n_probe)
         if getattr(self, "_planned", None) is not None and self._planned[0] >= key[0] and self._planned[1:] == key[1:]:
             return
@@ -368,6 +378,21 @@ class ClusterPipeline:
             index.close()
         return labels, medoids, last
 
+    def _exact(self, ds, st, precursor_tol_mass, precursor_tol_mode, rt_tol, fragment_tol, p, keep_intermediates):
+        """exact mode after `_front`: every pair of every bucket scored, linkage cut at eps, refinement, exact medoids, labels
+        (fal_cluster_exact: the edges stay in library scratch).  With `keep_intermediates` the staged edge call runs as well
+        and `last` carries its CSR; `last` always carries the bucket table."""
+        c = self.ctx
+        order, mzs, rts, splits = (st[k] for k in ("order", "mzs", "rts", "splits"))
+        last = dict(order=order, mz_sorted=mzs, rt_sorted=rts, splits=splits, csr=None)
+        if keep_intermediates:
+            last["csr"] = c.exact_edges(ds.mz, ds.intensity, ds.indptr, order, splits, fragment_tol, p.min_matches, p.eps)
+        labels, medoids, lab_sorted, n_cl = c.cluster_exact(ds.mz, ds.intensity, ds.indptr, order, splits, fragment_tol,
+                                                            p.min_matches, p.eps, p.linkage, mzs, rts, precursor_tol_mass,
+                                                            precursor_tol_mode, rt_tol)
+        last.update(lab_sorted=lab_sorted, n_clusters=n_cl)
+        return labels, medoids, last
+
     def run(self, ds: SpectrumDataset, precursor_tol_mass: float, precursor_tol_mode: str,
             rt_tol: Optional[float], fragment_tol: float, batch_size: int, p: AnnParams,
             keep_intermediates: bool = False):
@@ -378,6 +403,10 @@ class ClusterPipeline:
             return c.empty((0,), torch.int32), c.empty((0,), torch.int32)
         self.plan(len(ds), batch_size, p)
         st = self._front(c, ds, precursor_tol_mass, precursor_tol_mode, rt_tol, batch_size, p)
+        if p.exact:
+            labels, medoids, self.last = self._exact(ds, st, precursor_tol_mass, precursor_tol_mode, rt_tol, fragment_tol, p,
+                                                     keep_intermediates)
+            return labels, medoids
         self._search(ds, st, precursor_tol_mass, precursor_tol_mode, rt_tol, fragment_tol, p, keep_intermediates)
         labels, medoids, self.last = self._graph(st, precursor_tol_mass, precursor_tol_mode, rt_tol, p, keep_intermediates)
         return labels, medoids
@@ -395,6 +424,16 @@ class ClusterPipeline:
         lasts[j]["rows"] (i64, device) maps them back -- the exchange step assembles the global result."""
         import torch
         c = self.ctx
+        if p.exact:
+            # exact mode: one partition after the other (no scan to overlap a front end with); not sharded
+            _refuse_sharded_exact(p, shard)
+            outs, self.lasts = [], []
+            for ds in datasets:
+                outs.append(self.run(ds, precursor_tol_mass, precursor_tol_mode, rt_tol, fragment_tol, batch_size, p))
+                self.lasts.append(self.last if len(ds) > 0 else {})
+            if self.lasts:
+                self.last = self.lasts[-1]
+            return outs
         args = (precursor_tol_mass, precursor_tol_mode, rt_tol)
         live = [i for i, ds in enumerate(datasets) if len(ds) > 0]
         if live:
@@ -486,7 +525,8 @@ class ClusterPipeline:
         -> [(labels i32[N_j] by dataset row, medoids i32[n_labels_j] dataset rows)] per dataset."""
         import torch
         c = self.ctx
-        if n_chunks <= 1:
+        if n_chunks <= 1 or p.exact:
+            # (exact mode holds no vectors, index or hand-off buffers: its working set is the edges, one pass)
             return self.run_many(datasets, precursor_tol_mass, precursor_tol_mode, rt_tol, fragment_tol, batch_size, p)
         labels = [torch.full((len(ds),), -1, dtype=torch.int32, device=c.tdev) for ds in datasets]
         medoids = [[] for _ in datasets]
@@ -499,6 +539,12 @@ class ClusterPipeline:
                 on_chunk(ch, outs, self.lasts)
             del outs
         return [(labels[j], torch.cat(medoids[j]) if medoids[j] else c.empty((0,), torch.int32)) for j in range(len(datasets))]
+
+
+def _refuse_sharded_exact(p, shard):
+    if p.exact and shard is not None and shard[1] > 1:
+        raise ValueError("exact mode (AnnParams(exact=True) / --exact) runs on one GPU: the multi-GPU path exchanges nearest-"
+                         "neighbour lists, which exact mode does not build")
 
 
 def _merge_share(labels, medoids, off, outs, lasts):
@@ -573,9 +619,10 @@ class PartitionRunner:
         import torch
         if not inputs_ready:
             torch.cuda.current_stream(self.device).synchronize()      # inputs produced on the caller's stream
+        p = args[5] if len(args) > 5 else kwargs["p"]
+        _refuse_sharded_exact(p, shard)
         order = sorted(range(len(datasets)), key=lambda i: -len(datasets[i]))
         shards = [shard] * len(datasets)
-        p = args[5]
         if shard is not None and shard[1] > 1 and p.mz_interval and p.mz_interval > 0:
             # one deal for the whole job (`distributed.deal_job` over every partition's windows), then a slot per partition
             if not hasattr(self, "_planner"):
@@ -634,8 +681,8 @@ class PartitionRunner:
         through `run(shard=(c, n_chunks))`.  Same partition as one pass; cluster ids are share-major.
         -> [(labels i32[N_j] by dataset row, medoids i32[n_labels_j] dataset rows)] per dataset."""
         import torch
-        if n_chunks <= 1:
-            return self.run(datasets, *args, **kwargs)
+        if n_chunks <= 1 or (args[5] if len(args) > 5 else kwargs["p"]).exact:
+            return self.run(datasets, *args, **kwargs)         # (exact mode: one pass, as ClusterPipeline.run_chunked)
         dev = torch.device("cuda", self.device)
         labels = [torch.full((len(ds),), -1, dtype=torch.int32, device=dev) for ds in datasets]
         medoids = [[] for _ in datasets]
@@ -687,6 +734,11 @@ def generate_clusters(dataset, linkage: str, distance_threshold: float, min_matc
         p = dataclasses.replace(ann)                 # never mutate the caller's parameters
     if p.rescore:
         p.min_matches = int(min_matches)
+    if p.exact:
+        if p.clustering == "dbscan" and not isinstance(p.clustering, _DefaultClustering):
+            raise ValueError("exact mode clusters the all-pairs distances hierarchically (the snapshot's linkage); "
+                             "AnnParams(exact=True) does not combine with clustering=\"dbscan\"")
+        p.clustering = "hierarchical"
     if p.clustering not in ("dbscan", "hierarchical"):
         raise ValueError(f"unknown clustering {p.clustering!r}")
     if p.clustering == "hierarchical":

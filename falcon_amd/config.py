@@ -48,6 +48,10 @@ class Config:
                        help="dbscan (README: density clustering of the neighbour graph, default) or hierarchical "
                             "(the snapshot's linkage + cut at the distance threshold, on the re-scored neighbour graph; "
                             "implies --rescore).")
+        p.add_argument("--exact", action="store_true",
+                       help="Exact mode: the matched-peak cosine of every pair inside each precursor bucket, then the "
+                            "snapshot's hierarchical clustering (--linkage) on those distances; no vectors, index or "
+                            "nearest-neighbour search.  Implies --clustering hierarchical.")
         p.add_argument("--distance_threshold", type=float, default=0.1,
                        help="Cosine distance threshold; alias of --eps (default: 0.1).")
         p.add_argument("--eps", type=float, default=None,
@@ -141,6 +145,11 @@ class Config:
             ns["distance_threshold"] = ns["eps"]
         # the reference's --linkage values keep their meaning: a non-default linkage selects the hierarchical clustering;
         # with an explicit --clustering dbscan (which has no linkage) the command line fails here, not per charge later
+        if ns["exact"]:
+            if ns["clustering"] == "dbscan":
+                self._parser.error("--exact clusters the all-pairs distances hierarchically: it does not combine with "
+                                   "--clustering dbscan")
+            ns["clustering"] = "hierarchical"
         if ns["clustering"] is None:
             ns["clustering"] = "hierarchical" if ns["linkage"] != "complete" else "dbscan"
         elif ns["clustering"] == "dbscan" and ns["linkage"] != "complete":

@@ -37,6 +37,7 @@ void set_error(const char* fmt, ...);
     } while (0)
 
 constexpr int kNumStages = 9;
+constexpr int kNumSlots = 37;   // scratch slots of a context (ivf.h names them)
 enum Stage { ST_VECTORIZE = 0, ST_BUILD = 1, ST_COARSE = 2, ST_SCAN = 3, ST_SELECT = 4,
              ST_FILTER = 5, ST_DBSCAN = 6, ST_TAIL = 7,
              ST_KERNEL = 8 };   // the launches of the cosine kernel alone (dense_kernel / scan16_kernel / list16_kernel / ivf_list4_kernel;
@@ -71,7 +72,7 @@ struct fal_ctx {
         std::vector<std::pair<hipEvent_t, hipEvent_t>> ev;
         size_t used = 0;
     } timers[fal::kNumStages];
-    fal::Scratch scratch[32];
+    fal::Scratch scratch[fal::kNumSlots];
     int32_t* fb_host = nullptr;           // pinned, 16 words, zeroed at creation: [0] / [2] fallback queries of the last prefiltered
                                           // search (flat / IVF buckets), [1] ambiguous rows of the last k-means pass
     int32_t* zero_dev = nullptr;          // 16 zero words on the device (stream-ordered resets of fb_host)
@@ -94,8 +95,8 @@ struct fal_ctx {
     bool debug_poison = false;
     int call_depth = 0;
     uint64_t call_epoch = 1;
-    uint64_t slot_epoch[32] = {};
-    uint32_t slot_gen[32] = {};
+    uint64_t slot_epoch[fal::kNumSlots] = {};
+    uint32_t slot_gen[fal::kNumSlots] = {};
     std::vector<void*> retired;
     std::vector<bool> retired_held;       // parallel to `retired`: the slot had been reserved in the call that retired the block
     void release_retired();

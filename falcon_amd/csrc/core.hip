@@ -308,7 +308,7 @@ int fal_ctx_plan(fal_ctx* c, int64_t n, int low_dim, int k_ann, int n_probe, int
     }
     // per-row arrays of the graph stages (graph.hip, tail.hip): labels, parents, segment tables
     for (int slot : {SLOT_DB, SLOT_DB2, SLOT_TAIL, SLOT_TAIL2, SLOT_FIN, SLOT_FIN2}) FAL_TRY(c->reserve(slot, 8 * nn + 4096, &p));
-    for (int slot = 0; slot < 32; ++slot) c->release(slot);      // (no pointer is held: the passes may still grow them)
+    for (int slot = 0; slot < fal::kNumSlots; ++slot) c->release(slot);      // (no pointer is held: the passes may still grow them)
     return FAL_OK;
 }
 

@@ -20,6 +20,7 @@
 #include "common.h"
 #include "ivf.h"
 #include "util.h"
+#include "peakmatch.h"
 
 namespace fal {
 
@@ -80,6 +81,16 @@ __global__ void lk_edges_kernel(const int32_t* __restrict__ nb_idx, const float*
     }
 }
 
+// the same over a symmetric CSR of float64 distances (exact mode: ids in sorted-row space, rows of the CSR = rows here)
+__global__ void lk_edges_csr_kernel(const int64_t* __restrict__ ptr, const int32_t* __restrict__ idx, const double* __restrict__ dist,
+                                    int64_t n, double t, int32_t* __restrict__ parent) {
+    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
+        for (int64_t e = ptr[i]; e < ptr[i + 1]; ++e) {
+            const int32_t j = idx[e];
+            if (j >= 0 && (int64_t)j < n && (int64_t)j != i && dist[e] <= t) lk_union(parent, (int32_t)i, j);
+        }
+}
+
 __global__ void lk_roots_kernel(int32_t* __restrict__ parent, int32_t* __restrict__ count, int64_t n) {
     for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
         const int32_t root = lk_find_final(parent, (int32_t)i);
@@ -126,7 +137,9 @@ __global__ void lk_single_kernel(const int32_t* __restrict__ parent, const int32
 
 // one wave per component: method 1 = complete, 2 = average
 __global__ __launch_bounds__(64) void lk_agglomerate_kernel(const int32_t* __restrict__ nb_idx, const float* __restrict__ nb_dist,
-                                                            int64_t n, int k, double t, int method, const int32_t* __restrict__ parent,
+                                                            int64_t n, int k, const int64_t* __restrict__ csr_ptr,
+                                                            const int32_t* __restrict__ csr_idx, const double* __restrict__ csr_dist,
+                                                            double t, int method, const int32_t* __restrict__ parent,
                                                             const int32_t* __restrict__ count, const int32_t* __restrict__ comp_root,
                                                             const int64_t* __restrict__ moff, const int64_t* __restrict__ qoff,
                                                             const int32_t* __restrict__ mem, int32_t* __restrict__ mem_sorted,
@@ -155,11 +168,19 @@ __global__ __launch_bounds__(64) void lk_agglomerate_kernel(const int32_t* __res
         a_sz[x] = 1;
         a_cl[x] = x;
     }
-    // (D arrives filled with 1.0: missing pair = distance 1, lk_fill_kernel)
+    // (D arrives filled with 1.0: missing pair = distance 1, lk_fill_kernel -- or with every exact distance, lk_exact_fill_kernel:
+    // then there is no edge source to read)
     __threadfence_block();
     __syncthreads();
     for (int a = 0; a < m; ++a) {
         const int64_t row = ms[a];
+        if (csr_ptr) {
+            for (int64_t e = csr_ptr[row] + lane; e < csr_ptr[row + 1]; e += 64) {
+                const int32_t j = csr_idx[e];
+                if (j >= 0 && (int64_t)j < n && (int64_t)j != row && parent[j] == root) D[(int64_t)a * m + lidx[j]] = csr_dist[e];
+            }
+            continue;
+        }
         for (int s = lane; s < k; s += 64) {
             const int32_t j = nb_idx[row * k + s];
             if (j >= 0 && (int64_t)j < n && (int64_t)j != row && parent[j] == root) D[(int64_t)a * m + lidx[j]] = (double)nb_dist[row * k + s];
@@ -236,7 +257,9 @@ __global__ __launch_bounds__(64) void lk_agglomerate_kernel(const int32_t* __res
 // partner was one of the merged pair are searched again (a wave per row), the others are updated in place (a new value can
 // only tie the cached one: complete and average linkage are reducible, d(a + b, c) >= min(d(a, c), d(b, c))).
 __global__ __launch_bounds__(1024) void lk_agglomerate_big_kernel(const int32_t* __restrict__ nb_idx, const float* __restrict__ nb_dist,
-                                                                  int64_t n, int k, double t, int method, const int32_t* __restrict__ parent,
+                                                                  int64_t n, int k, const int64_t* __restrict__ csr_ptr,
+                                                                  const int32_t* __restrict__ csr_idx, const double* __restrict__ csr_dist,
+                                                                  double t, int method, const int32_t* __restrict__ parent,
                                                                   const int32_t* __restrict__ count, const int32_t* __restrict__ big,
                                                                   const int64_t* __restrict__ moff, const int64_t* __restrict__ qoff,
                                                                   const int32_t* __restrict__ mem, int32_t* __restrict__ mem_sorted,
@@ -278,6 +301,15 @@ __global__ __launch_bounds__(1024) void lk_agglomerate_big_kernel(const int32_t*
         a_cl[x] = x;
     }
     sync();
+    if (csr_ptr) {                                          // (CSR source: one wave per member row)
+        for (int a = w; a < m; a += W) {
+            const int64_t row = ms[a];
+            for (int64_t e = csr_ptr[row] + lane; e < csr_ptr[row + 1]; e += 64) {
+                const int32_t j = csr_idx[e];
+                if (j >= 0 && (int64_t)j < n && (int64_t)j != row && parent[j] == root) D[(int64_t)a * m + lidx[j]] = csr_dist[e];
+            }
+        }
+    }
     for (int64_t e = tid; e < (int64_t)m * k; e += T) {     // stored edges inside the group (D arrives filled with 1.0)
         const int a = (int)(e / k), s = (int)(e % k);
         const int64_t row = ms[a];
@@ -398,6 +430,51 @@ __global__ __launch_bounds__(1024) void lk_agglomerate_big_kernel(const int32_t*
     }
 }
 
+// exact mode, average linkage: the matrix of a component holds the exact distance of EVERY member pair (heights above t enter
+// the Lance-Williams averages).  Members in ascending row order first (the agglomeration kernels rank them the same way again).
+__global__ __launch_bounds__(64) void lk_rank_kernel(const int32_t* __restrict__ comp_root, const int32_t* __restrict__ count,
+                                                     const int64_t* __restrict__ moff, const int32_t* __restrict__ mem,
+                                                     int32_t* __restrict__ mem_sorted) {
+    const int32_t root = comp_root[blockIdx.x];
+    const int m = count[root];
+    const int32_t* mu = mem + moff[root];
+    for (int x = threadIdx.x; x < m; x += 64) {
+        const int32_t rx = mu[x];
+        int rank = 0;
+        for (int y = 0; y < m; ++y) rank += mu[y] < rx;
+        mem_sorted[moff[root] + rank] = rx;
+    }
+}
+
+// one thread per matrix cell of every component (cells of component c: qoff[comp_root[c]] ..); the lower row of a pair is the
+// query spectrum, as in the reference's condensed matrix (cluster.py:593-639: cosine_fast(i, j) for i < j)
+__global__ __launch_bounds__(256) void lk_exact_fill_kernel(int64_t n_comp, const int32_t* __restrict__ comp_root,
+                                                            const int32_t* __restrict__ count, const int64_t* __restrict__ moff,
+                                                            const int64_t* __restrict__ qoff, const int32_t* __restrict__ mem_sorted,
+                                                            int64_t n_sq, ExactPeaks pk, double* __restrict__ Dall) {
+    for (int64_t c = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; c < n_sq; c += (int64_t)gridDim.x * blockDim.x) {
+        int64_t lo = 0, hi = n_comp - 1;                    // the last component whose first cell is <= c
+        while (lo < hi) {
+            const int64_t mid = (lo + hi + 1) >> 1;
+            if (qoff[comp_root[mid]] <= c) lo = mid;
+            else hi = mid - 1;
+        }
+        const int32_t root = comp_root[lo];
+        const int m = count[root];
+        const int64_t q = c - qoff[root];
+        const int a = (int)(q / m), b = (int)(q % m);
+        double* D = Dall + qoff[root];
+        if (a == b) D[q] = 0.0;
+        if (a >= b) continue;
+        const int32_t* ms = mem_sorted + moff[root];
+        bool ok = true;
+        const double d = exact_distance(pk, ms[a], ms[b], &ok);
+        if (!ok) atomicExch(pk.err, 1);
+        D[(int64_t)a * m + b] = d;
+        D[(int64_t)b * m + a] = d;
+    }
+}
+
 __global__ void lk_isrep_kernel(const int32_t* __restrict__ rep, int64_t n, int32_t* __restrict__ is_rep) {
     for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
         is_rep[i] = rep[i] == (int32_t)i;
@@ -411,8 +488,11 @@ __global__ void lk_label_kernel(const int32_t* __restrict__ rep, const int64_t* 
 
 // labels + cluster count on the device (the interface of dbscan_dev); synchronises once for the scratch sizes of the
 // complete / average forms
-int linkage_dev(fal_ctx* ctx, const int32_t* nb_idx, const float* nb_dist, int64_t n, int k, float t, int method,
-                int32_t* labels, int64_t** d_count_out) {
+int linkage_dev_src(fal_ctx* ctx, const LinkageSource& src, int64_t n, double t, int method, int32_t* labels,
+                    int64_t** d_count_out) {
+    const int32_t* nb_idx = src.nb_idx;
+    const float* nb_dist = src.nb_dist;
+    const int k = src.csr_ptr || src.exact_fill ? 0 : src.k;
     hipStream_t st = ctx->stream;
     int32_t* buf = nullptr;
     int64_t* rank = nullptr;
@@ -420,11 +500,14 @@ int linkage_dev(fal_ctx* ctx, const int32_t* nb_idx, const float* nb_dist, int64
     FAL_TRY(ctx->reserve(SLOT_DB2, sizeof(int64_t) * (size_t)(n + 1), (void**)&rank));
     int32_t *parent = buf, *count = buf + n, *rep = buf + 2 * n, *flag = buf + 3 * n;
     const int grid = (int)std::min<int64_t>(ceil_div(n, 256), (int64_t)ctx->num_cus * 16);
-    const int egrid = (int)std::min<int64_t>(ceil_div(n * k, 256), (int64_t)ctx->num_cus * 32);
+    const int egrid = (int)std::min<int64_t>(ceil_div(n * src.k, 256), (int64_t)ctx->num_cus * 32);
     ctx->stage_reset(ST_DBSCAN);
     StageScope ts(ctx, ST_DBSCAN);
     hipLaunchKernelGGL(lk_init_kernel, dim3(grid), dim3(256), 0, st, parent, count, rep, n);
-    hipLaunchKernelGGL(lk_edges_kernel, dim3(egrid), dim3(256), 0, st, nb_idx, nb_dist, n, k, t, parent);
+    if (src.csr_ptr)
+        hipLaunchKernelGGL(lk_edges_csr_kernel, dim3(grid), dim3(256), 0, st, src.csr_ptr, src.csr_idx, src.csr_dist, n, t, parent);
+    else
+        hipLaunchKernelGGL(lk_edges_kernel, dim3(egrid), dim3(256), 0, st, nb_idx, nb_dist, n, src.k, (float)t, parent);
     hipLaunchKernelGGL(lk_roots_kernel, dim3(grid), dim3(256), 0, st, parent, count, n);
     if (method == 0) {
         hipLaunchKernelGGL(lk_single_kernel, dim3(grid), dim3(256), 0, st, parent, count, n, rep);
@@ -466,14 +549,23 @@ int linkage_dev(fal_ctx* ctx, const int32_t* nb_idx, const float* nb_dist, int64
             int32_t *lidx = todo + n_mem, *cursor = lidx + n, *comp_root = cursor + n;
             double* nnv = D + n_sq;
             FAL_CHECK_HIP(hipMemsetAsync(cursor, 0, sizeof(int32_t) * (size_t)n, st));
-            hipLaunchKernelGGL(lk_fill_kernel, dim3((unsigned)std::min<int64_t>(ceil_div(n_sq, 256), (int64_t)ctx->num_cus * 32)), dim3(256), 0, st,
-                               D, n_sq);
+            const unsigned qgrid = (unsigned)std::min<int64_t>(ceil_div(n_sq, 256), (int64_t)ctx->num_cus * 32);
             hipLaunchKernelGGL(lk_scatter_kernel, dim3(grid), dim3(256), 0, st, parent, count, n, moff, cursor, mem, crank, comp_root);
-            hipLaunchKernelGGL(lk_agglomerate_kernel, dim3((unsigned)n_comp), dim3(64), 0, st, nb_idx, nb_dist, n, k, (double)t, method,
-                               parent, count, comp_root, moff, qoff, mem, mem_sorted, lidx, act, sz, cl, D, rep);
+            const int64_t* cp = src.csr_ptr;
+            if (src.exact_fill) {                           // every member pair scored again (average linkage of exact mode)
+                hipLaunchKernelGGL(lk_rank_kernel, dim3((unsigned)n_comp), dim3(64), 0, st, comp_root, count, moff, mem, mem_sorted);
+                hipLaunchKernelGGL(lk_exact_fill_kernel, dim3(qgrid), dim3(256), 0, st, n_comp, comp_root, count, moff, qoff, mem_sorted,
+                                   n_sq, src.peaks, D);
+                cp = nullptr;
+            } else {
+                hipLaunchKernelGGL(lk_fill_kernel, dim3(qgrid), dim3(256), 0, st, D, n_sq);
+            }
+            hipLaunchKernelGGL(lk_agglomerate_kernel, dim3((unsigned)n_comp), dim3(64), 0, st, nb_idx, nb_dist, n, k, cp, src.csr_idx,
+                               src.csr_dist, t, method, parent, count, comp_root, moff, qoff, mem, mem_sorted, lidx, act, sz, cl, D, rep);
             if (n_big > 0)
-                hipLaunchKernelGGL(lk_agglomerate_big_kernel, dim3((unsigned)n_big), dim3(1024), 0, st, nb_idx, nb_dist, n, k, (double)t,
-                                   method, parent, count, big, moff, qoff, mem, mem_sorted, lidx, act, sz, cl, nni, todo, nnv, D, rep);
+                hipLaunchKernelGGL(lk_agglomerate_big_kernel, dim3((unsigned)n_big), dim3(1024), 0, st, nb_idx, nb_dist, n, k, cp,
+                                   src.csr_idx, src.csr_dist, t, method, parent, count, big, moff, qoff, mem, mem_sorted, lidx, act, sz,
+                                   cl, nni, todo, nnv, D, rep);
         }
     }
     hipLaunchKernelGGL(lk_isrep_kernel, dim3(grid), dim3(256), 0, st, rep, n, flag);
@@ -484,6 +576,15 @@ int linkage_dev(fal_ctx* ctx, const int32_t* nb_idx, const float* nb_dist, int64
     // the agglomeration's work arrays are dead on the host side (their kernels are enqueued): the tail stage reuses the slots
     for (int slot : {SLOT_TAIL, SLOT_TAIL2, SLOT_TAIL3, SLOT_TAIL4, SLOT_DB3}) ctx->release(slot);
     return FAL_OK;
+}
+
+int linkage_dev(fal_ctx* ctx, const int32_t* nb_idx, const float* nb_dist, int64_t n, int k, float t, int method,
+                int32_t* labels, int64_t** d_count_out) {
+    LinkageSource src;
+    src.nb_idx = nb_idx;
+    src.nb_dist = nb_dist;
+    src.k = k;
+    return linkage_dev_src(ctx, src, n, (double)t, method, labels, d_count_out);
 }
 
 }  // namespace fal

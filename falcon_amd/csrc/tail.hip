@@ -528,7 +528,8 @@ int fal::refine_dev(fal_ctx* ctx, int32_t* labels, int64_t n, const float* mz, c
 // a11 + a12 on a device-resident cluster count; the number of noise rows is left at *d_noise_out
 int fal::finalize_dev(fal_ctx* ctx, const int32_t* labels_sorted, int64_t n, const int64_t* d_count,
                       const int64_t* row_order, const int32_t* nb_idx, const float* nb_dist, int k,
-                      int32_t* labels_out, int32_t* medoids_out, int64_t** d_noise_out, const int32_t* extent) {
+                      int32_t* labels_out, int32_t* medoids_out, int64_t** d_noise_out, const int32_t* extent,
+                      const ExactPeaks* exact) {
     hipStream_t st = ctx->stream;
     const int64_t cmax = n + 1;               // fal_finalize accepts any n_clusters <= n (single-member clusters included)
     int32_t *size = nullptr, *noise = nullptr;
@@ -544,7 +545,9 @@ int fal::finalize_dev(fal_ctx* ctx, const int32_t* labels_sorted, int64_t n, con
     {
         StageScope ts(ctx, ST_TAIL);
         hipLaunchKernelGGL(cluster_size_kernel, dim3(grid), dim3(256), 0, st, labels_sorted, n, size, row_order, noise);
-        if (extent)
+        if (exact)
+            FAL_TRY(exact_medoids_dev(ctx, *exact, labels_sorted, n, size, best));
+        else if (extent)
             hipLaunchKernelGGL(medoid_score_rows_kernel, dim3((unsigned)std::min<int64_t>(ceil_div(n, 256), (int64_t)ctx->num_cus * 32)),
                                dim3(256), 0, st, labels_sorted, n, nb_idx, nb_dist, k, extent, size, best);
         else

@@ -1,6 +1,7 @@
 // Small shared launch helpers (implemented in sortutil.hip).
 #pragma once
 #include "common.h"
+#include "peakmatch.h"
 
 namespace fal {
 // out[0..n) = exclusive prefix of in (int32 flags/counts), out[n] = total (all on device)
@@ -16,9 +17,29 @@ int dbscan_dev(fal_ctx* ctx, const int32_t* nb_idx, const float* nb_dist, int64_
 // f4: hierarchical clustering of the neighbour graph cut at t (linkage.hip): method 0 single, 1 complete, 2 average
 int linkage_dev(fal_ctx* ctx, const int32_t* nb_idx, const float* nb_dist, int64_t n, int k, float t, int method, int32_t* labels,
                 int64_t** d_count_out);
+// the edge source of linkage_dev_src: the ANN's ELL lists (float32), or exact mode's symmetric CSR (float64, sorted-row ids);
+// exact_fill: every member pair of a component is scored again from `peaks` (average linkage), *err set on a component of
+// more than kMaxComp peaks (peaks.err)
+struct LinkageSource {
+    const int32_t* nb_idx = nullptr;
+    const float* nb_dist = nullptr;
+    int k = 0;
+    const int64_t* csr_ptr = nullptr;
+    const int32_t* csr_idx = nullptr;
+    const double* csr_dist = nullptr;
+    bool exact_fill = false;
+    ExactPeaks peaks{};
+};
+int linkage_dev_src(fal_ctx* ctx, const LinkageSource& src, int64_t n, double t, int method, int32_t* labels,
+                    int64_t** d_count_out);
 int refine_dev(fal_ctx* ctx, int32_t* labels, int64_t n, const float* mz, const float* rt, double tol, int is_da,
                double rt_tol, const int64_t* d_count_in, int64_t** d_count_out);
 int finalize_dev(fal_ctx* ctx, const int32_t* labels_sorted, int64_t n, const int64_t* d_count,
                  const int64_t* row_order, const int32_t* nb_idx, const float* nb_dist, int k, int32_t* labels_out,
-                 int32_t* medoids_out, int64_t** d_noise_out, const int32_t* extent = nullptr);
+                 int32_t* medoids_out, int64_t** d_noise_out, const int32_t* extent = nullptr,
+                 const ExactPeaks* exact = nullptr);
+// exact mode's medoid scores (exact.hip): per member, the float32 sum in ascending member order of float32(d) to every other
+// member of its cluster, all pairs scored again; argmin per cluster into best (score bits, row), ties to the lowest row
+int exact_medoids_dev(fal_ctx* ctx, const ExactPeaks& pk, const int32_t* labels_sorted, int64_t n, const int32_t* size,
+                      unsigned long long* best);
 }  // namespace fal

@@ -389,6 +389,68 @@ class Context:
                                            self.LINKAGE[linkage], self._p(labels), C.byref(nc)), "fal_linkage_cluster")
         return labels, int(nc.value)
 
+    # ------------------------------------------------------------------ f5 exact mode
+    def _peaks(self, mz, intensity, indptr, order):
+        torch = _torch()
+        return (self.to_dev(mz, torch.float32), self.to_dev(intensity, torch.float32), self.to_dev(indptr, torch.int64),
+                self.to_dev(order, torch.int64))
+
+    def exact_edges(self, mz, intensity, indptr, order, splits, fragment_tol: float, min_matches: int, threshold: float,
+                    max_edges: Optional[int] = None):
+        """f5 staged (`fal_exact_edges`): every pair of every bucket of `splits` scored with the matched-peak cosine
+        -> symmetric CSR of the pairs with d <= threshold in sorted-row space: (indptr i64[n+1], idx i32[m], dist f64[m]).
+        `max_edges` (directed entries) defaults to every pair of the buckets."""
+        torch = _torch()
+        mz, intensity, indptr, order = self._peaks(mz, intensity, indptr, order)
+        n = order.numel()
+        sp = np.ascontiguousarray(splits, dtype=np.int64)
+        if max_edges is None:
+            nb = np.diff(sp)
+            max_edges = int((nb * (nb - 1)).sum())
+        ptr = self.empty((n + 1,), torch.int64)
+        idx = self.empty((max(max_edges, 1),), torch.int32)
+        dist = self.empty((max(max_edges, 1),), torch.float64)
+        m = C.c_int64()
+        check(self.lib.fal_exact_edges(self._h, self._p(mz), self._p(intensity), self._p(indptr), self._p(order), n,
+                                       sp.ctypes.data_as(C.c_void_p), len(sp), float(fragment_tol), int(min_matches),
+                                       float(threshold), self._p(ptr), self._p(idx), self._p(dist), int(max_edges), C.byref(m)),
+              "fal_exact_edges")
+        return ptr, idx[:m.value], dist[:m.value]
+
+    def linkage_cluster_csr(self, indptr_csr, idx, dist, threshold: float, linkage: str, mz=None, intensity=None, indptr=None,
+                            order=None, fragment_tol: float = 0.0, min_matches: int = 0):
+        """f5 staged (`fal_linkage_cluster_csr`): `linkage_cluster` on exact mode's CSR; average linkage needs the peaks
+        (every member pair of a connected group is scored again).  -> labels i32[n], n_clusters"""
+        torch = _torch()
+        n = indptr_csr.numel() - 1
+        peaks = (None,) * 4 if mz is None else self._peaks(mz, intensity, indptr, order)
+        labels = self.empty((max(n, 1),), torch.int32)
+        nc = C.c_int64()
+        check(self.lib.fal_linkage_cluster_csr(self._h, self._p(indptr_csr), self._p(idx), self._p(dist), n, float(threshold),
+                                               self.LINKAGE[linkage], *(self._p(t) for t in peaks), float(fragment_tol),
+                                               int(min_matches), self._p(labels), C.byref(nc)), "fal_linkage_cluster_csr")
+        return labels[:n], int(nc.value)
+
+    def cluster_exact(self, mz, intensity, indptr, order, splits, fragment_tol: float, min_matches: int, threshold: float,
+                      linkage: str, mz_sorted, rt_sorted, tol: float, mode: str, rt_tol):
+        """f5 fused (`fal_cluster_exact`): all-pairs edges -> linkage -> refinement -> exact medoids -> labels.
+        -> labels i32[n] (dataset rows), medoids i32[n_labels], labels_sorted, n_clusters (as `cluster_graph`)"""
+        torch = _torch()
+        mz, intensity, indptr, order = self._peaks(mz, intensity, indptr, order)
+        n = order.numel()
+        sp = np.ascontiguousarray(splits, dtype=np.int64)
+        lab_sorted = self.empty((n,), torch.int32)
+        labels = self.empty((n,), torch.int32)
+        medoids = self.empty((n,), torch.int32)
+        nc, nl = C.c_int64(), C.c_int64()
+        check(self.lib.fal_cluster_exact(self._h, self._p(mz), self._p(intensity), self._p(indptr), self._p(order), n,
+                                         sp.ctypes.data_as(C.c_void_p), len(sp), float(fragment_tol), int(min_matches),
+                                         float(threshold), self.LINKAGE[linkage], self._p(mz_sorted), self._p(rt_sorted),
+                                         float(tol), int(mode == "Da"), -1.0 if rt_tol is None else float(rt_tol),
+                                         self._p(lab_sorted), self._p(labels), self._p(medoids), C.byref(nc), C.byref(nl)),
+              "fal_cluster_exact")
+        return labels, medoids[:int(nl.value)], lab_sorted, int(nc.value)
+
 
 class IvfIndex:
     """Opaque `fal_ivf` handle (keeps the vectors alive: the index borrows them)."""

@@ -342,6 +342,33 @@ int fal_cluster_graph_linkage(fal_ctx* ctx, const int32_t* nb_idx, const float* 
                               const int64_t* row_order, int32_t* labels_sorted_scratch, int32_t* labels_out,
                               int32_t* medoids_out, int64_t* n_clusters /*[host]*/, int64_t* n_labels /*[host]*/);
 
+/* ---- f5  exact mode: the snapshot's own clustering -- the matched-peak cosine (fal_rescore_neighbors' arithmetic) of EVERY
+ *          pair inside every bucket [splits[b], splits[b + 1]) of the bucket table (splits [host], first 0, last n), then the
+ *          hierarchical clustering cut at threshold < 1 (cluster.py:212-331, 593-639).  Rows and ids are sorted positions;
+ *          row_order maps them to the rows of the peaks CSR (mz / intensity f32, indptr i64).  A pair whose peaks chain into a
+ *          component of more than 32 peaks a side fails the call with FAL_EUNSUPPORTED, as in fal_rescore_neighbors.
+ *          fal_exact_edges: the pairs with d = 1 - sim <= threshold (sim = 0 below min_matches) as a symmetric CSR,
+ *          rows and columns ascending: csr_indptr i64[n+1], csr_idx i32 / csr_dist f64 [max_edges]; *n_edges = directed
+ *          entries (FAL_EINVAL with *n_edges set when they exceed max_edges: call again with room for them).
+ *          fal_linkage_cluster_csr: fal_linkage_cluster's contract on that CSR; average linkage (method 2) scores every
+ *          member pair of a connected group again (the peak arguments are needed for it only).
+ *          fal_cluster_exact: edges -> linkage -> fal_refine_clusters -> medoids over all member pairs (float32 sums in
+ *          ascending member order, ties to the lowest row) -> fal_finalize's labels; the edges stay in library scratch.
+ *          [dev] except splits and the counts */
+int fal_exact_edges(fal_ctx* ctx, const float* mz, const float* intensity, const int64_t* indptr, const int64_t* row_order,
+                    int64_t n, const int64_t* splits /*[host]*/, int64_t n_splits, double fragment_tol, int min_matches,
+                    double threshold, int64_t* csr_indptr, int32_t* csr_idx, double* csr_dist, int64_t max_edges,
+                    int64_t* n_edges /*[host]*/);
+int fal_linkage_cluster_csr(fal_ctx* ctx, const int64_t* csr_indptr, const int32_t* csr_idx, const double* csr_dist, int64_t n,
+                            double threshold, int method, const float* mz, const float* intensity, const int64_t* indptr,
+                            const int64_t* row_order, double fragment_tol, int min_matches, int32_t* labels,
+                            int64_t* n_clusters /*[host]*/);
+int fal_cluster_exact(fal_ctx* ctx, const float* mz, const float* intensity, const int64_t* indptr, const int64_t* row_order,
+                      int64_t n, const int64_t* splits /*[host]*/, int64_t n_splits, double fragment_tol, int min_matches,
+                      double threshold, int method, const float* precursor_mz_sorted, const float* rt_sorted, double tol,
+                      int tol_is_da, double rt_tol, int32_t* labels_sorted_scratch, int32_t* labels_out, int32_t* medoids_out,
+                      int64_t* n_clusters /*[host]*/, int64_t* n_labels /*[host]*/);
+
 /* ---- f1  spectrum preprocessing, the step in front of the path: reference
  *          spectrum.py:73-169 `process_spectrum` over a CSR of raw peaks (m/z float64
  *          sorted per spectrum, intensity float32): m/z range cut (135), precursor-peak
