@@ -226,8 +226,12 @@ class ClusterPipeline:
                 ds._pmz_dev = c.to_dev(ds.precursor_mz, torch.float32)
         counts = c.window_counts([getattr(ds, "_pmz_dev", None) if ds.on_host() else ds.precursor_mz for ds in datasets],
                                  p.mz_interval)
-        # (`tol` = (precursor tolerance, mode): the cost model then prices the stored neighbours too)
-        costs = fdist.window_costs(counts, batch_size, p.n_probe, p.mz_interval, tol, p.n_neighbors_ann, p.n_neighbors)
+        # (`tol` = (precursor tolerance, mode): the cost model then prices the stored neighbours too; exact mode prices the
+        # pairs of every bucket instead)
+        if p.exact:
+            costs = fdist.exact_window_costs(counts, batch_size)
+        else:
+            costs = fdist.window_costs(counts, batch_size, p.n_probe, p.mz_interval, tol, p.n_neighbors_ann, p.n_neighbors)
         return fdist.deal_job(list(costs), world)
 
     def _front_windows(self, c, ds, precursor_tol_mass, precursor_tol_mode, rt_tol, batch_size, p, shard, owner=None):
@@ -274,14 +278,17 @@ class ClusterPipeline:
     def _restrict(self, c, st, p, shard):
         """One dataset on several GPUs (reference analogue: blocks are clustered independently and only
         their labels are offset afterwards, cluster.py:115-155).  Every rank derived the SAME buckets in `_front`;
-        buckets are dealt to ranks by longest-processing-time on `distributed.bucket_costs`, and this rank keeps the
-        rows of its own buckets: st becomes the state of that subset (buckets whole and in order), plus
+        buckets are dealt to ranks by longest-processing-time on `distributed.bucket_costs` (exact mode:
+        `distributed.exact_bucket_costs`), and this rank keeps the rows of its own buckets: st becomes the state of that
+        subset (buckets whole and in order), plus
         `rows` (i64, device: dataset rows of the subset in sorted order) and `n_total`."""
         import torch
         from .. import distributed as fdist
         rank, world = shard
         splits = np.asarray(st["splits"], np.int64)
-        owner = fdist.shard_units(fdist.bucket_costs(np.diff(splits), st["n_list"], p.n_probe), world)
+        sizes = np.diff(splits)
+        costs = fdist.exact_bucket_costs(sizes) if p.exact else fdist.bucket_costs(sizes, st["n_list"], p.n_probe)
+        owner = fdist.shard_units(costs, world)
         first, sizes, sub_splits, mine = fdist.shard_buckets(splits, owner, rank)
         n_sub = int(sub_splits[-1])
         if n_sub:
@@ -424,9 +431,11 @@ class ClusterPipeline:
         lasts[j]["rows"] (i64, device) maps them back -- the exchange step assembles the global result."""
         import torch
         c = self.ctx
+        if p.exact and shard is not None and shard[1] > 1:
+            return self._run_many_exact_sharded(datasets, precursor_tol_mass, precursor_tol_mode, rt_tol, fragment_tol,
+                                                batch_size, p, shard)
         if p.exact:
-            # exact mode: one partition after the other (no scan to overlap a front end with); not sharded
-            _refuse_sharded_exact(p, shard)
+            # exact mode: one partition after the other (no scan to overlap a front end with)
             outs, self.lasts = [], []
             for ds in datasets:
                 outs.append(self.run(ds, precursor_tol_mass, precursor_tol_mode, rt_tol, fragment_tol, batch_size, p))
@@ -513,6 +522,60 @@ class ClusterPipeline:
             self.last = self.lasts[-1]
         return outs
 
+    def _run_many_exact_sharded(self, datasets, precursor_tol_mass, precursor_tol_mode, rt_tol, fragment_tol, batch_size, p,
+                                shard):
+        """`run_many(shard=...)` in exact mode: buckets are independent (no neighbour list crosses one, there is no index), so a
+        rank runs `_exact` on its own whole buckets -- windows dealt job-wide on `distributed.exact_window_costs`
+        (`mz_interval` > 0, `_front_windows`), else the replicated sort and `_restrict` on `distributed.exact_bucket_costs`.
+        The subset runs as a compact CSR (row i = sorted position i), so the kernel's outputs are sized to it.  Same
+        contract as the nearest-neighbour path: labels / medoids over the subset, `lasts[j]["rows"]` = its dataset rows."""
+        import torch
+        c = self.ctx
+        args = (precursor_tol_mass, precursor_tol_mode, rt_tol)
+        windows = bool(p.mz_interval and p.mz_interval > 0)
+        owners = shard[2] if len(shard) > 2 else None
+        if windows and owners is None:
+            owners = self.plan_shards(c, datasets, batch_size, p, shard[1])
+        outs, self.lasts = [], []
+        for j, ds in enumerate(datasets):
+            st = None
+            if len(ds) > 0:
+                if windows:
+                    st = self._front_windows(c, ds, *args, batch_size, p, shard[:2], owner=owners[j])
+                else:
+                    st = self._restrict(c, self._front(c, ds, *args, batch_size, p), p, shard[:2])
+            if st is None or st["rows"].numel() == 0:
+                outs.append((c.empty((0,), torch.int32), c.empty((0,), torch.int32)))
+                self.lasts.append({"rows": c.empty((0,), torch.int64)})
+                continue
+            rows = st["rows"]
+            st["order"] = torch.arange(rows.numel(), dtype=torch.int64, device=c.tdev)
+            labels, medoids, last = self._exact(self._take_rows(c, ds, rows), st, *args, fragment_tol, p, False)
+            last["rows"] = rows
+            outs.append((labels, medoids))
+            self.lasts.append(last)
+        if self.lasts:
+            self.last = self.lasts[-1]
+        return outs
+
+    @staticmethod
+    def _take_rows(c, ds, rows):
+        """the peaks of dataset rows `rows` (i64, device) as a compact CSR on the device: row i of the result = rows[i].
+        A host-resident dataset gathers them on the host into pinned memory (`take_rows`) and uploads only those; a
+        device-resident one gathers them with a few device ops (the expansion `_restrict` uses)."""
+        import torch
+        if ds.on_host():
+            sub = ds.take_rows(rows.cpu().numpy())
+            return SpectrumDataset(None, None, c.to_dev(sub.mz), c.to_dev(sub.intensity), c.to_dev(sub.indptr))
+        indptr = c.to_dev(ds.indptr, torch.int64)
+        start = indptr[rows]
+        cnt = indptr[rows + 1] - start
+        out = torch.zeros(rows.numel() + 1, dtype=torch.int64, device=c.tdev)
+        torch.cumsum(cnt, 0, out=out[1:])
+        nnz = int(out[-1].item())
+        pos = torch.repeat_interleave(start - out[:-1], cnt, output_size=nnz) + torch.arange(nnz, device=c.tdev)
+        return SpectrumDataset(None, None, c.to_dev(ds.mz, torch.float32)[pos], c.to_dev(ds.intensity, torch.float32)[pos],
+                               out)
 
     def run_chunked(self, datasets, precursor_tol_mass: float, precursor_tol_mode: str, rt_tol: Optional[float],
                     fragment_tol: float, batch_size: int, p: AnnParams, n_chunks: int, on_chunk=None):
@@ -539,12 +602,6 @@ class ClusterPipeline:
                 on_chunk(ch, outs, self.lasts)
             del outs
         return [(labels[j], torch.cat(medoids[j]) if medoids[j] else c.empty((0,), torch.int32)) for j in range(len(datasets))]
-
-
-def _refuse_sharded_exact(p, shard):
-    if p.exact and shard is not None and shard[1] > 1:
-        raise ValueError("exact mode (AnnParams(exact=True) / --exact) runs on one GPU: the multi-GPU path exchanges nearest-"
-                         "neighbour lists, which exact mode does not build")
 
 
 def _merge_share(labels, medoids, off, outs, lasts):
@@ -620,7 +677,6 @@ class PartitionRunner:
         if not inputs_ready:
             torch.cuda.current_stream(self.device).synchronize()      # inputs produced on the caller's stream
         p = args[5] if len(args) > 5 else kwargs["p"]
-        _refuse_sharded_exact(p, shard)
         order = sorted(range(len(datasets)), key=lambda i: -len(datasets[i]))
         shards = [shard] * len(datasets)
         if shard is not None and shard[1] > 1 and p.mz_interval and p.mz_interval > 0:
@@ -703,25 +759,10 @@ class PartitionRunner:
 _default_pipeline: Optional[ClusterPipeline] = None
 
 
-def generate_clusters(dataset, linkage: str, distance_threshold: float, min_matches: int,
-                      precursor_tol_mass: float, precursor_tol_mode: str, rt_tol: Optional[float],
-                      fragment_tol: float, batch_size: int, *, ann: Optional[AnnParams] = None,
-                      pipeline: Optional[ClusterPipeline] = None) -> Tuple[np.ndarray, np.ndarray]:
-    """Same call as the reference (cluster.py:24-34).  `distance_threshold` is the cosine
-    distance threshold and plays the role of DBSCAN's eps (README.md:73-79); `linkage` and
-    `min_matches` belong to the snapshot's exact-cosine path: `min_matches` is used when `ann.rescore` is on
-    (matched-peak re-scoring of the ANN neighbours, similarity.py:17-80); `linkage` selects the hierarchical
-    clustering of those exact distances when `ann.clustering == "hierarchical"` and is an error otherwise unless
-    it is the reference default "complete".
-
-    Returns (labels int32[N] by dataset row with noise renumbered as singletons --
-    cluster.py:144-155 --, medoids int32[n_labels]: medoids[c] = dataset row representing
-    cluster c, usable as `dataset.take(medoids)`, falcon.py:198-203)."""
-    global _default_pipeline
-    if not isinstance(dataset, SpectrumDataset):
-        dataset = SpectrumDataset.from_table(
-            dataset.to_table(columns=["precursor_mz", "precursor_charge", "retention_time", "mz", "intensity"])
-            if hasattr(dataset, "to_table") else dataset)
+def resolve_params(linkage: str, distance_threshold: float, min_matches: int, ann: Optional[AnnParams] = None) -> AnnParams:
+    """The parameters a pass runs with, from `generate_clusters`' arguments (and the CLI's, single or distributed): eps =
+    distance_threshold, exact mode => hierarchical, linkage / re-scoring / min_matches for the hierarchical clustering.
+    Raises ValueError on a combination the path cannot honour.  Never mutates `ann`."""
     import dataclasses
     if linkage not in ("complete", "single", "average"):
         raise ValueError(f"unknown linkage {linkage!r} (choose complete, single or average; cluster.py:283-290)")
@@ -749,6 +790,29 @@ def generate_clusters(dataset, linkage: str, distance_threshold: float, min_matc
         raise ValueError(f"linkage={linkage!r} only applies to the hierarchical clustering of the exact distances "
                          "(AnnParams(clustering=\"hierarchical\", rescore=True) / --clustering hierarchical); the default "
                          "nearest-neighbour path clusters with DBSCAN and would ignore it")
+    return p
+
+
+def generate_clusters(dataset, linkage: str, distance_threshold: float, min_matches: int,
+                      precursor_tol_mass: float, precursor_tol_mode: str, rt_tol: Optional[float],
+                      fragment_tol: float, batch_size: int, *, ann: Optional[AnnParams] = None,
+                      pipeline: Optional[ClusterPipeline] = None) -> Tuple[np.ndarray, np.ndarray]:
+    """Same call as the reference (cluster.py:24-34).  `distance_threshold` is the cosine
+    distance threshold and plays the role of DBSCAN's eps (README.md:73-79); `linkage` and
+    `min_matches` belong to the snapshot's exact-cosine path: `min_matches` is used when `ann.rescore` is on
+    (matched-peak re-scoring of the ANN neighbours, similarity.py:17-80); `linkage` selects the hierarchical
+    clustering of those exact distances when `ann.clustering == "hierarchical"` and is an error otherwise unless
+    it is the reference default "complete".
+
+    Returns (labels int32[N] by dataset row with noise renumbered as singletons --
+    cluster.py:144-155 --, medoids int32[n_labels]: medoids[c] = dataset row representing
+    cluster c, usable as `dataset.take(medoids)`, falcon.py:198-203)."""
+    global _default_pipeline
+    if not isinstance(dataset, SpectrumDataset):
+        dataset = SpectrumDataset.from_table(
+            dataset.to_table(columns=["precursor_mz", "precursor_charge", "retention_time", "mz", "intensity"])
+            if hasattr(dataset, "to_table") else dataset)
+    p = resolve_params(linkage, distance_threshold, min_matches, ann)
     pipe = pipeline or _default_pipeline
     if pipe is None:
         pipe = _default_pipeline = ClusterPipeline()

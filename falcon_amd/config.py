@@ -75,6 +75,10 @@ class Config:
                        help="Re-score the nearest neighbours with the matched-peak cosine (fragment_tol, "
                             "min_matched_peaks) before clustering.")
         p.add_argument("--device", type=int, default=0, help="HIP device ordinal.")
+        p.add_argument("--distributed", action="store_true",
+                       help="Run as one rank of a multi-GPU job launched by `python -m torch.distributed.run --module "
+                            "falcon_amd.falcon ...`: the precursor windows / buckets of every charge are dealt to the ranks, "
+                            "rank 0 writes the outputs.")
         # PREPROCESSING  (config.py:126-183)
         p.add_argument("--min_peaks", default=5, type=int)
         p.add_argument("--min_mz_range", default=250.0, type=float)

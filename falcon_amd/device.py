@@ -395,6 +395,21 @@ class Context:
         return (self.to_dev(mz, torch.float32), self.to_dev(intensity, torch.float32), self.to_dev(indptr, torch.int64),
                 self.to_dev(order, torch.int64))
 
+    @staticmethod
+    def _check_order(order, indptr, n_out: int, what: str):
+        """exact mode reads the peaks of row order[i] and writes labels_out[order[i]]: every entry must be a row of the CSR
+        and fit the n_out-row outputs.  One min / max on the host before any launch (a subset whose `order` holds
+        dataset rows has to run as a compact CSR, order = arange).  The min / max costs one device-to-host wait per call,
+        single-GPU passes included; accepted: both callers wait for the library anyway (`fal_cluster_exact` synchronises
+        to read its counts, `fal_exact_edges` to read the edge count), and an out-of-range order would write past a
+        device buffer."""
+        if order.numel() == 0:
+            return
+        lo, hi = (int(x) for x in _torch().aminmax(order))
+        if lo < 0 or hi >= min(int(n_out), int(indptr.numel()) - 1):
+            raise ValueError(f"{what}: row_order holds rows in [{lo}, {hi}], outside the {n_out} output rows / "
+                             f"{int(indptr.numel()) - 1} CSR rows (run a subset as a compact CSR with order = arange)")
+
     def exact_edges(self, mz, intensity, indptr, order, splits, fragment_tol: float, min_matches: int, threshold: float,
                     max_edges: Optional[int] = None):
         """f5 staged (`fal_exact_edges`): every pair of every bucket of `splits` scored with the matched-peak cosine
@@ -403,6 +418,7 @@ class Context:
         torch = _torch()
         mz, intensity, indptr, order = self._peaks(mz, intensity, indptr, order)
         n = order.numel()
+        self._check_order(order, indptr, int(indptr.numel()) - 1, "exact_edges")
         sp = np.ascontiguousarray(splits, dtype=np.int64)
         if max_edges is None:
             nb = np.diff(sp)
@@ -438,6 +454,7 @@ class Context:
         torch = _torch()
         mz, intensity, indptr, order = self._peaks(mz, intensity, indptr, order)
         n = order.numel()
+        self._check_order(order, indptr, n, "cluster_exact")
         sp = np.ascontiguousarray(splits, dtype=np.int64)
         lab_sorted = self.empty((n,), torch.int32)
         labels = self.empty((n,), torch.int32)

@@ -153,6 +153,26 @@ def window_costs(counts: np.ndarray, batch_size: int, n_probe: int, mz_interval:
     return cost
 
 
+EXACT_ROW_UNITS = 70.0       # exact mode: the per-row tail (linkage, refinement, medoids, labels) in units of one scored pair.
+                             # profiles/exact/exact_rate_1M.txt: 19 ms of tail for 1 M rows against 48 ms of edge kernel for
+                             # 176 M pairs -> (19 / 1e6) / (48 / 176e6) ~ 70 pairs per row
+
+
+def exact_bucket_costs(sizes: np.ndarray) -> np.ndarray:
+    """exact mode's cost of a bucket of n_b spectra: its n_b (n_b - 1) / 2 scored pairs plus the per-row tail"""
+    n = np.asarray(sizes, np.float64)
+    return n * (n - 1.0) * 0.5 + EXACT_ROW_UNITS * n
+
+
+def exact_window_costs(counts: np.ndarray, batch_size: int) -> np.ndarray:
+    """`window_costs` for exact mode, from the count alone: a window becomes ceil(count / batch_size) buckets of count / chunks
+    spectra, each scoring all of its pairs.  `counts` may be 2-D [partitions, windows]."""
+    counts = np.asarray(counts, np.float64)
+    chunks = np.maximum(1.0, np.ceil(counts / max(int(batch_size), 1)))
+    size = counts / chunks
+    return chunks * size * (size - 1.0) * 0.5 + EXACT_ROW_UNITS * counts
+
+
 _cost_tables = {}
 
 
@@ -508,13 +528,19 @@ def run_sharded(pipe, ds, precursor_tol_mass: float, precursor_tol_mode: str, rt
     c = pipe.ctx
     n = len(ds)
     st = pipe._front(c, ds, precursor_tol_mass, precursor_tol_mode, rt_tol, batch_size, p)
-    sub = pipe._restrict(c, st, p, (rank, world_size))
+    sub = pipe._restrict(c, st, p, (rank, world_size))          # (exact mode: dealt on `exact_bucket_costs`)
     order_sub = sub["rows"]
     n_sub = int(order_sub.numel())
-    if n_sub:
+    if n_sub and p.exact:
+        # exact mode on the subset as a compact CSR (row i = sorted position i): labels_out is sized to the subset
+        sub["order"] = torch.arange(n_sub, dtype=torch.int64, device=c.tdev)
+        labels_sub, medoids_sub, _ = pipe._exact(pipe._take_rows(c, ds, order_sub), sub, precursor_tol_mass,
+                                                 precursor_tol_mode, rt_tol, fragment_tol, p, False)
+    elif n_sub:
         pipe._search(ds, sub, precursor_tol_mass, precursor_tol_mode, rt_tol, fragment_tol, p, False)
         sub["order"] = torch.arange(n_sub, dtype=torch.int64, device=c.tdev)      # label the subset locally ...
         labels_sub, medoids_sub, _ = pipe._graph(sub, precursor_tol_mass, precursor_tol_mode, rt_tol, p, False)
+    if n_sub:
         mine_rows = order_sub.cpu().numpy()                                       # ... and map back to dataset rows
         mine_lab = labels_sub.cpu().numpy()
         mine_med = mine_rows[medoids_sub.cpu().numpy()].astype(np.int32)
@@ -546,3 +572,52 @@ def _gather_shards(rows, labels, medoids, device):
         a += counts[r]
         b += mcounts[r]
     return out
+
+
+def gather_partitions(outs, lasts, sizes, device):
+    """The results of every charge partition of a sharded job on every rank: `outs` / `lasts` = what
+    `PartitionRunner.run(..., shard=(rank, world))` returned / left in `.lasts` (labels over the rank's rows in sorted order,
+    medoids as positions into them, `lasts[j]["rows"]` = their dataset rows), `sizes[j]` = spectra of partition j.  One
+    all-gatherv round per array kind (per-partition counts, dataset rows, labels, medoid rows) on `device` (a CUDA device for
+    RCCL, the CPU for gloo), then `merge_shards` per partition.  -> [(labels i32[N_j] by dataset row, medoids i32[n_labels_j]
+    dataset rows)] as numpy; cluster ids are rank-major (the per-block offset of cluster.py:144-155), the partition and the
+    medoid rows are those of the single-GPU pass.
+    A partition whose `last` has no "rows" ran unsharded (`PartitionRunner.run(shard=(0, 1))` takes `ClusterPipeline.run`):
+    its labels are by dataset row and its medoids are dataset rows already, i.e. rows = arange(N_j)."""
+    import torch
+    rank, ws = world()
+    n_parts = len(sizes)
+    rows, labels, meds, cnt = [], [], [], np.zeros((n_parts, 2), np.int64)
+    for j, ((lab, med), last) in enumerate(zip(outs, lasts)):
+        if lab.numel() == 0:
+            continue
+        r = last.get("rows")
+        if r is None:
+            if lab.numel() != int(sizes[j]):
+                raise ValueError(f"gather_partitions: partition {j} has {lab.numel()} labels and no \"rows\" for "
+                                 f"{int(sizes[j])} spectra")
+            r = torch.arange(lab.numel(), dtype=torch.int64, device=lab.device)
+        r = r.long()
+        rows.append(r)
+        labels.append(lab.to(torch.int32))
+        meds.append(r[med.long()])
+        cnt[j] = (r.numel(), med.numel())
+    cat = lambda xs, dt: (torch.cat(xs).to(device=device, dtype=dt) if xs else torch.zeros(0, dtype=dt, device=device))
+    t_cnt = torch.from_numpy(cnt.reshape(-1)).to(device)
+    g_cnt, _ = allgatherv_rows(t_cnt, [2 * n_parts] * ws)
+    g_cnt = g_cnt.cpu().numpy().reshape(ws, n_parts, 2)
+    n_rows, n_meds = g_cnt[:, :, 0].sum(1).tolist(), g_cnt[:, :, 1].sum(1).tolist()
+    g_rows, _ = allgatherv_rows(cat(rows, torch.int64), n_rows)
+    g_lab, _ = allgatherv_rows(cat(labels, torch.int32), n_rows)
+    g_med, _ = allgatherv_rows(cat(meds, torch.int64), n_meds)
+    g_rows, g_lab, g_med = g_rows.cpu().numpy(), g_lab.cpu().numpy(), g_med.cpu().numpy()
+    shards = [[] for _ in range(n_parts)]
+    a = b = 0
+    for r in range(ws):                                  # rank-major: rank r's pieces in partition order
+        for j in range(n_parts):
+            nr, nm = int(g_cnt[r, j, 0]), int(g_cnt[r, j, 1])
+            shards[j].append((g_rows[a:a + nr], g_lab[a:a + nr], g_med[b:b + nm].astype(np.int32)))
+            a += nr
+            b += nm
+    return [merge_shards(int(sizes[j]), shards[j]) if sizes[j] else (np.zeros(0, np.int32), np.zeros(0, np.int32))
+            for j in range(n_parts)]

@@ -81,7 +81,39 @@ def _run(args) -> int:
     logger.info("falcon version %s", str(__version__))
     for line in _option_lines():
         logger.debug(line)
+    if config.distributed:
+        return _run_distributed()
 
+    rm_work_dir, exit_code = _setup_work_dir()
+    if exit_code:
+        return exit_code
+    spectra_dir = os.path.join(config.work_dir, "spectra")
+    pipe = cluster.ClusterPipeline(device=config.device)
+    pipe.ctx.plan(0)                 # the kernels' code objects, once per process: not between the kernels of the first charge's pass
+    charges = _load_or_prepare(spectra_dir, pipe.ctx)
+
+    ann = _ann_params()
+    rows_all, current_label, representatives = [], 0, []
+    for charge in charges:                                                                     # falcon.py:153
+        part = np.load(os.path.join(spectra_dir, f"spectra_charge_{charge}.npz"))     # plain arrays: no pickle
+        n = len(part["precursor_mz"])
+        if n == 0:
+            continue
+        ds = cluster.SpectrumDataset(part["precursor_mz"], part["retention_time"], part["mz"], part["intensity"],
+                                     part["indptr"])
+        labels, medoids = cluster.generate_clusters(
+            ds, config.linkage, config.distance_threshold, config.min_matched_peaks, config.precursor_tol[0],
+            config.precursor_tol[1], config.rt_tol, config.fragment_tol, config.batch_size, ann=ann, pipeline=pipe)
+        current_label = _emit_charge(part, charge, labels, medoids, current_label, rows_all, representatives)
+    _write_outputs(rows_all, representatives)
+    if rm_work_dir:
+        shutil.rmtree(config.work_dir)
+    return 0
+
+
+def _setup_work_dir():
+    """falcon.py:70-122: the work directory (a temporary one unless --work_dir) and the refusal to clobber existing outputs
+    unless --overwrite -> (remove the work directory at the end, exit code or 0)"""
     rm_work_dir = False
     if config.work_dir is None:
         config.work_dir = tempfile.mkdtemp()
@@ -103,55 +135,56 @@ def _run(args) -> int:
             else:
                 logger.error("Output file %s (%s) already exists, aborting...", fn, what)
                 exit_exists = True
-    if exit_exists:
-        return 1
+    return rm_work_dir, 1 if exit_exists else 0
 
+
+def _load_or_prepare(spectra_dir: str, ctx) -> List[str]:
+    """the charge partitions of the work directory: read back, or prepared from the peak files (falcon.py:124-149)"""
     _, min_mz, max_mz = spectrum.get_dim(config.min_mz, config.max_mz, config.fragment_tol)   # falcon.py:124-126
     if config.overwrite:
         for fn in os.listdir(spectra_dir):
             os.remove(os.path.join(spectra_dir, fn))
-    pipe = cluster.ClusterPipeline(device=config.device)
-    pipe.ctx.plan(0)                 # the kernels' code objects, once per process: not between the kernels of the first charge's pass
     charge_path = os.path.join(spectra_dir, "charges.json")
     if os.path.isfile(charge_path) and not config.overwrite:                                   # falcon.py:143-149
         with open(charge_path) as f:
             charges = json.load(f)
     else:
-        charges = _prepare_spectra(spectra_dir, min_mz, max_mz, pipe.ctx)
+        charges = _prepare_spectra(spectra_dir, min_mz, max_mz, ctx)
         with open(charge_path, "w") as f:
             json.dump(charges, f)
+    return charges
 
-    ann = cluster.AnnParams(eps=config.eps, low_dim=config.low_dim, n_probe=config.n_probe,
+
+def _ann_params():
+    return cluster.AnnParams(eps=config.eps, low_dim=config.low_dim, n_probe=config.n_probe,
                             n_neighbors=config.n_neighbors, n_neighbors_ann=config.n_neighbors_ann,
                             mz_interval=config.mz_interval, min_mz=config.min_mz, max_mz=config.max_mz,
                             rescore=config.rescore, clustering=config.clustering, dtype=config.dtype,
                             exact=config.exact)
-    rows_all, current_label, representatives = [], 0, []
-    for charge in charges:                                                                     # falcon.py:153
-        part = np.load(os.path.join(spectra_dir, f"spectra_charge_{charge}.npz"))     # plain arrays: no pickle
-        n = len(part["precursor_mz"])
-        if n == 0:
-            continue
-        ds = cluster.SpectrumDataset(part["precursor_mz"], part["retention_time"], part["mz"], part["intensity"],
-                                     part["indptr"])
-        labels, medoids = cluster.generate_clusters(
-            ds, config.linkage, config.distance_threshold, config.min_matched_peaks, config.precursor_tol[0],
-            config.precursor_tol[1], config.rt_tol, config.fragment_tol, config.batch_size, ann=ann, pipeline=pipe)
-        labels = labels + current_label                                                        # falcon.py:189-193
-        current_label = int(labels.max()) + 1
-        for i in range(n):
-            # float32 columns keep their own (shortest round-trip) text form, as pandas' to_csv prints them
-            rows_all.append((str(part["filename"][i]), str(part["identifier"][i]), charge,
-                             np.float32(part["precursor_mz"][i]), np.float32(part["retention_time"][i]), int(labels[i])))
-        if config.export_representatives:                                                      # falcon.py:198-203
-            ip = part["indptr"]
-            for c, m in enumerate(medoids):
-                representatives.append({
-                    "identifier": str(part["identifier"][m]), "precursor_mz": float(part["precursor_mz"][m]),
-                    "precursor_charge": None if charge == "None" else int(charge),
-                    "retention_time": float(part["retention_time"][m]), "mz": part["mz"][ip[m]:ip[m + 1]],
-                    "intensity": part["intensity"][ip[m]:ip[m + 1]], "cluster": int(labels[m])})
 
+
+def _emit_charge(part, charge, labels, medoids, current_label, rows_all, representatives) -> int:
+    """one charge's labels (by row of its partition) and medoid rows -> CSV rows and representatives; -> the next label"""
+    n = len(part["precursor_mz"])
+    labels = labels + current_label                                                            # falcon.py:189-193
+    current_label = int(labels.max()) + 1
+    for i in range(n):
+        # float32 columns keep their own (shortest round-trip) text form, as pandas' to_csv prints them
+        rows_all.append((str(part["filename"][i]), str(part["identifier"][i]), charge,
+                         np.float32(part["precursor_mz"][i]), np.float32(part["retention_time"][i]), int(labels[i])))
+    if config.export_representatives:                                                          # falcon.py:198-203
+        ip = part["indptr"]
+        for c, m in enumerate(medoids):
+            representatives.append({
+                "identifier": str(part["identifier"][m]), "precursor_mz": float(part["precursor_mz"][m]),
+                "precursor_charge": None if charge == "None" else int(charge),
+                "retention_time": float(part["retention_time"][m]), "mz": part["mz"][ip[m]:ip[m + 1]],
+                "intensity": part["intensity"][ip[m]:ip[m + 1]], "cluster": int(labels[m])})
+    return current_label
+
+
+def _write_outputs(rows_all, representatives) -> None:
+    """falcon.py:206-244: the CSV (+ the MGF of representatives), written on two threads"""
     rows_all.sort(key=lambda r: (_natural_key(r[0]), _natural_key(r[1])))                      # falcon.py:206-208
     n_clusters = len({r[5] for r in rows_all})
     logger.info("Export cluster assignments of %d spectra to %d unique clusters to output file %s",
@@ -166,9 +199,80 @@ def _run(args) -> int:
         mgf_worker.start()
         mgf_worker.join()
     csv_worker.join()
-    if rm_work_dir:
-        shutil.rmtree(config.work_dir)
-    return 0
+
+
+def _run_distributed() -> int:
+    """`--distributed`: one rank of a job launched by `python -m torch.distributed.run --module falcon_amd.falcon ...`.
+    Rank 0 sets the work directory up, checks the outputs and prepares the charge partitions; every rank then clusters its
+    share of every partition (`PartitionRunner.run(shard=(rank, world))`: precursor windows / buckets dealt on the cost
+    model of the mode, exact or nearest-neighbour), one all-gatherv round assembles every partition on every rank
+    (`distributed.gather_partitions`) and rank 0 writes the outputs.  Cluster ids are rank-major; the partition and the
+    representatives are those of one process.  Backend RCCL ("nccl"), or gloo with FALCON_DIST_BACKEND=gloo; device
+    LOCAL_RANK, or FALCON_DIST_DEVICE (RCCL refuses two ranks on one device: the gloo + one-device form is for tests).
+    Every rank reads the partitions from rank 0's work directory: the ranks must share a filesystem (one node, or a
+    `--work_dir` on a shared mount)."""
+    import torch
+    import torch.distributed as dist
+    from . import distributed as fdist
+    rank, world = int(os.environ.get("RANK", "0")), int(os.environ.get("WORLD_SIZE", "1"))
+    device = int(os.environ.get("FALCON_DIST_DEVICE", os.environ.get("LOCAL_RANK", "0")))
+    backend = "gloo" if os.environ.get("FALCON_DIST_BACKEND") == "gloo" else "nccl"
+    torch.cuda.set_device(device)
+    dev = torch.device("cuda", device)
+    os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
+    if backend == "nccl":
+        dist.init_process_group("nccl", rank=rank, world_size=world, device_id=dev)
+    else:
+        dist.init_process_group(backend, rank=rank, world_size=world)
+    try:
+        state = [None, 0, False]                                  # work_dir, exit code, remove the work dir at the end
+        if rank == 0:
+            rm_work_dir, exit_code = _setup_work_dir()
+            state = [config.work_dir, exit_code, rm_work_dir]
+            if not exit_code:
+                # a context of its own for the preprocessing, released before the clustering (the runner's slots make theirs)
+                from .device import Context
+                prep = Context(device)
+                try:
+                    _load_or_prepare(os.path.join(config.work_dir, "spectra"), prep)
+                finally:
+                    prep.close()
+                    torch.cuda.empty_cache()
+        dist.broadcast_object_list(state, src=0)
+        dist.barrier()
+        if state[1]:
+            return state[1]
+        config.work_dir = state[0]
+        spectra_dir = os.path.join(config.work_dir, "spectra")
+        with open(os.path.join(spectra_dir, "charges.json")) as f:
+            charges = json.load(f)
+        p = cluster.resolve_params(config.linkage, config.distance_threshold, config.min_matched_peaks, _ann_params())
+        parts, sets = [], []
+        for charge in charges:
+            part = np.load(os.path.join(spectra_dir, f"spectra_charge_{charge}.npz"))
+            parts.append(part)
+            sets.append(cluster.SpectrumDataset(part["precursor_mz"], part["retention_time"], part["mz"], part["intensity"],
+                                                part["indptr"]))                      # host-resident: a rank uploads its rows
+        runner = cluster.PartitionRunner(device, 2)
+        try:
+            outs = runner.run(sets, config.precursor_tol[0], config.precursor_tol[1], config.rt_tol, config.fragment_tol,
+                              config.batch_size, p, shard=(rank, world))
+            merged = fdist.gather_partitions(outs, runner.lasts, [len(ds) for ds in sets],
+                                             dev if backend == "nccl" else torch.device("cpu"))
+        finally:
+            runner.close()
+        if rank == 0:
+            rows_all, current_label, representatives = [], 0, []
+            for charge, part, (labels, medoids) in zip(charges, parts, merged):
+                if len(labels):
+                    current_label = _emit_charge(part, charge, labels, medoids, current_label, rows_all, representatives)
+            _write_outputs(rows_all, representatives)
+        dist.barrier()
+        if rank == 0 and state[2]:
+            shutil.rmtree(config.work_dir)
+        return 0
+    finally:
+        dist.destroy_process_group()
 
 
 def _raw_csr(specs):
