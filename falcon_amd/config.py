@@ -29,7 +29,7 @@ class Config:
         p = argparse.ArgumentParser(description=_HELP_HEADER, formatter_class=argparse.RawDescriptionHelpFormatter)
         p.add_argument("-c", "--config", default=None, help="Config file path (default: config.ini if present).")
         # IO  (config.py:52-74)
-        p.add_argument("input_filenames", nargs="+", help="Input peak files (supported format here: .MGF).")
+        p.add_argument("input_filenames", nargs="+", help="Input peak files (supported formats: .mzML, .mzXML, .MGF).")
         p.add_argument("output_filename", help="Output file name.")
         p.add_argument("--work_dir", default=None, help="Working directory (default: temporary directory).")
         p.add_argument("--overwrite", action="store_true", help="Overwrite existing results.")

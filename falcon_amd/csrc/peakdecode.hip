@@ -1,0 +1,526 @@
+// Peak-file payload decode on the device: the binary arrays of mzML / mzXML spectra (base64 text, optionally zlib) -> the raw
+// peak CSR that fal_process_spectra takes (indptr i64, m/z f64, intensity f32, peaks sorted by m/z inside every spectrum).
+//
+// The host reader keeps the XML structure; every binary array arrives as a range of one contiguous payload buffer plus a
+// descriptor row (offset, base64 length, declared value count, flags).  Five launches, no host round trip:
+//   arrays  : one thread per array: validate the row, inflate capacity (declared count x element size, 8-byte rounded);
+//   counts  : one thread per spectrum: its peak count (the declared count of its m/z array); two device scans give the output
+//             indptr and the per-array offsets of the inflate buffer;
+//   base64  : one wave per array, 4 characters -> 3 bytes per lane; the decoded bytes land at the array's own payload offset in
+//             a buffer the size of the payload (decoded <= encoded), so arrays never overlap and stay 8-byte aligned;
+//   inflate : one thread per zlib array (RFC 1950/1951: stored, fixed- and dynamic-Huffman blocks, overlapping copies, header and
+//             Adler-32 checks).  Canonical-code tables of the thread in LDS (puff-style count / symbol form, 896 B per thread:
+//             64 threads = 56 KB per block); output bytes go straight to the array's slot, bounded by its declared capacity;
+//   convert : one wave per spectrum: byte swap (mzXML is big-endian), widen / narrow to f64 m/z and f32 intensity, de-interleave
+//             the mzXML pairs, stable sort by m/z (what np.lexsort does in falcon._raw_csr: NaN last, ties in input order) --
+//             already-sorted spectra (nearly all) are copied, the rest ranked within the wave.
+// A bad array sets bits of its spectrum's status word (FAL_PEAK_ST_*) and the spectrum's output range is zero-filled; nothing is
+// ever written outside an array's slot or a spectrum's range, and every loop is bounded by the input or the declared output.
+#include <math.h>
+#include <algorithm>
+#include "common.h"
+#include "ivf.h"
+#include "util.h"
+
+namespace fal {
+namespace {
+
+constexpr int kInflateBlock = 64;
+constexpr int kMaxBits = 15;
+constexpr int kMaxLit = 288;
+constexpr int kMaxDist = 30;
+
+// per-thread canonical Huffman tables (LDS)
+struct __attribute__((aligned(16))) HuffLds {
+    uint16_t lencnt[16];
+    uint16_t distcnt[16];
+    uint16_t offs[16];
+    uint16_t lensym[kMaxLit];
+    uint16_t distsym[kMaxDist + 2];
+    uint8_t lengths[160];            // code lengths of the dynamic header, two 4-bit values per byte (320 symbols)
+};
+static_assert(sizeof(HuffLds) == 896, "HuffLds layout");
+
+__host__ __device__ __forceinline__ int elem_bytes(int64_t flags) { return (flags & FAL_PEAK_F64) ? 8 : 4; }
+
+__host__ __device__ __forceinline__ int64_t array_bytes(const int64_t* d) {      // declared decoded size of an array
+    return d[2] * elem_bytes(d[3]) * ((d[3] & FAL_PEAK_PAIRS) ? 2 : 1);
+}
+
+// ---- launch 1: descriptors ------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void pd_arrays_kernel(const int64_t* __restrict__ desc, int64_t n_arrays, int64_t payload_bytes,
+                                                        int32_t* __restrict__ arr_status, int64_t* __restrict__ cap) {
+    for (int64_t a = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; a < n_arrays; a += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t* d = desc + 4 * a;
+        const int64_t off = d[0], len = d[1], cnt = d[2], flags = d[3];
+        const bool ok = off >= 0 && len >= 0 && (off & 7) == 0 && (len & 3) == 0 && off <= payload_bytes &&
+                        len <= payload_bytes - off && cnt >= 0 && cnt < (int64_t(1) << 40) &&
+                        (flags & ~(int64_t)(FAL_PEAK_F64 | FAL_PEAK_ZLIB | FAL_PEAK_BIG_ENDIAN | FAL_PEAK_PAIRS)) == 0;
+        arr_status[a] = ok ? 0 : FAL_PEAK_ST_DESC;
+        cap[a] = ok && (flags & FAL_PEAK_ZLIB) ? (array_bytes(d) + 7) & ~(int64_t)7 : 0;
+    }
+}
+
+// ---- launch 2: peaks per spectrum -----------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void pd_counts_kernel(const int64_t* __restrict__ desc, int64_t n_arrays,
+                                                        const int64_t* __restrict__ spec, int64_t n_spec, int64_t* __restrict__ count) {
+    for (int64_t s = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; s < n_spec; s += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t ma = spec[2 * s];
+        const int64_t c = ma >= 0 && ma < n_arrays ? desc[4 * ma + 2] : 0;
+        count[s] = c >= 0 && c < (int64_t(1) << 40) ? c : 0;
+    }
+}
+
+// ---- launch 3: base64 -----------------------------------------------------------------------------------------------------
+__device__ __forceinline__ int b64_value(uint32_t c) {          // -1: not a base64 character ('=' handled by the caller)
+    if (c - 'A' < 26u) return (int)(c - 'A');
+    if (c - 'a' < 26u) return (int)(c - 'a') + 26;
+    if (c - '0' < 10u) return (int)(c - '0') + 52;
+    if (c == '+') return 62;
+    if (c == '/') return 63;
+    return -1;
+}
+
+__global__ __launch_bounds__(256) void pd_base64_kernel(const uint8_t* __restrict__ payload, const int64_t* __restrict__ desc,
+                                                        int64_t n_arrays, int32_t* __restrict__ arr_status, uint8_t* __restrict__ dec,
+                                                        int64_t* __restrict__ dec_len) {
+    const int lane = threadIdx.x & 63;
+    const int64_t waves = (int64_t)gridDim.x * (blockDim.x >> 6);
+    for (int64_t a = blockIdx.x * (int64_t)(blockDim.x >> 6) + (threadIdx.x >> 6); a < n_arrays; a += waves) {
+        if (arr_status[a]) continue;                                    // wave-uniform
+        const int64_t* d = desc + 4 * a;
+        const int64_t off = d[0], groups = d[1] >> 2;
+        const uint32_t* src = reinterpret_cast<const uint32_t*>(payload + off);
+        uint8_t* out = dec + off;
+        int pad = 0;
+        bool bad = false;
+        for (int64_t g = lane; g < groups; g += 64) {
+            const uint32_t w = src[g];
+            const uint32_t c0 = w & 0xFF, c1 = (w >> 8) & 0xFF, c2 = (w >> 16) & 0xFF, c3 = w >> 24;
+            const bool last = g == groups - 1;
+            const int p3 = last && c3 == '=', p2 = p3 && c2 == '=';
+            const int v0 = b64_value(c0), v1 = b64_value(c1), v2 = p2 ? 0 : b64_value(c2), v3 = p3 ? 0 : b64_value(c3);
+            if ((v0 | v1 | v2 | v3) < 0) {
+                bad = true;
+                continue;
+            }
+            const uint32_t v = ((uint32_t)v0 << 18) | ((uint32_t)v1 << 12) | ((uint32_t)v2 << 6) | (uint32_t)v3;
+            out[3 * g] = (uint8_t)(v >> 16);
+            if (!p2) out[3 * g + 1] = (uint8_t)(v >> 8);
+            if (!p3) out[3 * g + 2] = (uint8_t)v;
+            if (last) pad = p3 + p2;
+        }
+        const bool any_bad = __ballot(bad) != 0;
+        const int total_pad = __shfl(pad, (int)((groups - 1) & 63), 64);
+        if (lane == 0) {
+            const int64_t n = groups * 3 - (groups ? total_pad : 0);
+            dec_len[a] = n;
+            int st = any_bad ? FAL_PEAK_ST_BASE64 : 0;
+            if (!any_bad && !(d[3] & FAL_PEAK_ZLIB)) {
+                const int64_t want = array_bytes(d);
+                st = n > want ? FAL_PEAK_ST_OVERFLOW : n < want ? FAL_PEAK_ST_SHORT : 0;
+            }
+            arr_status[a] = st;
+        }
+    }
+}
+
+// ---- launch 4: inflate ----------------------------------------------------------------------------------------------------
+struct Inflater {
+    const uint8_t* in;
+    int64_t in_len, in_pos;
+    uint32_t bitbuf;
+    int bitcnt;
+    uint8_t* out;
+    int64_t out_cap, out_pos;
+    uint32_t s1, s2;                 // Adler-32
+    int err;
+
+    __host__ __device__ __forceinline__ uint32_t bits(int need) {        // need <= 16
+        while (bitcnt < need) {
+            if (in_pos >= in_len) {
+                err |= FAL_PEAK_ST_CODE;                        // stream ends inside a block
+                return 0;
+            }
+            bitbuf |= (uint32_t)in[in_pos++] << bitcnt;
+            bitcnt += 8;
+        }
+        const uint32_t v = bitbuf & ((1u << need) - 1u);
+        bitbuf >>= need;
+        bitcnt -= need;
+        return v;
+    }
+
+    __host__ __device__ __forceinline__ void emit(uint8_t b) {
+        out[out_pos++] = b;
+        s1 += b;
+        if (s1 >= 65521u) s1 -= 65521u;
+        s2 += s1;
+        if (s2 >= 65521u) s2 -= 65521u;
+    }
+
+    // one symbol of a canonical code (count per length, symbols in code order); -1 on a code that is not in the table
+    __host__ __device__ __forceinline__ int decode(const uint16_t* cnt, const uint16_t* sym) {
+        int code = 0, first = 0, index = 0;
+        for (int len = 1; len <= kMaxBits; ++len) {
+            code |= (int)bits(1);
+            const int count = cnt[len];
+            if (code - count < first) return sym[index + (code - first)];
+            index += count;
+            first = (first + count) << 1;
+            code <<= 1;
+            if (err) return -1;
+        }
+        return -1;
+    }
+};
+
+__host__ __device__ __forceinline__ int get_len(const uint8_t* l, int i) { return (l[i >> 1] >> ((i & 1) * 4)) & 15; }
+__host__ __device__ __forceinline__ void set_len(uint8_t* l, int i, int v) {
+    const int sh = (i & 1) * 4;
+    l[i >> 1] = (uint8_t)((l[i >> 1] & ~(15 << sh)) | (v << sh));
+}
+
+// canonical code from code lengths[first .. first + n) (4-bit packed) -> cnt / sym; returns the unused code space (0 = complete,
+// > 0 = incomplete, < 0 = over-subscribed), as puff's construct()
+__host__ __device__ int construct(uint16_t* cnt, uint16_t* sym, uint16_t* offs, const uint8_t* lengths, int first, int n) {
+    for (int len = 0; len <= kMaxBits; ++len) cnt[len] = 0;
+    for (int s = 0; s < n; ++s) cnt[get_len(lengths, first + s)]++;
+    if (cnt[0] == n) return 0;
+    int left = 1;
+    for (int len = 1; len <= kMaxBits; ++len) {
+        left <<= 1;
+        left -= cnt[len];
+        if (left < 0) return left;
+    }
+    offs[1] = 0;
+    for (int len = 1; len < kMaxBits; ++len) offs[len + 1] = offs[len] + cnt[len];
+    for (int s = 0; s < n; ++s) {
+        const int l = get_len(lengths, first + s);
+        if (l) sym[offs[l]++] = (uint16_t)s;
+    }
+    return left;
+}
+
+// length / distance bases and extra bits (RFC 1951 3.2.5) without tables
+__host__ __device__ __forceinline__ void length_base(int i, int* base, int* extra) {     // i = symbol - 257, 0..28
+    if (i < 8) { *base = 3 + i; *extra = 0; }
+    else if (i == 28) { *base = 258; *extra = 0; }
+    else { const int e = (i - 4) >> 2; *base = ((4 + (i & 3)) << e) + 3; *extra = e; }
+}
+__host__ __device__ __forceinline__ void dist_base(int i, int* base, int* extra) {       // i = 0..29
+    if (i < 4) { *base = 1 + i; *extra = 0; }
+    else { const int e = (i - 2) >> 1; *base = ((2 + (i & 1)) << e) + 1; *extra = e; }
+}
+
+// order of the code-length code lengths, 5 bits per entry: 16 17 18 0 8 7 9 6 10 5 11 4 | 12 3 13 2 14 1 15
+constexpr uint64_t pack5(const int* v, int n) {
+    uint64_t r = 0;
+    for (int i = 0; i < n; ++i) r |= (uint64_t)v[i] << (5 * i);
+    return r;
+}
+constexpr int kOrderLo[12] = {16, 17, 18, 0, 8, 7, 9, 6, 10, 5, 11, 4};
+constexpr int kOrderHi[7] = {12, 3, 13, 2, 14, 1, 15};
+constexpr uint64_t kOrderLoBits = pack5(kOrderLo, 12), kOrderHiBits = pack5(kOrderHi, 7);
+__host__ __device__ __forceinline__ int cl_order(int i) {
+    return (int)(((i < 12 ? kOrderLoBits >> (5 * i) : kOrderHiBits >> (5 * (i - 12)))) & 31);
+}
+
+// literal / length + distance symbols of one block until end-of-block
+__host__ __device__ void inflate_codes(Inflater& z, const HuffLds& h) {
+    while (!z.err) {
+        const int sym = z.decode(h.lencnt, h.lensym);
+        if (sym < 0) { z.err |= FAL_PEAK_ST_CODE; return; }
+        if (sym < 256) {
+            if (z.out_pos >= z.out_cap) { z.err |= FAL_PEAK_ST_OVERFLOW; return; }
+            z.emit((uint8_t)sym);
+        } else if (sym == 256) {
+            return;
+        } else {
+            if (sym > 285) { z.err |= FAL_PEAK_ST_CODE; return; }
+            int base, extra;
+            length_base(sym - 257, &base, &extra);
+            const int len = base + (int)z.bits(extra);
+            const int ds = z.decode(h.distcnt, h.distsym);
+            if (ds < 0 || ds > 29) { z.err |= FAL_PEAK_ST_CODE; return; }
+            dist_base(ds, &base, &extra);
+            const int64_t dist = base + (int64_t)z.bits(extra);
+            if (z.err) return;
+            if (dist > z.out_pos) { z.err |= FAL_PEAK_ST_CODE; return; }
+            if (len > z.out_cap - z.out_pos) { z.err |= FAL_PEAK_ST_OVERFLOW; return; }
+            for (int k = 0; k < len; ++k) z.emit(z.out[z.out_pos - dist]);     // byte by byte: overlapping copies repeat
+        }
+    }
+}
+
+__host__ __device__ void inflate_fixed(Inflater& z, HuffLds& h) {
+    for (int s = 0; s < 320; s += 2) {
+        const int l0 = s < 144 ? 8 : s < 256 ? 9 : s < 280 ? 7 : s < 288 ? 8 : 5;
+        const int l1 = s + 1 < 144 ? 8 : s + 1 < 256 ? 9 : s + 1 < 280 ? 7 : s + 1 < 288 ? 8 : 5;
+        h.lengths[s >> 1] = (uint8_t)(l0 | (l1 << 4));
+    }
+    construct(h.lencnt, h.lensym, h.offs, h.lengths, 0, 288);
+    construct(h.distcnt, h.distsym, h.offs, h.lengths, 288, 30);
+    inflate_codes(z, h);
+}
+
+__host__ __device__ void inflate_dynamic(Inflater& z, HuffLds& h) {
+    const int nlen = (int)z.bits(5) + 257, ndist = (int)z.bits(5) + 1, ncode = (int)z.bits(4) + 4;
+    if (z.err) return;
+    if (nlen > 286 || ndist > 30) { z.err |= FAL_PEAK_ST_CODE; return; }
+    // code-length code: 19 lengths in their permuted order, kept in lengths[0 .. 19)
+    for (int i = 0; i < 19; ++i) set_len(h.lengths, i, 0);
+    for (int i = 0; i < ncode; ++i) set_len(h.lengths, cl_order(i), (int)z.bits(3));
+    if (z.err) return;
+    if (construct(h.lencnt, h.lensym, h.offs, h.lengths, 0, 19) != 0) { z.err |= FAL_PEAK_ST_CODE; return; }
+    int idx = 0;
+    while (idx < nlen + ndist) {
+        int sym = z.decode(h.lencnt, h.lensym);
+        if (sym < 0 || z.err) { z.err |= FAL_PEAK_ST_CODE; return; }
+        if (sym < 16) {
+            set_len(h.lengths, idx++, sym);
+            continue;
+        }
+        int val = 0, rep;
+        if (sym == 16) {
+            if (idx == 0) { z.err |= FAL_PEAK_ST_CODE; return; }
+            val = get_len(h.lengths, idx - 1);
+            rep = 3 + (int)z.bits(2);
+        } else if (sym == 17) {
+            rep = 3 + (int)z.bits(3);
+        } else {
+            rep = 11 + (int)z.bits(7);
+        }
+        if (z.err || idx + rep > nlen + ndist) { z.err |= FAL_PEAK_ST_CODE; return; }
+        while (rep--) set_len(h.lengths, idx++, val);
+    }
+    if (get_len(h.lengths, 256) == 0) { z.err |= FAL_PEAK_ST_CODE; return; }      // no end-of-block code
+    // the lengths live in lengths[0 .. nlen + ndist); the code-length code's tables are overwritten now
+    int left = construct(h.lencnt, h.lensym, h.offs, h.lengths, 0, nlen);
+    if (left < 0 || (left > 0 && nlen != h.lencnt[0] + h.lencnt[1])) { z.err |= FAL_PEAK_ST_CODE; return; }
+    left = construct(h.distcnt, h.distsym, h.offs, h.lengths, nlen, ndist);
+    if (left < 0 || (left > 0 && ndist != h.distcnt[0] + h.distcnt[1])) { z.err |= FAL_PEAK_ST_CODE; return; }
+    inflate_codes(z, h);
+}
+
+__host__ __device__ void inflate_stored(Inflater& z) {
+    z.bitbuf = 0;                                                       // to the byte boundary (fewer than 8 bits are held)
+    z.bitcnt = 0;
+    if (z.in_len - z.in_pos < 4) { z.err |= FAL_PEAK_ST_CODE; return; }
+    const uint32_t len = z.in[z.in_pos] | ((uint32_t)z.in[z.in_pos + 1] << 8);
+    const uint32_t nlen = z.in[z.in_pos + 2] | ((uint32_t)z.in[z.in_pos + 3] << 8);
+    z.in_pos += 4;
+    if (len != (~nlen & 0xFFFFu)) { z.err |= FAL_PEAK_ST_CODE; return; }
+    if ((int64_t)len > z.in_len - z.in_pos) { z.err |= FAL_PEAK_ST_CODE; return; }
+    if ((int64_t)len > z.out_cap - z.out_pos) { z.err |= FAL_PEAK_ST_OVERFLOW; return; }
+    for (uint32_t k = 0; k < len; ++k) z.emit(z.in[z.in_pos + k]);
+    z.in_pos += len;
+}
+
+// one zlib stream (in[0 .. in_len)) into out[0 .. out_cap): 0, or FAL_PEAK_ST_* bits.  Host-callable as well (the same code is
+// checked against zlib on the CPU).
+__host__ __device__ int inflate_stream(const uint8_t* in, int64_t in_len, uint8_t* out, int64_t out_cap, HuffLds& h) {
+    Inflater z;
+    z.in = in;
+    z.in_len = in_len;
+    z.in_pos = 0;
+    z.bitbuf = 0;
+    z.bitcnt = 0;
+    z.out = out;
+    z.out_cap = out_cap;
+    z.out_pos = 0;
+    z.s1 = 1;
+    z.s2 = 0;
+    z.err = 0;
+    // RFC 1950 header: CM = 8, CINFO <= 7, FCHECK, no preset dictionary
+    if (in_len < 2) return FAL_PEAK_ST_HEADER;
+    const uint32_t cmf = in[0], flg = in[1];
+    if ((cmf & 15) != 8 || (cmf >> 4) > 7 || ((cmf << 8) | flg) % 31 != 0 || (flg & 0x20)) return FAL_PEAK_ST_HEADER;
+    z.in_pos = 2;
+    int last = 0;
+    while (!last && !z.err) {
+        last = (int)z.bits(1);
+        const int type = (int)z.bits(2);
+        if (z.err) break;
+        if (type == 0) inflate_stored(z);
+        else if (type == 1) inflate_fixed(z, h);
+        else if (type == 2) inflate_dynamic(z, h);
+        else z.err |= FAL_PEAK_ST_CODE;
+    }
+    if (!z.err && z.out_pos != z.out_cap) z.err |= FAL_PEAK_ST_SHORT;
+    if (!z.err) {
+        const int64_t p = z.in_pos;                                     // the bit buffer holds < 8 bits: the trailer is byte aligned
+        if (in_len - p < 4) return FAL_PEAK_ST_ADLER;
+        const uint32_t want = ((uint32_t)in[p] << 24) | ((uint32_t)in[p + 1] << 16) | ((uint32_t)in[p + 2] << 8) | in[p + 3];
+        if (want != ((z.s2 << 16) | z.s1)) z.err |= FAL_PEAK_ST_ADLER;
+    }
+    return z.err;
+}
+
+__global__ __launch_bounds__(kInflateBlock) void pd_inflate_kernel(const int64_t* __restrict__ desc, int64_t n_arrays,
+                                                                   const uint8_t* __restrict__ dec, const int64_t* __restrict__ dec_len,
+                                                                   const int64_t* __restrict__ raw_off, int64_t inflate_bytes,
+                                                                   uint8_t* __restrict__ raw, int32_t* __restrict__ arr_status) {
+    __shared__ HuffLds tables[kInflateBlock];
+    HuffLds& h = tables[threadIdx.x];
+    for (int64_t a = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; a < n_arrays; a += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t* d = desc + 4 * a;
+        if (!(d[3] & FAL_PEAK_ZLIB) || arr_status[a]) continue;
+        const int64_t cap = array_bytes(d);
+        arr_status[a] = raw_off[a] + cap > inflate_bytes ? FAL_PEAK_ST_CAPACITY
+                                                         : inflate_stream(dec + d[0], dec_len[a], raw + raw_off[a], cap, h);
+    }
+}
+
+// ---- launch 5: convert + sort ---------------------------------------------------------------------------------------------
+__device__ __forceinline__ double load_value(const uint8_t* base, int64_t i, bool f64, bool be) {
+    if (f64) {
+        uint64_t u = reinterpret_cast<const uint64_t*>(base)[i];
+        if (be) u = __builtin_bswap64(u);
+        return __builtin_bit_cast(double, u);
+    }
+    uint32_t u = reinterpret_cast<const uint32_t*>(base)[i];
+    if (be) u = __builtin_bswap32(u);
+    return (double)__builtin_bit_cast(float, u);
+}
+
+struct ArrayView {
+    const uint8_t* base;
+    bool f64, be;
+    int stride, shift;               // element index = stride * peak + shift (mzXML pairs: 2p, 2p + 1)
+    __device__ __forceinline__ double at(int64_t p) const { return load_value(base, stride * p + shift, f64, be); }
+    // intensity: float32 data as stored, float64 data rounded to nearest (numpy's astype(float32))
+    __device__ __forceinline__ float at_f32(int64_t p) const {
+        if (f64) return (float)load_value(base, stride * p + shift, true, be);
+        uint32_t u = reinterpret_cast<const uint32_t*>(base)[stride * p + shift];
+        if (be) u = __builtin_bswap32(u);
+        return __builtin_bit_cast(float, u);
+    }
+};
+
+// np.sort order on float64: NaN after every number, NaNs equal among themselves, -0.0 == 0.0
+__device__ __forceinline__ bool key_less(double a, double b) { return a < b || (isnan(b) && !isnan(a)); }
+
+__global__ __launch_bounds__(256) void pd_convert_kernel(const int64_t* __restrict__ desc, int64_t n_arrays,
+                                                         const int64_t* __restrict__ spec, int64_t n_spec,
+                                                         const int32_t* __restrict__ arr_status, const uint8_t* __restrict__ dec,
+                                                         const uint8_t* __restrict__ raw, const int64_t* __restrict__ raw_off,
+                                                         const int64_t* __restrict__ indptr, int64_t nnz_cap,
+                                                         double* __restrict__ out_mz, float* __restrict__ out_it,
+                                                         int32_t* __restrict__ status) {
+    const int lane = threadIdx.x & 63;
+    const int64_t waves = (int64_t)gridDim.x * (blockDim.x >> 6);
+    for (int64_t s = blockIdx.x * (int64_t)(blockDim.x >> 6) + (threadIdx.x >> 6); s < n_spec; s += waves) {
+        const int64_t ma = spec[2 * s], ia = spec[2 * s + 1];
+        const int64_t b = indptr[s], e = indptr[s + 1], n = e - b;
+        int st = 0;
+        if (ma < 0 || ma >= n_arrays || ia < 0 || ia >= n_arrays) {
+            st = FAL_PEAK_ST_DESC;
+        } else {
+            const int64_t fm = desc[4 * ma + 3], fi = desc[4 * ia + 3];
+            const bool pairs = (fm & FAL_PEAK_PAIRS) != 0;
+            if (pairs != ((fi & FAL_PEAK_PAIRS) != 0) || (pairs && ma != ia) || desc[4 * ia + 2] != n) st = FAL_PEAK_ST_DESC;
+            st |= arr_status[ma] | arr_status[ia];
+        }
+        if (e > nnz_cap) st |= FAL_PEAK_ST_CAPACITY;
+        if (st) {
+            for (int64_t j = b + lane; j < std::min(e, nnz_cap); j += 64) {
+                out_mz[j] = 0.0;
+                out_it[j] = 0.0f;
+            }
+            if (lane == 0) status[s] = st;
+            continue;
+        }
+        auto view = [&](int64_t a, int shift) {
+            const int64_t* d = desc + 4 * a;
+            ArrayView v;
+            v.base = (d[3] & FAL_PEAK_ZLIB) ? raw + raw_off[a] : dec + d[0];
+            v.f64 = (d[3] & FAL_PEAK_F64) != 0;
+            v.be = (d[3] & FAL_PEAK_BIG_ENDIAN) != 0;
+            v.stride = (d[3] & FAL_PEAK_PAIRS) ? 2 : 1;
+            v.shift = (d[3] & FAL_PEAK_PAIRS) ? shift : 0;
+            return v;
+        };
+        const ArrayView vm = view(ma, 0), vi = view(ia, 1);
+        bool unsorted = false;
+        for (int64_t j = 1 + lane; j < n; j += 64) unsorted |= key_less(vm.at(j), vm.at(j - 1));
+        if (__ballot(unsorted) == 0) {
+            for (int64_t j = lane; j < n; j += 64) {
+                out_mz[b + j] = vm.at(j);
+                out_it[b + j] = vi.at_f32(j);
+            }
+        } else {
+            // stable rank: peaks with a smaller key, plus equal keys earlier in the array
+            for (int64_t j = lane; j < n; j += 64) {
+                const double kj = vm.at(j);
+                int64_t r = 0;
+                for (int64_t k = 0; k < n; ++k) {
+                    const double kk = vm.at(k);
+                    r += key_less(kk, kj) || (k < j && !key_less(kj, kk));
+                }
+                out_mz[b + r] = kj;
+                out_it[b + r] = vi.at_f32(j);
+            }
+        }
+        if (lane == 0) status[s] = 0;
+    }
+}
+
+FAL_WARM_KERNEL(pd_convert_kernel);
+
+}  // namespace
+}  // namespace fal
+
+using namespace fal;
+
+extern "C" int fal_decode_peaks(fal_ctx* ctx, const uint8_t* payload, int64_t payload_bytes, const int64_t* arrays, int64_t n_arrays,
+                                const int64_t* spectra, int64_t n_spectra, int64_t inflate_bytes, int64_t nnz_cap,
+                                int64_t* out_indptr, double* out_mz, float* out_intensity, int32_t* status_out) {
+    fal::CallScope _call(ctx);
+    FAL_REQUIRE(ctx && payload_bytes >= 0 && n_arrays >= 0 && n_spectra >= 0 && inflate_bytes >= 0 && nnz_cap >= 0, FAL_EINVAL,
+                "fal_decode_peaks: bad argument");
+    FAL_REQUIRE(out_indptr, FAL_EINVAL, "fal_decode_peaks: NULL out_indptr");
+    if (n_spectra == 0) {
+        FAL_CHECK_HIP(hipMemsetAsync(out_indptr, 0, sizeof(int64_t), ctx->stream));
+        return FAL_OK;
+    }
+    FAL_REQUIRE(spectra && status_out && (n_arrays == 0 || arrays), FAL_EINVAL, "fal_decode_peaks: NULL table");
+    FAL_REQUIRE(payload_bytes == 0 || payload, FAL_EINVAL, "fal_decode_peaks: NULL payload");
+    FAL_REQUIRE(nnz_cap == 0 || (out_mz && out_intensity), FAL_EINVAL, "fal_decode_peaks: NULL peaks");
+    const int64_t na = std::max<int64_t>(n_arrays, 1);
+    int32_t* arr_status = nullptr;
+    int64_t *cap = nullptr, *raw_off = nullptr, *count = nullptr, *dec_len = nullptr;
+    uint8_t *dec = nullptr, *raw = nullptr;
+    FAL_TRY(ctx->reserve(SLOT_MISC, sizeof(int32_t) * (size_t)na, (void**)&arr_status));
+    FAL_TRY(ctx->reserve(SLOT_MISC2, sizeof(int64_t) * (size_t)na, (void**)&cap));
+    FAL_TRY(ctx->reserve(SLOT_SORT2, sizeof(int64_t) * (size_t)(na + 1), (void**)&raw_off));
+    FAL_TRY(ctx->reserve(SLOT_TAIL, sizeof(int64_t) * (size_t)n_spectra, (void**)&count));
+    FAL_TRY(ctx->reserve(SLOT_TAIL2, sizeof(int64_t) * (size_t)na, (void**)&dec_len));
+    FAL_TRY(ctx->reserve(SLOT_TAIL3, (size_t)payload_bytes + 64, (void**)&dec));
+    FAL_TRY(ctx->reserve(SLOT_TAIL4, (size_t)inflate_bytes + 64, (void**)&raw));
+    const auto grid_for = [&](int64_t items, int per_block) {
+        return (unsigned)std::max<int64_t>(1, std::min<int64_t>(ceil_div(items, per_block), (int64_t)ctx->num_cus * 16));
+    };
+    if (n_arrays > 0) {
+        hipLaunchKernelGGL(pd_arrays_kernel, dim3(grid_for(n_arrays, 256)), dim3(256), 0, ctx->stream, arrays, n_arrays, payload_bytes,
+                           arr_status, cap);
+        FAL_CHECK_HIP(hipGetLastError());
+    }
+    FAL_TRY(device_scan_i64(ctx, cap, n_arrays, raw_off, SLOT_SORT));
+    hipLaunchKernelGGL(pd_counts_kernel, dim3(grid_for(n_spectra, 256)), dim3(256), 0, ctx->stream, arrays, n_arrays, spectra,
+                       n_spectra, count);
+    FAL_CHECK_HIP(hipGetLastError());
+    FAL_TRY(device_scan_i64(ctx, count, n_spectra, out_indptr, SLOT_DB));
+    if (n_arrays > 0) {
+        hipLaunchKernelGGL(pd_base64_kernel, dim3(grid_for(n_arrays, 4)), dim3(256), 0, ctx->stream, payload, arrays, n_arrays,
+                           arr_status, dec, dec_len);
+        FAL_CHECK_HIP(hipGetLastError());
+        hipLaunchKernelGGL(pd_inflate_kernel, dim3(grid_for(n_arrays, kInflateBlock)), dim3(kInflateBlock), 0, ctx->stream, arrays,
+                           n_arrays, dec, dec_len, raw_off, inflate_bytes, raw, arr_status);
+        FAL_CHECK_HIP(hipGetLastError());
+    }
+    hipLaunchKernelGGL(pd_convert_kernel, dim3(grid_for(n_spectra, 4)), dim3(256), 0, ctx->stream, arrays, n_arrays, spectra, n_spectra,
+                       arr_status, dec, raw, raw_off, out_indptr, nnz_cap, out_mz, out_intensity, status_out);
+    FAL_CHECK_HIP(hipGetLastError());
+    return FAL_OK;
+}

@@ -292,6 +292,36 @@ class Context:
         nnz_out = int(out_indptr[-1].item())
         return valid.bool(), out_indptr, out_mz[:nnz_out], out_it[:nnz_out]
 
+    def decode_peaks(self, payload, arrays, spectra):
+        """`fal_decode_peaks`: the binary arrays of mzML / mzXML spectra -> the raw CSR `process_spectra` takes, on the device.
+        payload u8[] (base64 text, arrays at 8-byte aligned offsets), arrays i64[n_arrays, 4] (offset, base64 length, declared
+        count, `_lib.PEAK_*` flags), spectra i64[n, 2] (m/z array, intensity array).
+        -> indptr i64[n+1], mz f64[nnz], intensity f32[nnz] (sorted by m/z per spectrum, as falcon._raw_csr), status i32[n]
+        (0 = decoded; else `_lib.PEAK_STATUS` bits, and that spectrum's peaks are zeros).  Device tensors; no sync."""
+        torch = _torch()
+        arrays = np.ascontiguousarray(arrays, np.int64).reshape(-1, 4)
+        spectra = np.ascontiguousarray(spectra, np.int64).reshape(-1, 2)
+        payload = np.frombuffer(payload, np.uint8) if isinstance(payload, (bytes, bytearray, memoryview)) else payload
+        n = len(spectra)
+        # sizes from the host copy of the tables (the kernels check every slot against them)
+        flags, counts = arrays[:, 3], arrays[:, 2]
+        nbytes = np.maximum(counts, 0) * np.where(flags & _lib.PEAK_F64, 8, 4) * np.where(flags & _lib.PEAK_PAIRS, 2, 1)
+        inflate_bytes = int(((nbytes + 7) // 8 * 8)[(flags & _lib.PEAK_ZLIB) != 0].sum())
+        ma = spectra[:, 0]
+        ok = (ma >= 0) & (ma < len(arrays))
+        nnz = int(np.maximum(counts[ma[ok]], 0).sum()) if len(arrays) else 0
+        indptr = self.empty((n + 1,), torch.int64)
+        mz = self.empty((max(nnz, 1),), torch.float64)
+        it = self.empty((max(nnz, 1),), torch.float32)
+        status = self.empty((max(n, 1),), torch.int32)
+        d_payload = self.to_dev(payload, torch.uint8) if len(payload) else None
+        d_arrays = self.to_dev(arrays) if len(arrays) else None
+        d_spectra = self.to_dev(spectra) if n else None
+        check(self.lib.fal_decode_peaks(self._h, self._p(d_payload), len(payload), self._p(d_arrays), len(arrays),
+                                        self._p(d_spectra), n, inflate_bytes, nnz, self._p(indptr), self._p(mz), self._p(it),
+                                        self._p(status)), "fal_decode_peaks")
+        return indptr, mz[:nnz], it[:nnz], status[:n]
+
     def rescore_neighbors(self, nb_idx, nb_dist, mz, intensity, indptr, order, fragment_tol: float, min_matches: int):
         """f4 (`fal_rescore_neighbors`): nb_dist <- 1 - matched-peak cosine (reference similarity.py:17-80), in place."""
         torch = _torch()

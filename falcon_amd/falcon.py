@@ -5,9 +5,9 @@ read peak files, preprocess, cluster every precursor charge independently throug
 (+ optional `<out>.mgf` of cluster representatives).
 
 Differences kept deliberately small and listed in DESIGN.md: spectra are held in memory /
-`.npz` files in `work_dir` instead of Lance datasets (lance is not available), only MGF input is built
-(mzML / mzXML are host XML parsing, out of scope), and `process_spectrum` runs as one batched device call
-per peak file (`fal_process_spectra`) instead of a Python loop over spectra.
+`.npz` files in `work_dir` instead of Lance datasets (lance is not available), the mzML / mzXML readers are stdlib
+XML passes whose binary arrays are decoded on the device (`fal_decode_peaks`), and `process_spectrum` runs as one batched
+device call per peak file (`fal_process_spectra`) instead of a Python loop over spectra.
 """
 from __future__ import annotations
 
@@ -296,42 +296,88 @@ def _take_rows(indptr: np.ndarray, rows: np.ndarray):
     return pos, out
 
 
+def _process(ctx, mz, it, indptr, pmz, charge, min_mz, max_mz):
+    """`fal_process_spectra` over one raw CSR (host or device arrays) -> valid, out indptr, mz, intensity as host arrays"""
+    valid, oip, omz, oit = ctx.process_spectra(
+        mz, it, indptr, pmz, charge, config.min_peaks, config.min_mz_range, min_mz, max_mz,
+        config.remove_precursor_tol, config.min_intensity, config.max_peaks_used,
+        None if config.scaling == "off" else config.scaling)
+    return valid.cpu().numpy(), oip.cpu().numpy(), omz.cpu().numpy(), oit.cpu().numpy()
+
+
+def _partition(parts, fn, ident, pmz, rt, charge, valid, oip, omz, oit) -> None:
+    """append the valid spectra of one batch to their charge partitions"""
+    for z in np.unique(charge[valid]):
+        rows = np.flatnonzero(valid & (charge == z))
+        pos, off = _take_rows(oip, rows)
+        p = parts.setdefault("None" if z == 0 else str(int(z)),
+                             dict(identifier=[], filename=[], precursor_mz=[], retention_time=[], mz=[], intensity=[],
+                                  counts=[]))
+        p["identifier"].append(ident[rows])
+        p["filename"].append(np.array([fn] * len(rows), dtype=str))
+        p["precursor_mz"].append(pmz[rows].astype(np.float32))
+        p["retention_time"].append(rt[rows])
+        p["mz"].append(omz[pos])
+        p["intensity"].append(oit[pos])
+        p["counts"].append(np.diff(off))
+
+
+def _prepare_chunk(chunk, fn, parts, min_mz, max_mz, ctx) -> int:
+    """one PeakChunk of an mzML / mzXML file: `fal_decode_peaks` -> `fal_process_spectra` with the peaks left on the device
+    -> charge partitions.  A spectrum whose arrays do not decode is dropped and logged.  -> the low-quality count (spectra
+    process_spectrum rejects, undecodable ones and those the reader skipped as unsupported)."""
+    from ._lib import PEAK_STATUS
+    for reason, k in sorted(chunk.skipped.items()):
+        logger.warning("Skipped %d spectra of %s: %s", k, fn, reason)
+    dropped = sum(chunk.skipped.values())
+    if not len(chunk):
+        return dropped
+    payload, arrays, spec = chunk.tables()
+    indptr, mz, it, status = ctx.decode_peaks(payload, arrays, spec)
+    pmz = np.array(chunk.precursor_mz, np.float64)
+    charge = np.array([int(c) if c else 0 for c in chunk.precursor_charge], np.int32)
+    valid, oip, omz, oit = _process(ctx, mz, it, indptr, pmz, charge, min_mz, max_mz)
+    status = status.cpu().numpy()
+    bad = status != 0
+    if bad.any():
+        for bit, what in PEAK_STATUS.items():
+            k = int(((status & bit) != 0).sum())
+            if k:
+                logger.warning("Skipped %d spectra of %s: binary array not decoded (%s)", k, fn, what)
+        valid = valid & ~bad
+    ident = np.array(chunk.identifier, dtype=str)
+    rt = np.array(chunk.retention_time, np.float32)
+    _partition(parts, fn, ident, pmz, rt, charge, valid, oip, omz, oit)
+    return dropped + int((~valid).sum())
+
+
 def _prepare_spectra(spectra_dir: str, min_mz: float, max_mz: float, ctx) -> List[str]:
     """falcon.py:247-328: read every peak file, preprocess (`process_spectrum`, spectrum.py:73-169 -- here one
-    `fal_process_spectra` call per file on the GPU), partition by precursor charge, one CSR `.npz` per charge."""
+    `fal_process_spectra` call per file on the GPU), partition by precursor charge, one CSR `.npz` per charge.
+    mzML / mzXML files go through their reader's chunks, `fal_decode_peaks` and `fal_process_spectra` with the peaks left on
+    the device (one chunk per call; a file whose payload is larger than one chunk is split between spectra)."""
     filenames = [fn for pattern in config.input_filenames for fn in glob.glob(pattern)]
     logger.info("Read spectra from %d peak file(s)", len(filenames))
     parts: Dict[str, Dict[str, list]] = {}
     low_quality = 0
     for fn in filenames:
         fn = os.path.abspath(fn)
+        read_chunks = ms_io.chunk_reader(fn)
+        if read_chunks is not None:                      # mzML / mzXML: binary arrays decoded on the device (fal_decode_peaks)
+            for chunk in read_chunks(fn):
+                low_quality += _prepare_chunk(chunk, fn, parts, min_mz, max_mz, ctx)
+            continue
         specs = list(ms_io.get_spectra(fn))
         if not specs:
             continue
         mz, it, indptr = _raw_csr(specs)
         pmz = np.array([s["precursor_mz"] for s in specs], np.float64)
         charge = np.array([int(s["precursor_charge"]) if s.get("precursor_charge") else 0 for s in specs], np.int32)
-        valid, oip, omz, oit = ctx.process_spectra(
-            mz, it, indptr, pmz, charge, config.min_peaks, config.min_mz_range, min_mz, max_mz,
-            config.remove_precursor_tol, config.min_intensity, config.max_peaks_used,
-            None if config.scaling == "off" else config.scaling)
-        valid, oip, omz, oit = valid.cpu().numpy(), oip.cpu().numpy(), omz.cpu().numpy(), oit.cpu().numpy()
-        low_quality += int((~valid).sum())
+        valid = _process(ctx, mz, it, indptr, pmz, charge, min_mz, max_mz)
+        low_quality += int((~valid[0]).sum())
         ident = np.array([str(s["identifier"]) for s in specs], dtype=str)
         rt = np.array([s.get("retention_time", -1) for s in specs], np.float32)
-        for z in np.unique(charge[valid]):
-            rows = np.flatnonzero(valid & (charge == z))
-            pos, off = _take_rows(oip, rows)
-            p = parts.setdefault("None" if z == 0 else str(int(z)),
-                                 dict(identifier=[], filename=[], precursor_mz=[], retention_time=[], mz=[], intensity=[],
-                                      counts=[]))
-            p["identifier"].append(ident[rows])
-            p["filename"].append(np.array([fn] * len(rows), dtype=str))
-            p["precursor_mz"].append(pmz[rows].astype(np.float32))
-            p["retention_time"].append(rt[rows])
-            p["mz"].append(omz[pos])
-            p["intensity"].append(oit[pos])
-            p["counts"].append(np.diff(off))
+        _partition(parts, fn, ident, pmz, rt, charge, *valid)
     n_total = 0
     for charge, p in parts.items():
         counts = np.concatenate(p["counts"])

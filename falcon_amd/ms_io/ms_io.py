@@ -1,13 +1,13 @@
 """Peak-file front door: pick the reader / writer by file extension (the role of the reference's
-falcon/ms_io/ms_io.py:11-66).  Only MGF is built in this tree; mzML / mzXML are host-side XML parsing and
-outside the hot-path scope."""
+falcon/ms_io/ms_io.py:11-66).  MGF, mzML and mzXML are read (the extension test is case-insensitive); only MGF is written.
+The XML readers also hand their binary arrays, still encoded, to the device decoder (`read_chunks`)."""
 import os
 
-from . import mgf_io
+from . import mgf_io, mzml_io, mzxml_io
 
-_READERS = {".mgf": mgf_io.get_spectra}
+_READERS = {".mgf": mgf_io.get_spectra, ".mzml": mzml_io.get_spectra, ".mzxml": mzxml_io.get_spectra}
+_CHUNK_READERS = {".mzml": mzml_io.read_chunks, ".mzxml": mzxml_io.read_chunks}
 _WRITERS = {".mgf": mgf_io.write_spectra}
-_KNOWN_BUT_UNBUILT = {".mzml", ".mzxml"}
 
 
 def _extension(path: str) -> str:
@@ -18,13 +18,15 @@ def get_spectra(filename: str):
     """Iterate over the spectra of a peak file as plain dicts (see mgf_io.get_spectra)."""
     if not os.path.isfile(filename):
         raise ValueError(f"Non-existing peak file {filename}")
-    ext = _extension(filename)
-    reader = _READERS.get(ext)
+    reader = _READERS.get(_extension(filename))
     if reader is None:
-        if ext in _KNOWN_BUT_UNBUILT:
-            raise ValueError(f"{ext} input is outside this build's scope (SURVEY section 2, row 6); convert to MGF")
-        raise ValueError(f'Unknown spectrum file type with extension "{ext}"')
+        raise ValueError(f'Unknown spectrum file type with extension "{_extension(filename)}"')
     yield from reader(filename)
+
+
+def chunk_reader(filename: str):
+    """the `read_chunks(filename, max_bytes)` of an mzML / mzXML file (spectra + still-encoded arrays), None for other types"""
+    return _CHUNK_READERS.get(_extension(filename))
 
 
 def write_spectra(filename: str, spectra) -> None:

@@ -387,6 +387,33 @@ int fal_process_spectra(fal_ctx* ctx, const double* mz, const float* intensity,
                         int scaling, int32_t* valid_out, int64_t* out_indptr, float* out_mz,
                         float* out_intensity);
 
+/* ---- peak-file payload decode (mzML / mzXML binary arrays) ------------------------------------------------------------------
+ * payload: the base64 text of every array of the call, concatenated (u8[payload_bytes]).
+ * arrays:  i64[n_arrays][4] = {offset into payload (multiple of 8), base64 length (multiple of 4, no whitespace),
+ *          declared value count (mzML defaultArrayLength / arrayLength, mzXML peaksCount = pairs), FAL_PEAK_* flags}.
+ * spectra: i64[n_spectra][2] = {m/z array, intensity array} (rows of `arrays`; an mzXML pair array is named twice).
+ * inflate_bytes: device scratch for the zlib arrays, at least the sum over zlib arrays of round_up(count x element size
+ *          (x 2 for pairs), 8); nnz_cap: room of out_mz / out_intensity (the sum of the m/z arrays' counts).
+ * -> out_indptr i64[n_spectra + 1] (the declared counts), out_mz f64, out_intensity f32 (sorted by m/z inside every spectrum,
+ *    stable: the order of np.lexsort((mz, row))), status_out i32[n_spectra]: 0, or FAL_PEAK_ST_* bits (that spectrum's peaks
+ *    are zeros).  A corrupt array never makes the call fail or write outside its slot. ------------------------------ [dev] */
+#define FAL_PEAK_F64         1   /* 64-bit values (else 32-bit) */
+#define FAL_PEAK_ZLIB        2   /* zlib stream (RFC 1950) */
+#define FAL_PEAK_BIG_ENDIAN  4   /* network byte order (mzXML) */
+#define FAL_PEAK_PAIRS       8   /* interleaved m/z-intensity pairs (mzXML) */
+#define FAL_PEAK_ST_DESC      1  /* bad descriptor: range outside the payload, misaligned, unknown flags, count mismatch */
+#define FAL_PEAK_ST_BASE64    2  /* a character outside the base64 alphabet, or misplaced padding */
+#define FAL_PEAK_ST_HEADER    4  /* bad zlib header */
+#define FAL_PEAK_ST_CODE      8  /* bad block type / Huffman code / distance, or the stream ends inside a block */
+#define FAL_PEAK_ST_OVERFLOW 16  /* more data than the declared count */
+#define FAL_PEAK_ST_SHORT    32  /* less data than the declared count */
+#define FAL_PEAK_ST_ADLER    64  /* Adler-32 trailer mismatch or missing */
+#define FAL_PEAK_ST_CAPACITY 128 /* inflate_bytes / nnz_cap too small */
+int fal_decode_peaks(fal_ctx* ctx, const uint8_t* payload, int64_t payload_bytes,
+                     const int64_t* arrays, int64_t n_arrays, const int64_t* spectra, int64_t n_spectra,
+                     int64_t inflate_bytes, int64_t nnz_cap, int64_t* out_indptr, double* out_mz,
+                     float* out_intensity, int32_t* status_out);
+
 /* ---- sort by precursor m/z (reference cluster.py:73-85 `.sort_values`): stable.
  *          order_out i64[n] (dataset row of sorted position), mz_sorted_out f32[n]. [dev] */
 int fal_sort_by_precursor(fal_ctx* ctx, const float* precursor_mz, int64_t n,

@@ -1,0 +1,124 @@
+"""mzML / mzXML input rate: where the time of reading a peak file goes, host XML pass against device decode.
+
+Writes seeded synthetic MS2 spectra (`synth.generate`, seed 42) as mzML (64-bit m/z, 32-bit intensity, zlib), mzXML (32-bit
+pairs, zlib, MS2 nested in MS1) and MGF, with an MS1 spectrum in front of every 10th MS2, then reports per XML format:
+  xml_pass_s       the reader's streaming XML pass (`read_chunks`: metadata + base64 payload descriptors)
+  host_decode_s    the same payload decoded with stdlib base64 + zlib on one host thread (`PeakChunk.host_spectra`)
+  decode_call_ms   `fal_decode_peaks` (device events around the call after one warm-up, the payload already on the device;
+                   its five kernels and two scans), and GB/s of base64 in; decode_call_with_upload_ms also copies the payload
+  prepare_*        `falcon._prepare_spectra` end to end (read, decode, process_spectrum, partitions) in spectra/s, and the
+                   MGF reader's on the same spectra
+then one JSON line per format.
+
+    python tools/peakfile_rate.py [--n 1000000] [--dir /tmp/peakfiles]
+"""
+import argparse
+import json
+import os
+import sys
+import tempfile
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+import numpy as np  # noqa: E402
+
+
+def _spectra(n):
+    from falcon_amd import synth
+    d = synth.generate(n, seed=42)
+    out = []
+    for i in range(n):
+        a, b = d["indptr"][i], d["indptr"][i + 1]
+        out.append({"identifier": str(i + 1), "precursor_mz": float(d["precursor_mz"][i]),
+                    "precursor_charge": int(d["precursor_charge"][i]), "retention_time": float(d["retention_time"][i]),
+                    "mz": d["mz"][a:b].astype(np.float64), "intensity": d["intensity"][a:b]})
+    return out
+
+
+def _prepare(fn, work):
+    from falcon_amd import falcon
+    from falcon_amd.cluster import spectrum
+    from falcon_amd.config import config
+    config.parse([fn, os.path.join(work, "out"), "--work_dir", work])
+    _, min_mz, max_mz = spectrum.get_dim(config.min_mz, config.max_mz, config.fragment_tol)
+    os.makedirs(os.path.join(work, "spectra"), exist_ok=True)
+    return lambda ctx: falcon._prepare_spectra(os.path.join(work, "spectra"), min_mz, max_mz, ctx)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--n", type=int, default=1_000_000)
+    ap.add_argument("--dir", default=None)
+    a = ap.parse_args()
+    import torch
+    from falcon_amd.device import Context
+    from falcon_amd.ms_io import ms_io, mzml_io, mzxml_io
+    from tests import peakfile_writer as W
+    out_dir = a.dir or tempfile.mkdtemp()
+    os.makedirs(out_dir, exist_ok=True)
+    t0 = time.perf_counter()
+    spectra = _spectra(a.n)
+    files = {"mzML": os.path.join(out_dir, "run.mzML"), "mzXML": os.path.join(out_dir, "run.mzXML"),
+             "MGF": os.path.join(out_dir, "run.mgf")}
+    W.write_mzml(files["mzML"], spectra, mz_bits=64, int_bits=32, zlib_arrays=True, ms1_every=10)
+    W.write_mzxml(files["mzXML"], spectra, bits=32, zlib_arrays=True, ms1_every=10, nested=True)
+    ms_io.write_spectra(files["MGF"], spectra)
+    del spectra
+    print(f"wrote {a.n} spectra in 3 formats in {time.perf_counter() - t0:.1f} s:",
+          {k: os.path.getsize(v) for k, v in files.items()}, flush=True)
+    ctx = Context(0)
+    ctx.plan(0)
+    rows = {}
+    for fmt, reader in (("mzML", mzml_io), ("mzXML", mzxml_io)):
+        t0 = time.perf_counter()
+        chunks = list(reader.read_chunks(files[fmt]))
+        xml_s = time.perf_counter() - t0
+        n_spec = sum(len(c) for c in chunks)
+        b64 = sum(c.nbytes for c in chunks)
+        t0 = time.perf_counter()
+        n_host = sum(1 for c in chunks for _ in c.host_spectra())
+        host_s = time.perf_counter() - t0
+        tables = [c.tables() for c in chunks]
+        ctx.decode_peaks(*tables[0])                                    # warm-up: code objects, scratch slots
+        ms = {}
+        for what in ("with_upload", "on_device"):
+            # on_device: the payload is on the device before the call (the descriptor tables are still uploaded by it)
+            args = tables if what == "with_upload" else [(torch.from_numpy(p).cuda(), a_, s_) for p, a_, s_ in tables]
+            torch.cuda.synchronize()
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for t in args:
+                st = ctx.decode_peaks(*t)[3]
+            e1.record()
+            torch.cuda.synchronize()
+            ms[what] = e0.elapsed_time(e1)
+            del args
+        bad = int((st != 0).sum().item())
+        del tables, chunks
+        kern_ms = ms["on_device"]
+        rows[fmt] = dict(format=fmt, spectra=n_spec, host_decoded=n_host, status_nonzero=bad, base64_bytes=b64,
+                         xml_pass_s=round(xml_s, 2), host_decode_s=round(host_s, 2), decode_call_ms=round(kern_ms, 2),
+                         decode_call_with_upload_ms=round(ms["with_upload"], 2),
+                         decode_GBps=round(b64 / (kern_ms * 1e-3) / 1e9, 2), host_decode_GBps=round(b64 / host_s / 1e9, 3))
+        print(rows[fmt], flush=True)
+    for fmt in ("mzML", "mzXML", "MGF"):
+        run = _prepare(files[fmt], tempfile.mkdtemp(dir=out_dir))
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        charges = run(ctx)
+        torch.cuda.synchronize()
+        s = time.perf_counter() - t0
+        row = rows.setdefault(fmt, dict(format=fmt))
+        row.update(prepare_s=round(s, 2), prepare_spectra_per_s=round(a.n / s), charges=charges)
+        print(fmt, "prepare", row["prepare_s"], "s", flush=True)
+    for fmt in ("mzML", "mzXML"):
+        rows[fmt]["mgf_prepare_spectra_per_s"] = rows["MGF"]["prepare_spectra_per_s"]
+    for row in rows.values():
+        print(json.dumps(dict(tool="peakfile_rate", n=a.n, **row)), flush=True)
+    ctx.close()
+
+
+if __name__ == "__main__":
+    main()
