@@ -8,9 +8,21 @@
 // component (<= kMaxComp peaks a side, per-lane scratch).  Window arithmetic is the reference's: `peak_mz - tol` in float64,
 // `abs(peak_mz - other_mz)` in float32 against the float64 tolerance; pair costs are float32 products; the positive pair
 // scores are summed in query-peak order in float64.
+//
+// Pure functions, compiled for both sides: tests/test_peakmatch_cpu.py builds this header with the host compiler and checks
+// it against the oracle's `cosine_fast`.
 #pragma once
 #include <math.h>
+#ifdef __HIPCC__
 #include "common.h"
+#else                        // plain host compiler (the CPU tests' shim): the qualifiers mean nothing there
+#include <stdint.h>
+#ifndef __host__
+#define __host__
+#define __device__
+#define __forceinline__ inline
+#endif
+#endif
 
 namespace fal {
 
@@ -23,15 +35,17 @@ struct PeakLists {
     const float* bit;
 };
 
+__host__ __device__ inline int imax(int a, int b) { return a > b ? a : b; }     // (HIP's own max is device-only)
+
 // weight of (component row r, column q): the float32 product inside the row's window, else 0
-__device__ __forceinline__ float comp_w(const PeakLists& s, const int* rp, const int* rs, const int* re, int r, int q) {
+__host__ __device__ __forceinline__ float comp_w(const PeakLists& s, const int* rp, const int* rs, const int* re, int r, int q) {
     return (q >= rs[r] && q < re[r]) ? s.ait[rp[r]] * s.bit[q] : 0.f;
 }
 
 // maximum-weight assignment of one component (rows = query peaks rp[0..nr), columns [qs, qe)); adds the
 // positive pair scores in row order.  Returns false when the component is larger than kMaxComp.
-__device__ inline bool solve_component(const PeakLists& s, const int* rp, const int* rs, const int* re, int nr, int qs, int qe,
-                                double* score, int* n_match) {
+__host__ __device__ inline bool solve_component(const PeakLists& s, const int* rp, const int* rs, const int* re, int nr, int qs,
+                                                int qe, double* score, int* n_match) {
     const int nc = qe - qs;
     if (nr == 1) {                                    // one query peak: its best partner
         float best = 0.f;
@@ -125,7 +139,7 @@ __device__ inline bool solve_component(const PeakLists& s, const int* rp, const 
 }
 
 // The whole pair: score (before clipping) and matched peaks.  Returns false when a component is larger than kMaxComp.
-__device__ inline bool pair_score(const PeakLists& s, int na, int nb, double tol, double* score_out, int* n_match_out) {
+__host__ __device__ inline bool pair_score(const PeakLists& s, int na, int nb, double tol, double* score_out, int* n_match_out) {
     double score = 0.0;
     int n_match = 0;
     bool ok = true;
@@ -149,7 +163,7 @@ __device__ inline bool pair_score(const PeakLists& s, int na, int nb, double tol
                 re[nr] = q;
             }
             ++nr;
-            qe = nr == 1 ? q : max(qe, q);
+            qe = nr == 1 ? q : imax(qe, q);
         }
         if (nr > 0) ok = solve_component(s, rp, rs, re, nr, qs, qe, &score, &n_match) && ok;
     }
@@ -159,7 +173,7 @@ __device__ inline bool pair_score(const PeakLists& s, int na, int nb, double tol
 }
 
 // cosine distance of a scored pair: 1 - sim, sim clipped to [0, 1] (similarity.py:78) and 0 below min_matches (cluster.py:624-626)
-__device__ __forceinline__ double pair_distance(double score, int n_match, int min_matches) {
+__host__ __device__ __forceinline__ double pair_distance(double score, int n_match, int min_matches) {
     double sim = fmax(0.0, fmin(score, 1.0));
     if (n_match < min_matches) sim = 0.0;
     return 1.0 - sim;
@@ -178,7 +192,7 @@ struct ExactPeaks {
 
 // the reference's pair distance of sorted rows i < j (i is the query spectrum, cluster.py:593-639); *ok cleared when a
 // component is larger than kMaxComp
-__device__ inline double exact_distance(const ExactPeaks& pk, int64_t i, int64_t j, bool* ok) {
+__host__ __device__ inline double exact_distance(const ExactPeaks& pk, int64_t i, int64_t j, bool* ok) {
     const int64_t a = pk.order[i], b = pk.order[j];
     const int64_t a0 = pk.indptr[a], b0 = pk.indptr[b];
     const PeakLists s{pk.mz + a0, pk.it + a0, pk.mz + b0, pk.it + b0};

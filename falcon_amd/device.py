@@ -422,8 +422,10 @@ class Context:
     # ------------------------------------------------------------------ f5 exact mode
     def _peaks(self, mz, intensity, indptr, order):
         torch = _torch()
-        return (self.to_dev(mz, torch.float32), self.to_dev(intensity, torch.float32), self.to_dev(indptr, torch.int64),
-                self.to_dev(order, torch.int64))
+        mz, intensity = self.to_dev(mz, torch.float32), self.to_dev(intensity, torch.float32)
+        if mz.numel() == 0:                  # spectra without a single peak: an empty tensor has no address, the library takes no NULL
+            mz, intensity = self.empty((1,), torch.float32), self.empty((1,), torch.float32)
+        return mz, intensity, self.to_dev(indptr, torch.int64), self.to_dev(order, torch.int64)
 
     @staticmethod
     def _check_order(order, indptr, n_out: int, what: str):
