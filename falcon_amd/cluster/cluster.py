@@ -820,3 +820,27 @@ def generate_clusters(dataset, linkage: str, distance_threshold: float, min_matc
                 p.n_probe, p.n_neighbors, p.n_neighbors_ann, p.eps)
     labels, medoids = pipe.run(dataset, precursor_tol_mass, precursor_tol_mode, rt_tol, fragment_tol, batch_size, p)
     return labels.cpu().numpy(), medoids.cpu().numpy()
+
+
+def consensus_spectra(dataset, labels, medoids, fragment_tol: float, min_fraction: float = 0.25,
+                      pipeline: Optional[ClusterPipeline] = None):
+    """Consensus representatives of the clusters `generate_clusters` returned for `dataset` (a SpectrumDataset on the host or the
+    device, or what `generate_clusters` accepts): every cluster's members merged peak by peak (`fal_consensus_spectra`; DESIGN.md
+    "Consensus representatives").  A merged peak is kept when min(its peaks, members) >= max(1, ceil(min_fraction * members)).
+
+    Returns (indptr int64[n_clusters + 1], mz float32[], intensity float32[], status int32[n_clusters]): cluster c's consensus
+    peaks are mz / intensity[indptr[c]:indptr[c + 1]] in m/z order, L2-normalised; status bit `_lib.CONS_FALLBACK` marks the
+    clusters without a kept peak, which carry their medoid's peaks; a cluster of one member carries that member's peaks."""
+    global _default_pipeline
+    if not isinstance(dataset, SpectrumDataset):
+        dataset = SpectrumDataset.from_table(
+            dataset.to_table(columns=["precursor_mz", "precursor_charge", "retention_time", "mz", "intensity"])
+            if hasattr(dataset, "to_table") else dataset)
+    if not 0.0 < float(min_fraction) <= 1.0:
+        raise ValueError("min_fraction must lie in (0, 1]")
+    pipe = pipeline or _default_pipeline
+    if pipe is None:
+        pipe = _default_pipeline = ClusterPipeline()
+    indptr, mz, intensity, status = pipe.ctx.consensus_spectra(dataset.mz, dataset.intensity, dataset.indptr, labels, medoids,
+                                                               fragment_tol, min_fraction)
+    return indptr.cpu().numpy(), mz.cpu().numpy(), intensity.cpu().numpy(), status.cpu().numpy()

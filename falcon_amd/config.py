@@ -35,6 +35,12 @@ class Config:
         p.add_argument("--overwrite", action="store_true", help="Overwrite existing results.")
         p.add_argument("--export_representatives", action="store_true",
                        help="Export cluster representatives to an MGF file.")
+        p.add_argument("--representatives", type=str, default="medoid", choices=["medoid", "consensus"],
+                       help="Peaks of an exported representative: the cluster's medoid spectrum (default), or the consensus "
+                            "of its members merged peak by peak (needs --export_representatives).")
+        p.add_argument("--consensus_min_fraction", type=float, default=0.25,
+                       help="Consensus representatives: a merged peak is kept when at least this fraction of the cluster's "
+                            "members' worth of peaks falls into it (0 < q <= 1, default: 0.25).")
         # CLUSTERING  (config.py:76-124)
         p.add_argument("--precursor_tol", nargs=2, default=[20, "ppm"],
                        help='Precursor tolerance mass and mode (default: 20 ppm). Mode is "ppm" or "Da".')
@@ -160,6 +166,12 @@ class Config:
             self._parser.error(f"--linkage {ns['linkage']} needs --clustering hierarchical (DBSCAN has no linkage)")
         if ns["clustering"] == "hierarchical":
             ns["rescore"] = True
+        if not 0.0 < ns["consensus_min_fraction"] <= 1.0:
+            self._parser.error(f"--consensus_min_fraction {ns['consensus_min_fraction']} is outside (0, 1]")
+        if ns["representatives"] not in ("medoid", "consensus"):          # (a config file's value: choices guard the command line)
+            self._parser.error(f"--representatives {ns['representatives']}: medoid or consensus")
+        if ns["representatives"] == "consensus" and not ns["export_representatives"]:
+            self._parser.error("--representatives consensus needs --export_representatives (there is no other output it changes)")
         if not 1 <= ns["low_dim"] <= 800:
             raise ValueError("low_dim must be an integer in [1, 800] (README.md:114-117; the widest rows the kernels hold)")
         if ns["n_neighbors_ann"] < ns["n_neighbors"]:

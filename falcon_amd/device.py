@@ -322,6 +322,37 @@ class Context:
                                         self._p(status)), "fal_decode_peaks")
         return indptr, mz[:nnz], it[:nnz], status[:n]
 
+    def consensus_spectra(self, mz, intensity, indptr, labels, medoids, fragment_tol: float, min_fraction: float = 0.25,
+                          nnz_cap: Optional[int] = None):
+        """`fal_consensus_spectra`: every cluster's members merged peak by peak (DESIGN.md "Consensus representatives").
+        mz / intensity f32, indptr i64[n+1]: the preprocessed peaks by dataset row; labels i32[n] in [0, n_clusters); medoids
+        i32[n_clusters].  nnz_cap: room for the output peaks (default: the dataset's peak count, which always suffices).
+        -> indptr i64[n_clusters+1], mz f32, intensity f32, status i32[n_clusters] of `_lib.CONS_*` bits.  Device tensors;
+        synchronises.  Raises FalconHipError when nnz_cap is too small for the output (indptr would point behind the peaks
+        returned); the C entry point itself reports that per cluster with `_lib.CONS_CAPACITY`."""
+        torch = _torch()
+        mz = self.to_dev(mz, torch.float32)
+        intensity = self.to_dev(intensity, torch.float32)
+        indptr = self.to_dev(indptr, torch.int64)
+        labels = self.to_dev(labels, torch.int32)
+        medoids = self.to_dev(medoids, torch.int32)
+        n, nc = int(labels.shape[0]), int(medoids.shape[0])
+        if indptr.shape[0] != n + 1:
+            raise ValueError(f"consensus_spectra: indptr has {indptr.shape[0]} entries for {n} labels")
+        cap = int(mz.shape[0]) if nnz_cap is None else int(nnz_cap)
+        out_indptr = self.empty((nc + 1,), torch.int64)
+        out_mz = self.empty((max(cap, 1),), torch.float32)
+        out_it = self.empty((max(cap, 1),), torch.float32)
+        status = self.empty((max(nc, 1),), torch.int32)
+        check(self.lib.fal_consensus_spectra(self._h, self._p(mz), self._p(intensity), self._p(indptr), n, self._p(labels),
+                                             self._p(medoids), nc, float(fragment_tol), float(min_fraction), cap,
+                                             self._p(out_indptr), self._p(out_mz), self._p(out_it), self._p(status)),
+              "fal_consensus_spectra")
+        used = int(out_indptr[-1].item())
+        if used > cap:
+            raise FalconHipError(f"consensus_spectra: the consensus holds {used} peaks, nnz_cap = {cap} is too small")
+        return out_indptr, out_mz[:used], out_it[:used], status[:nc]
+
     def rescore_neighbors(self, nb_idx, nb_dist, mz, intensity, indptr, order, fragment_tol: float, min_matches: int):
         """f4 (`fal_rescore_neighbors`): nb_dist <- 1 - matched-peak cosine (reference similarity.py:17-80), in place."""
         torch = _torch()

@@ -58,6 +58,9 @@ def main(args: Union[str, List[str], None] = None) -> int:
 
 def _option_lines() -> List[str]:
     c = config
+    # (the consensus options are listed only when chosen: the default header stays what it was)
+    extra = ([f"representatives = {c.representatives}", f"consensus_min_fraction = {c.consensus_min_fraction:.3f}"]
+             if c.representatives == "consensus" else [])
     return [
         f"work_dir = {c.work_dir}", f"overwrite = {c.overwrite}",
         f"export_representatives = {c.export_representatives}",
@@ -73,7 +76,7 @@ def _option_lines() -> List[str]:
         f"n_neighbors_ann = {c.n_neighbors_ann}", f"low_dim = {c.low_dim}", f"mz_interval = {c.mz_interval}",
         f"rescore = {c.rescore}", f"clustering = {c.clustering}", f"dtype = {c.dtype}",
         f"exact = {c.exact}",
-    ]
+    ] + extra
 
 
 def _run(args) -> int:
@@ -104,7 +107,8 @@ def _run(args) -> int:
         labels, medoids = cluster.generate_clusters(
             ds, config.linkage, config.distance_threshold, config.min_matched_peaks, config.precursor_tol[0],
             config.precursor_tol[1], config.rt_tol, config.fragment_tol, config.batch_size, ann=ann, pipeline=pipe)
-        current_label = _emit_charge(part, charge, labels, medoids, current_label, rows_all, representatives)
+        current_label = _emit_charge(part, charge, labels, medoids, current_label, rows_all, representatives,
+                                     _consensus(pipe.ctx, part, charge, labels, medoids))
     _write_outputs(rows_all, representatives)
     if rm_work_dir:
         shutil.rmtree(config.work_dir)
@@ -163,8 +167,29 @@ def _ann_params():
                             exact=config.exact)
 
 
-def _emit_charge(part, charge, labels, medoids, current_label, rows_all, representatives) -> int:
-    """one charge's labels (by row of its partition) and medoid rows -> CSV rows and representatives; -> the next label"""
+def _consensus(ctx, part, charge, labels, medoids):
+    """`--representatives consensus`: the consensus peaks of one charge's clusters (`fal_consensus_spectra`) as host arrays
+    (indptr, mz, intensity); None with medoid representatives"""
+    if config.representatives != "consensus" or not config.export_representatives:
+        return None
+    from ._lib import CONS_FALLBACK, CONS_GLOBAL
+    indptr, mz, it, status = ctx.consensus_spectra(part["mz"], part["intensity"], part["indptr"], labels, medoids,
+                                                   config.fragment_tol, config.consensus_min_fraction)
+    status = status.cpu().numpy()
+    # (CONS_GLOBAL only says which sort a large cluster took; the peak count given as capacity always suffices, so the
+    # capacity bit -- or a bit this code does not know -- is an error)
+    bad = status & ~(CONS_FALLBACK | CONS_GLOBAL)
+    if bad.any():
+        raise RuntimeError(f"consensus representatives of charge {charge}: status bits {int(np.bitwise_or.reduce(bad))} on "
+                           f"{int((bad != 0).sum())} clusters")
+    logger.info("Consensus representatives of charge %s: %d clusters, %d fell back to their medoid (no merged peak reached "
+                "the quorum)", charge, len(status), int(((status & CONS_FALLBACK) != 0).sum()))
+    return indptr.cpu().numpy(), mz.cpu().numpy(), it.cpu().numpy()
+
+
+def _emit_charge(part, charge, labels, medoids, current_label, rows_all, representatives, consensus=None) -> int:
+    """one charge's labels (by row of its partition) and medoid rows -> CSV rows and representatives; -> the next label.
+    consensus (indptr, mz, intensity by cluster): the representatives' peaks; everything else stays the medoid's"""
     n = len(part["precursor_mz"])
     labels = labels + current_label                                                            # falcon.py:189-193
     current_label = int(labels.max()) + 1
@@ -178,8 +203,11 @@ def _emit_charge(part, charge, labels, medoids, current_label, rows_all, represe
             representatives.append({
                 "identifier": str(part["identifier"][m]), "precursor_mz": float(part["precursor_mz"][m]),
                 "precursor_charge": None if charge == "None" else int(charge),
-                "retention_time": float(part["retention_time"][m]), "mz": part["mz"][ip[m]:ip[m + 1]],
-                "intensity": part["intensity"][ip[m]:ip[m + 1]], "cluster": int(labels[m])})
+                "retention_time": float(part["retention_time"][m]),
+                "mz": part["mz"][ip[m]:ip[m + 1]] if consensus is None else consensus[1][consensus[0][c]:consensus[0][c + 1]],
+                "intensity": (part["intensity"][ip[m]:ip[m + 1]] if consensus is None
+                              else consensus[2][consensus[0][c]:consensus[0][c + 1]]),
+                "cluster": int(labels[m])})
     return current_label
 
 
@@ -263,9 +291,18 @@ def _run_distributed() -> int:
             runner.close()
         if rank == 0:
             rows_all, current_label, representatives = [], 0, []
-            for charge, part, (labels, medoids) in zip(charges, parts, merged):
-                if len(labels):
-                    current_label = _emit_charge(part, charge, labels, medoids, current_label, rows_all, representatives)
+            cons_ctx = None
+            if config.representatives == "consensus":     # a context of rank 0's own, as for the preparation of the partitions
+                from .device import Context
+                cons_ctx = Context(device)
+            try:
+                for charge, part, (labels, medoids) in zip(charges, parts, merged):
+                    if len(labels):
+                        cons = _consensus(cons_ctx, part, charge, labels, medoids) if cons_ctx is not None else None
+                        current_label = _emit_charge(part, charge, labels, medoids, current_label, rows_all, representatives, cons)
+            finally:
+                if cons_ctx is not None:
+                    cons_ctx.close()
             _write_outputs(rows_all, representatives)
         dist.barrier()
         if rank == 0 and state[2]:

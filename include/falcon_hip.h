@@ -414,6 +414,31 @@ int fal_decode_peaks(fal_ctx* ctx, const uint8_t* payload, int64_t payload_bytes
                      int64_t inflate_bytes, int64_t nnz_cap, int64_t* out_indptr, double* out_mz,
                      float* out_intensity, int32_t* status_out);
 
+/* ---- consensus representatives: the members of every cluster merged peak by peak (the reference exports medoids only,
+ *          falcon.py:198-203; DESIGN.md "Consensus representatives" states the definition).
+ * mz / intensity f32, indptr i64[n+1]: the preprocessed peaks in dataset-row order (fewer than 2^31 in all); labels i32[n]:
+ * one cluster id in [0, n_clusters) per row (a row with another value belongs to no cluster); medoids i32[n_clusters].
+ * Cluster c of m members: m = 1 -> its member's peaks as they are.  Else the members' peaks are pooled in the order (m/z,
+ * dataset row, peak index); a group is a maximal run whose neighbours lie within fragment_tol ((double)mz[k] - (double)mz[k-1]
+ * > fragment_tol starts a new one: peaks chain); it is kept when min(peaks of the group, m) >= max(1, ceil(min_fraction m))
+ * (support counts peaks, not members); a kept group gives m/z = sum(mz * intensity) / sum(intensity) (the plain mean when the
+ * intensities sum to 0) and intensity = sum(intensity) / m, float64 sums in pooled order, then L2-normalised over the kept
+ * groups in m/z order (all 0 when the norm is 0).  No group kept (or no member): the medoid's peaks as they are,
+ * FAL_CONS_ST_FALLBACK.
+ * -> out_indptr i64[n_clusters + 1] (always the true sizes), out_mz / out_intensity f32 with room for nnz_cap peaks
+ *    (indptr[n] always suffices), status_out i32[n_clusters] of FAL_CONS_ST_* bits.  A cluster whose peaks would end behind
+ *    nnz_cap gets FAL_CONS_ST_CAPACITY and writes nothing; the others are complete.  FAL_CONS_ST_GLOBAL marks the clusters
+ *    with more than FAL_CONS_LDS_PEAKS pooled peaks, sorted by the device-wide radix sort instead of inside one workgroup:
+ *    same bits either way.  One stream synchronisation (the pooled sizes decide the scratch); no per-cluster host work. [dev] */
+#define FAL_CONS_LDS_PEAKS 4096
+#define FAL_CONS_ST_FALLBACK 1   /* no group reached the quorum: the medoid's peaks */
+#define FAL_CONS_ST_GLOBAL   2   /* pooled peaks sorted by the device-wide sort */
+#define FAL_CONS_ST_CAPACITY 4   /* nnz_cap too small for this cluster: nothing written for it */
+int fal_consensus_spectra(fal_ctx* ctx, const float* mz, const float* intensity, const int64_t* indptr, int64_t n,
+                          const int32_t* labels, const int32_t* medoids, int64_t n_clusters, double fragment_tol,
+                          double min_fraction, int64_t nnz_cap, int64_t* out_indptr, float* out_mz, float* out_intensity,
+                          int32_t* status_out);
+
 /* ---- sort by precursor m/z (reference cluster.py:73-85 `.sort_values`): stable.
  *          order_out i64[n] (dataset row of sorted position), mz_sorted_out f32[n]. [dev] */
 int fal_sort_by_precursor(fal_ctx* ctx, const float* precursor_mz, int64_t n,
