@@ -17,6 +17,8 @@ FAL_DTYPE_F32, FAL_DTYPE_F16, FAL_DTYPE_SPLIT16, FAL_OUT_F32_F16, FAL_OUT_F16_IM
 PEAK_F64, PEAK_ZLIB, PEAK_BIG_ENDIAN, PEAK_PAIRS = 1, 2, 4, 8
 PEAK_STATUS = {1: "bad descriptor", 2: "bad base64", 4: "bad zlib header", 8: "bad deflate stream", 16: "more values than declared",
                32: "fewer values than declared", 64: "Adler-32 mismatch", 128: "decode buffer too small"}
+# fal_mgf_index / fal_mgf_parse: flags of a text the host reader has to read, and the per-spectrum status (include/falcon_hip.h)
+MGF_FLAG_BYTES, MGF_FLAG_LINES, MGF_ST_HOST = 1, 2, 1
 # fal_consensus_spectra: per-cluster status bits, and the pooled peaks one workgroup sorts in LDS (include/falcon_hip.h)
 CONS_FALLBACK, CONS_GLOBAL, CONS_CAPACITY, CONS_LDS_PEAKS = 1, 2, 4, 4096
 STAGES = {"vectorize": 0, "build": 1, "coarse": 2, "scan": 3, "select": 4, "filter": 5, "dbscan": 6, "tail": 7,
@@ -105,6 +107,9 @@ _SIGNATURES = {
     "fal_gather_f32": ([c_void_p, c_void_p, c_void_p, c_int64, c_void_p], c_int),
     "fal_decode_peaks": ([c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_int64, c_int64, c_void_p, c_void_p,
                           c_void_p, c_void_p], c_int),
+    "fal_mgf_index": ([c_void_p, c_void_p, c_int64, P(c_int64)], c_int),
+    "fal_mgf_parse": ([c_void_p, c_void_p, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                       c_void_p, c_void_p, c_void_p, c_void_p], c_int),
     "fal_consensus_spectra": ([c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_double, c_double,
                                c_int64, c_void_p, c_void_p, c_void_p, c_void_p], c_int),
 }

@@ -81,6 +81,8 @@ class Config:
                        help="Re-score the nearest neighbours with the matched-peak cosine (fragment_tol, "
                             "min_matched_peaks) before clustering.")
         p.add_argument("--device", type=int, default=0, help="HIP device ordinal.")
+        p.add_argument("--mgf_reader", type=str, default="device", choices=["device", "host"],
+                       help="MGF input: parse the text on the GPU (device), or with the host reader; the outputs are the same.")
         p.add_argument("--distributed", action="store_true",
                        help="Run as one rank of a multi-GPU job launched by `python -m torch.distributed.run --module "
                             "falcon_amd.falcon ...`: the precursor windows / buckets of every charge are dealt to the ranks, "
@@ -170,6 +172,8 @@ class Config:
             self._parser.error(f"--consensus_min_fraction {ns['consensus_min_fraction']} is outside (0, 1]")
         if ns["representatives"] not in ("medoid", "consensus"):          # (a config file's value: choices guard the command line)
             self._parser.error(f"--representatives {ns['representatives']}: medoid or consensus")
+        if ns["mgf_reader"] not in ("device", "host"):
+            self._parser.error(f"--mgf_reader {ns['mgf_reader']}: device or host")
         if ns["representatives"] == "consensus" and not ns["export_representatives"]:
             self._parser.error("--representatives consensus needs --export_representatives (there is no other output it changes)")
         if not 1 <= ns["low_dim"] <= 800:

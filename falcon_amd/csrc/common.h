@@ -37,7 +37,7 @@ void set_error(const char* fmt, ...);
     } while (0)
 
 constexpr int kNumStages = 9;
-constexpr int kNumSlots = 37;   // scratch slots of a context (ivf.h names them)
+constexpr int kNumSlots = 42;   // scratch slots of a context (ivf.h names them)
 enum Stage { ST_VECTORIZE = 0, ST_BUILD = 1, ST_COARSE = 2, ST_SCAN = 3, ST_SELECT = 4,
              ST_FILTER = 5, ST_DBSCAN = 6, ST_TAIL = 7,
              ST_KERNEL = 8 };   // the launches of the cosine kernel alone (dense_kernel / scan16_kernel / list16_kernel / ivf_list4_kernel;
@@ -77,6 +77,14 @@ struct fal_ctx {
                                           // search (flat / IVF buckets), [1] ambiguous rows of the last k-means pass
     int32_t* zero_dev = nullptr;          // 16 zero words on the device (stream-ordered resets of fb_host)
     int64_t counters[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+
+    // the tables fal_mgf_index left in the SLOT_MGF* slots for fal_mgf_parse (mgfparse.hip): the text they describe, the slot
+    // blocks they live in (fal_ctx_trim frees them: the pointers then differ) and the counts the host read back
+    struct MgfIndex {
+        const void* text = nullptr;
+        int64_t bytes = -1, spectra = 0, peaks = 0, cap_lines = 0, cap_spectra = 0;
+        const void* blocks[4] = {nullptr, nullptr, nullptr, nullptr};
+    } mgf;
 
     // caching device allocator for per-call objects (index arrays): blocks are recycled, never
     // returned to the driver before the context dies (hipMalloc / hipFree cost ~100 us each and

@@ -13,7 +13,8 @@
 //             64 threads = 56 KB per block); output bytes go straight to the array's slot, bounded by its declared capacity;
 //   convert : one wave per spectrum: byte swap (mzXML is big-endian), widen / narrow to f64 m/z and f32 intensity, de-interleave
 //             the mzXML pairs, stable sort by m/z (what np.lexsort does in falcon._raw_csr: NaN last, ties in input order) --
-//             already-sorted spectra (nearly all) are copied, the rest ranked within the wave.
+//             already-sorted spectra (nearly all) are copied, the rest ranked within the wave (peaksort.h, shared with the
+//             MGF reader).
 // A bad array sets bits of its spectrum's status word (FAL_PEAK_ST_*) and the spectrum's output range is zero-filled; nothing is
 // ever written outside an array's slot or a spectrum's range, and every loop is bounded by the input or the declared output.
 #include <math.h>
@@ -21,6 +22,7 @@
 #include "common.h"
 #include "inflate.h"
 #include "ivf.h"
+#include "peaksort.h"
 #include "util.h"
 
 namespace fal {
@@ -154,9 +156,6 @@ struct ArrayView {
     }
 };
 
-// np.sort order on float64: NaN after every number, NaNs equal among themselves, -0.0 == 0.0
-__device__ __forceinline__ bool key_less(double a, double b) { return a < b || (isnan(b) && !isnan(a)); }
-
 __global__ __launch_bounds__(256) void pd_convert_kernel(const int64_t* __restrict__ desc, int64_t n_arrays,
                                                          const int64_t* __restrict__ spec, int64_t n_spec,
                                                          const int32_t* __restrict__ arr_status, const uint8_t* __restrict__ dec,
@@ -198,26 +197,7 @@ __global__ __launch_bounds__(256) void pd_convert_kernel(const int64_t* __restri
             return v;
         };
         const ArrayView vm = view(ma, 0), vi = view(ia, 1);
-        bool unsorted = false;
-        for (int64_t j = 1 + lane; j < n; j += 64) unsorted |= key_less(vm.at(j), vm.at(j - 1));
-        if (__ballot(unsorted) == 0) {
-            for (int64_t j = lane; j < n; j += 64) {
-                out_mz[b + j] = vm.at(j);
-                out_it[b + j] = vi.at_f32(j);
-            }
-        } else {
-            // stable rank: peaks with a smaller key, plus equal keys earlier in the array
-            for (int64_t j = lane; j < n; j += 64) {
-                const double kj = vm.at(j);
-                int64_t r = 0;
-                for (int64_t k = 0; k < n; ++k) {
-                    const double kk = vm.at(k);
-                    r += key_less(kk, kj) || (k < j && !key_less(kj, kk));
-                }
-                out_mz[b + r] = kj;
-                out_it[b + r] = vi.at_f32(j);
-            }
-        }
+        wave_sort_peaks(n, lane, [&](int64_t j) { return vm.at(j); }, [&](int64_t j) { return vi.at_f32(j); }, out_mz + b, out_it + b);
         if (lane == 0) status[s] = 0;
     }
 }

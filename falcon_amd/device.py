@@ -322,6 +322,51 @@ class Context:
                                         self._p(status)), "fal_decode_peaks")
         return indptr, mz[:nnz], it[:nnz], status[:n]
 
+    def mgf_index(self, d_text):
+        """`fal_mgf_index` of MGF text on the device (uint8 tensor) -> (spectra, peaks, `_lib.MGF_FLAG_*` bits, lines).
+        Synchronises once.  The tables stay in the context for the `mgf_parse` of the same tensor."""
+        counts = (C.c_int64 * 4)()
+        check(self.lib.fal_mgf_index(self._h, self._p(d_text) if d_text.numel() else None, d_text.numel(), counts), "fal_mgf_index")
+        return tuple(int(c) for c in counts)
+
+    def mgf_parse(self, d_text, n: int, nnz: int):
+        """`fal_mgf_parse` behind `mgf_index` of the same tensor -> device tensors indptr i64[n+1], mz f64[nnz], intensity
+        f32[nnz], precursor_mz f64[n], charge i32[n], has_charge i32[n], retention_time f64[n], title i64[n, 2], span i64[n, 2],
+        status i32[n].  No sync."""
+        torch = _torch()
+        m = max(n, 1)
+        indptr, mz, it = self.empty((n + 1,), torch.int64), self.empty((max(nnz, 1),), torch.float64), self.empty((max(nnz, 1),), torch.float32)
+        pmz, rt = self.empty((m,), torch.float64), self.empty((m,), torch.float64)
+        charge, has_charge, status = (self.empty((m,), torch.int32) for _ in range(3))
+        title, span = self.empty((m, 2), torch.int64), self.empty((m, 2), torch.int64)
+        check(self.lib.fal_mgf_parse(self._h, self._p(d_text) if d_text.numel() else None, d_text.numel(), n, nnz, self._p(indptr),
+                                     self._p(mz), self._p(it), self._p(pmz), self._p(charge), self._p(has_charge), self._p(rt),
+                                     self._p(title), self._p(span), self._p(status)), "fal_mgf_parse")
+        return indptr, mz[:nnz], it[:nnz], pmz[:n], charge[:n], has_charge[:n], rt[:n], title[:n], span[:n], status[:n]
+
+    def parse_mgf(self, text):
+        """MGF text (bytes, uint8 array or uint8 device tensor) -> dict: `flags` (`_lib.MGF_FLAG_*`; non-zero: the text is the
+        host reader's and nothing else is set), else the raw CSR on the device -- `indptr` i64[n+1], `mz` f64, `intensity` f32,
+        sorted by m/z inside every spectrum as falcon._raw_csr -- and the per-spectrum host columns `precursor_mz` f64,
+        `charge` i32, `has_charge` bool, `retention_time` f64 (-1 when absent), `title` / `span` i64[n, 2] (byte ranges of the
+        title value and of the spectrum), `status` i32 (0, or `_lib.MGF_ST_HOST`: the host reader decides that spectrum; its
+        slot has the right size and placeholder values).  DESIGN.md "MGF on the device" states the grammar."""
+        torch = _torch()
+        if isinstance(text, torch.Tensor):
+            d_text = self.to_dev(text, torch.uint8)
+        else:
+            raw = np.frombuffer(text, np.uint8) if isinstance(text, (bytes, bytearray, memoryview)) else np.asarray(text, np.uint8)
+            if not raw.flags.writeable:
+                raw = raw.copy()                 # (immutable bytes: torch takes writable arrays only)
+            d_text = self.to_dev(raw) if len(raw) else self.empty((0,), torch.uint8)
+        n, nnz, flags, lines = self.mgf_index(d_text)
+        if flags:
+            return dict(flags=flags, lines=lines)
+        indptr, mz, it, *cols = self.mgf_parse(d_text, n, nnz)
+        pmz, charge, has_charge, rt, title, span, status = (c.cpu().numpy() for c in cols)
+        return dict(flags=0, lines=lines, indptr=indptr, mz=mz, intensity=it, precursor_mz=pmz, charge=charge,
+                    has_charge=has_charge.astype(bool), retention_time=rt, title=title, span=span, status=status)
+
     def consensus_spectra(self, mz, intensity, indptr, labels, medoids, fragment_tol: float, min_fraction: float = 0.25,
                           nnz_cap: Optional[int] = None):
         """`fal_consensus_spectra`: every cluster's members merged peak by peak (DESIGN.md "Consensus representatives").

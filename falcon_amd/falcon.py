@@ -28,7 +28,7 @@ import numpy as np
 from . import __version__
 from .cluster import cluster, spectrum
 from .config import config
-from .ms_io import ms_io
+from .ms_io import mgf_io, ms_io
 
 logger = logging.getLogger("falcon")
 
@@ -84,6 +84,7 @@ def _run(args) -> int:
     logger.info("falcon version %s", str(__version__))
     for line in _option_lines():
         logger.debug(line)
+    logger.debug("mgf_reader = %s", config.mgf_reader)       # (no output depends on it: not an option line of the CSV header)
     if config.distributed:
         return _run_distributed()
 
@@ -315,13 +316,7 @@ def _run_distributed() -> int:
 def _raw_csr(specs):
     """spectra read from one peak file -> raw CSR (peaks sorted by m/z inside every spectrum, which is
     what spectrum_utils does when the reference constructs an MsmsSpectrum)."""
-    sizes = np.array([len(s["mz"]) for s in specs], np.int64)
-    indptr = np.zeros(len(specs) + 1, np.int64)
-    np.cumsum(sizes, out=indptr[1:])
-    mz = np.concatenate([np.asarray(s["mz"], np.float64) for s in specs]) if len(specs) else np.zeros(0)
-    it = np.concatenate([np.asarray(s["intensity"], np.float32) for s in specs]) if len(specs) else np.zeros(0, np.float32)
-    order = np.lexsort((mz, np.repeat(np.arange(len(specs)), sizes)))
-    return mz[order], it[order], indptr
+    return mgf_io.raw_csr(specs)
 
 
 def _take_rows(indptr: np.ndarray, rows: np.ndarray):
@@ -388,11 +383,25 @@ def _prepare_chunk(chunk, fn, parts, min_mz, max_mz, ctx) -> int:
     return dropped + int((~valid).sum())
 
 
+def _prepare_mgf_chunk(chunk, fn, parts, min_mz, max_mz, ctx) -> int:
+    """one MgfChunk of the device reader: `fal_process_spectra` with the peaks left on the device -> charge partitions.
+    Spectra the host reader rejects are no spectra (they are skipped silently, as `get_spectra` skips them).
+    -> the low-quality count"""
+    if not len(chunk):
+        return 0
+    valid, oip, omz, oit = _process(ctx, chunk.mz, chunk.intensity, chunk.indptr, chunk.precursor_mz, chunk.precursor_charge,
+                                    min_mz, max_mz)
+    _partition(parts, fn, chunk.identifier, chunk.precursor_mz, chunk.retention_time.astype(np.float32), chunk.precursor_charge,
+               valid & ~chunk.dropped, oip, omz, oit)
+    return int((~valid & ~chunk.dropped).sum())
+
+
 def _prepare_spectra(spectra_dir: str, min_mz: float, max_mz: float, ctx) -> List[str]:
     """falcon.py:247-328: read every peak file, preprocess (`process_spectrum`, spectrum.py:73-169 -- here one
     `fal_process_spectra` call per file on the GPU), partition by precursor charge, one CSR `.npz` per charge.
     mzML / mzXML files go through their reader's chunks, `fal_decode_peaks` and `fal_process_spectra` with the peaks left on
-    the device (one chunk per call; a file whose payload is larger than one chunk is split between spectra)."""
+    the device (one chunk per call; a file whose payload is larger than one chunk is split between spectra).  MGF files go
+    through the device reader (`mgf_io.read_chunks`) unless `--mgf_reader host`: same spectra, same partitions."""
     filenames = [fn for pattern in config.input_filenames for fn in glob.glob(pattern)]
     logger.info("Read spectra from %d peak file(s)", len(filenames))
     parts: Dict[str, Dict[str, list]] = {}
@@ -403,6 +412,14 @@ def _prepare_spectra(spectra_dir: str, min_mz: float, max_mz: float, ctx) -> Lis
         if read_chunks is not None:                      # mzML / mzXML: binary arrays decoded on the device (fal_decode_peaks)
             for chunk in read_chunks(fn):
                 low_quality += _prepare_chunk(chunk, fn, parts, min_mz, max_mz, ctx)
+            continue
+        read_mgf = ms_io.device_reader(fn) if config.mgf_reader == "device" else None
+        if read_mgf is not None:                         # MGF: the text parsed on the device (fal_mgf_index / fal_mgf_parse)
+            n_host = n_read = 0
+            for chunk in read_mgf(fn, ctx):
+                low_quality += _prepare_mgf_chunk(chunk, fn, parts, min_mz, max_mz, ctx)
+                n_host, n_read = n_host + chunk.n_host, n_read + len(chunk)
+            logger.debug("MGF file %s: %d spectra parsed on the device, %d of them decided by the host reader", fn, n_read, n_host)
             continue
         specs = list(ms_io.get_spectra(fn))
         if not specs:

@@ -7,9 +7,12 @@ mgf_io.py:85-116 (TITLE, PEPMASS, CHARGE, RTINSECONDS, peaks).
 """
 from __future__ import annotations
 
+import io
 from typing import Dict, Iterable, Iterator
 
 import numpy as np
+
+DEFAULT_CHUNK_BYTES = 256 << 20      # text of one device call (the line table is sized by it: DESIGN.md "MGF on the device")
 
 
 def _parse_charge(txt: str):
@@ -65,6 +68,151 @@ def get_spectra(source) -> Iterator[Dict]:
     finally:
         if close:
             f.close()
+
+
+def raw_csr(specs):
+    """spectra of one peak file -> raw CSR (mz f64, intensity f32, indptr i64), peaks sorted by m/z inside every spectrum
+    (stable), which is what spectrum_utils does when the reference constructs an MsmsSpectrum"""
+    sizes = np.array([len(s["mz"]) for s in specs], np.int64)
+    indptr = np.zeros(len(specs) + 1, np.int64)
+    np.cumsum(sizes, out=indptr[1:])
+    mz = np.concatenate([np.asarray(s["mz"], np.float64) for s in specs]) if len(specs) else np.zeros(0)
+    it = np.concatenate([np.asarray(s["intensity"], np.float32) for s in specs]) if len(specs) else np.zeros(0, np.float32)
+    order = np.lexsort((mz, np.repeat(np.arange(len(specs)), sizes)))
+    return mz[order], it[order], indptr
+
+
+class MgfChunk:
+    """The spectra of one stretch of an MGF file, in file order: the raw CSR `indptr` / `mz` / `intensity` (device tensors from
+    the device reader, host arrays where the host reader read the stretch) and the host columns `identifier` (str),
+    `precursor_mz` f64, `precursor_charge` i32 (0: none), `retention_time` f64.  `dropped`: spectra the host reader rejects
+    (their rows stay, so that the CSR is the device's; they are no spectra and are not counted).  `n_host`: spectra the host
+    reader decided; `reader`: "device", or "host" for a stretch outside the device grammar."""
+
+    def __init__(self, indptr, mz, intensity, identifier, precursor_mz, precursor_charge, retention_time, dropped, n_host, reader):
+        self.indptr, self.mz, self.intensity = indptr, mz, intensity
+        self.identifier, self.precursor_mz, self.precursor_charge = identifier, precursor_mz, precursor_charge
+        self.retention_time, self.dropped, self.n_host, self.reader = retention_time, dropped, n_host, reader
+
+    def __len__(self):
+        return len(self.precursor_mz)
+
+
+def _host_chunk(specs) -> MgfChunk:
+    mz, it, indptr = raw_csr(specs)
+    return MgfChunk(indptr, mz, it, np.array([str(s["identifier"]) for s in specs], dtype=str),
+                    np.array([s["precursor_mz"] for s in specs], np.float64),
+                    np.array([int(s["precursor_charge"]) if s.get("precursor_charge") else 0 for s in specs], np.int32),
+                    np.array([s["retention_time"] for s in specs], np.float64), np.zeros(len(specs), bool), len(specs), "host")
+
+
+def _cut(buf, final: bool) -> int:
+    """bytes of `buf` up to and including the last complete line that strips to END IONS (the reader is outside a spectrum
+    behind it); 0: none; everything when `final`"""
+    if final:
+        return len(buf)
+    end = len(buf)
+    while True:
+        pos = buf.rfind(b"END IONS", 0, end)
+        if pos < 0:
+            return 0
+        stop = buf.find(b"\n", pos)
+        begin = buf.rfind(b"\n", 0, pos) + 1
+        if stop >= 0 and bytes(buf[begin:stop]).strip(b" \t\r") == b"END IONS":
+            return stop + 1
+        end = pos
+
+
+_TITLE_WIDTH = 256       # identifiers up to this length are gathered as one fixed-width array; longer ones one by one
+
+
+def _identifiers(text: np.ndarray, title: np.ndarray) -> np.ndarray:
+    """the title byte ranges of a chunk -> str array, without a Python loop over the spectra"""
+    n = len(title)
+    if n == 0:
+        return np.zeros(0, dtype=str)
+    lo, size = title[:, 0], title[:, 1] - title[:, 0]
+    w = int(min(max(size.max(initial=0), 1), _TITLE_WIDTH))
+    col = np.arange(w)
+    chars = text[np.minimum(lo[:, None] + col, max(len(text) - 1, 0))] if len(text) else np.zeros((n, w), np.uint8)
+    chars = np.where(col < size[:, None], chars, 0).astype(np.uint8)
+    out = np.ascontiguousarray(chars).view(f"S{w}").reshape(n)
+    long = np.flatnonzero(size > w)
+    if len(long):
+        out = out.astype(object)
+        for i in long:
+            out[i] = text[title[i, 0]:title[i, 1]].tobytes()
+        return np.array([b.decode("ascii") for b in out], dtype=str)
+    return np.char.decode(out, "ascii")
+
+
+def _device_chunk(ctx, buf, res) -> MgfChunk:
+    """one parsed stretch: identifiers from the title ranges, and every HOST spectrum read again by `get_spectra` from its own
+    byte range and patched into its slot"""
+    import torch
+    from .._lib import MGF_ST_HOST
+    text = np.frombuffer(buf, np.uint8)
+    n = len(res["status"])
+    ident = _identifiers(text, res["title"])
+    pmz, rt = res["precursor_mz"].copy(), res["retention_time"].copy()
+    charge = np.where(res["has_charge"], res["charge"], 0).astype(np.int32)
+    dropped = np.zeros(n, bool)
+    host = np.flatnonzero(res["status"] == MGF_ST_HOST)
+    if len(host):
+        ident = ident.astype(object)
+        indptr = res["indptr"].cpu().numpy()
+        pos, mzs, its = [], [], []
+        for i in host:
+            a, b = res["span"][i]
+            got = list(get_spectra(io.StringIO(bytes(buf[a:b]).decode("ascii"))))
+            size = int(indptr[i + 1] - indptr[i])
+            if len(got) != 1:                      # the host reader rejects it: no spectrum
+                dropped[i], ident[i], pmz[i], charge[i], rt[i] = True, "", 0.0, 0, -1.0
+                continue
+            s = got[0]
+            if len(s["mz"]) != size:
+                raise RuntimeError(f"MGF spectrum at bytes {a}-{b}: {size} peak lines on the device, {len(s['mz'])} on the host")
+            order = np.argsort(s["mz"], kind="stable")
+            pos.append(np.arange(indptr[i], indptr[i + 1]))
+            mzs.append(s["mz"][order])
+            its.append(s["intensity"][order])
+            ident[i], pmz[i], rt[i] = str(s["identifier"]), s["precursor_mz"], s["retention_time"]
+            charge[i] = int(s["precursor_charge"]) if s["precursor_charge"] else 0
+        ident = np.array(list(ident), dtype=str) if n else np.zeros(0, dtype=str)
+        if pos and sum(len(p) for p in pos):
+            at = torch.from_numpy(np.concatenate(pos)).to(res["mz"].device)
+            res["mz"][at] = torch.from_numpy(np.concatenate(mzs)).to(res["mz"].device)
+            res["intensity"][at] = torch.from_numpy(np.concatenate(its)).to(res["mz"].device)
+    return MgfChunk(res["indptr"], res["mz"], res["intensity"], ident, pmz, charge, rt, dropped, len(host), "device")
+
+
+def read_chunks(filename: str, ctx, max_bytes: int = DEFAULT_CHUNK_BYTES) -> Iterator[MgfChunk]:
+    """The device reader: the file as bytes, cut directly behind END IONS lines into stretches of about `max_bytes` (a
+    stretch grows when one spectrum is larger), each parsed by `ctx.parse_mgf`; spectra with status HOST are read again by
+    `get_spectra`.  A stretch outside the device grammar (a byte the device does not take) ends the device
+    path: the rest of the file is read by `get_spectra` through the same text layer as `open(filename)`, exceptions included.
+    The spectra of all chunks together are `get_spectra(filename)`'s."""
+    with open(filename, "rb") as f:
+        buf = bytearray()
+        final = False
+        while not final:
+            more = f.read(max(max_bytes - len(buf), max_bytes // 2, 1))
+            final = len(more) == 0
+            buf += more
+            if not final and len(buf) < max_bytes:
+                continue
+            cut = _cut(buf, final)
+            if cut == 0:
+                continue                           # one spectrum larger than the stretch: read on
+            head = buf[:cut]
+            res = ctx.parse_mgf(head)
+            if res["flags"]:
+                rest = io.BytesIO(bytes(buf) + f.read())
+                yield _host_chunk(list(get_spectra(io.TextIOWrapper(rest))))
+                return
+            if len(res["status"]):
+                yield _device_chunk(ctx, head, res)
+            del buf[:cut]
 
 
 def write_spectra(filename: str, spectra: Iterable[Dict]) -> None:

@@ -1,12 +1,14 @@
 """Peak-file front door: pick the reader / writer by file extension (the role of the reference's
 falcon/ms_io/ms_io.py:11-66).  MGF, mzML and mzXML are read (the extension test is case-insensitive); only MGF is written.
-The XML readers also hand their binary arrays, still encoded, to the device decoder (`read_chunks`)."""
+The XML readers also hand their binary arrays, still encoded, to the device decoder (`read_chunks`); MGF text is parsed on the
+device as a whole (`device_reader`), with `mgf_io.get_spectra` as the reader of record."""
 import os
 
 from . import mgf_io, mzml_io, mzxml_io
 
 _READERS = {".mgf": mgf_io.get_spectra, ".mzml": mzml_io.get_spectra, ".mzxml": mzxml_io.get_spectra}
 _CHUNK_READERS = {".mzml": mzml_io.read_chunks, ".mzxml": mzxml_io.read_chunks}
+_DEVICE_READERS = {".mgf": mgf_io.read_chunks}
 _WRITERS = {".mgf": mgf_io.write_spectra}
 
 
@@ -27,6 +29,11 @@ def get_spectra(filename: str):
 def chunk_reader(filename: str):
     """the `read_chunks(filename, max_bytes)` of an mzML / mzXML file (spectra + still-encoded arrays), None for other types"""
     return _CHUNK_READERS.get(_extension(filename))
+
+
+def device_reader(filename: str):
+    """the `read_chunks(filename, ctx, max_bytes)` of an MGF file, whose text is parsed on the device; None for other types"""
+    return _DEVICE_READERS.get(_extension(filename))
 
 
 def write_spectra(filename: str, spectra) -> None:

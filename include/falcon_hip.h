@@ -414,6 +414,32 @@ int fal_decode_peaks(fal_ctx* ctx, const uint8_t* payload, int64_t payload_bytes
                      int64_t inflate_bytes, int64_t nnz_cap, int64_t* out_indptr, double* out_mz,
                      float* out_intensity, int32_t* status_out);
 
+/* ---- MGF text -> raw peak CSR + per-spectrum columns (the device reader; DESIGN.md "MGF on the device" states the grammar;
+ *          falcon_amd/ms_io/mgf_io.get_spectra is the reader it mirrors and the one that decides whatever it leaves open).
+ * text: u8[n_bytes] on the device, 16-byte aligned, n_bytes < 2^31 - 1 (the caller cuts larger files behind an END IONS line).
+ * fal_mgf_index: line table, line classes and spectrum table of the text -> counts_out[4] (host) = {spectra, peak lines of
+ *          those spectra, FAL_MGF_FLAG_* bits, lines}.  One stream synchronisation.  A flag means "this text is the host
+ *          reader's": BYTES -- a byte outside \t, \n, 0x20-0x7E, \r directly followed by \n; LINES -- more lines than one per
+ *          4 bytes (the line table is sized before the count is known; the counts are then 0).
+ * fal_mgf_parse: fills the caller's outputs from the tables of the fal_mgf_index call before it, which stay in scratch
+ *          slots of the context (kept, not recomputed: the call checks text, n_bytes and n_spectra against that index and
+ *          fails with FAL_EINVAL when they are not its own, or when fal_ctx_trim ran in between).
+ * -> out_indptr i64[n + 1] (a spectrum's count = its peak lines, whether or not their values parse), out_mz f64 / out_intensity
+ *    f32 with room for nnz_cap >= the indexed peak count (sorted by m/z inside every spectrum, stable: the order of
+ *    np.lexsort((mz, row)), as fal_decode_peaks), precursor_mz f64[n], charge i32[n] + has_charge i32[n], retention_time f64[n]
+ *    (-1 when absent), title i64[n][2] / span i64[n][2]: byte ranges [from, to) of the title value and of the spectrum from its
+ *    BEGIN IONS line to the end of its END IONS line, status i32[n]: 0, or FAL_MGF_ST_HOST -- the host reader decides this
+ *    spectrum (a number or charge outside the fast forms, no TITLE / PEPMASS, an empty PEPMASS, a header or peak line longer
+ *    than 4096 bytes); its columns and values are then placeholders, its slot already has the right size.
+ * Malformed text never makes a call fail or write outside a slot.  No host work per line or per peak. ------------------ [dev] */
+#define FAL_MGF_FLAG_BYTES 1
+#define FAL_MGF_FLAG_LINES 2
+#define FAL_MGF_ST_HOST    1
+int fal_mgf_index(fal_ctx* ctx, const uint8_t* text, int64_t n_bytes, int64_t* counts_out);
+int fal_mgf_parse(fal_ctx* ctx, const uint8_t* text, int64_t n_bytes, int64_t n_spectra, int64_t nnz_cap,
+                  int64_t* out_indptr, double* out_mz, float* out_intensity, double* precursor_mz, int32_t* charge,
+                  int32_t* has_charge, double* retention_time, int64_t* title, int64_t* span, int32_t* status_out);
+
 /* ---- consensus representatives: the members of every cluster merged peak by peak (the reference exports medoids only,
  *          falcon.py:198-203; DESIGN.md "Consensus representatives" states the definition).
  * mz / intensity f32, indptr i64[n+1]: the preprocessed peaks in dataset-row order (fewer than 2^31 in all); labels i32[n]:
