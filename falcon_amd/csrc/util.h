@@ -4,7 +4,14 @@
 #include "peakmatch.h"
 
 namespace fal {
-// out[0..n) = exclusive prefix of in (int32 flags/counts), out[n] = total (all on device)
+// out[0..n) = exclusive prefix of in (int32 flags/counts), out[n] = total (all on device).  Sums are int64 throughout.
+// Three forms (sortutil.hip device_scan_t), by nb = ceil(n / 1024) blocks:
+//   nb <= 1,025 (n <= 1,049,600)   block sums + fused apply: every block adds up the sums in front of it in ONE round of
+//                                  its front-sum loop (1,024 threads, block index <= 1,024); the last block writes the total
+//   nb <= 4,096 (n <= 4,194,304)   the same two launches, the front-sum loop goes round up to four times
+//   nb >  4,096 (n >= 4,194,305)   block sums -> exclusive_scan_kernel over them (ivf.hip, one workgroup) -> scan_apply_kernel
+//                                  -> a device-to-device copy of the total
+// tests/test_gpu_plumbing.py has a case on each side of both switches, for both input types.
 int device_scan_i32(fal_ctx* ctx, const int32_t* in, int64_t n, int64_t* out, int scratch_slot);
 int device_scan_i64(fal_ctx* ctx, const int64_t* in, int64_t n, int64_t* out, int scratch_slot);   // same, int64 input
 // stable LSD radix sort of (uint32 key, int32 value) pairs on bits [0, end_bit)

@@ -213,6 +213,9 @@ def bucket_splits(precursor_mzs: np.ndarray, tol: float, mode: str, batch_size: 
       the two differ only where a gap-free run of >= batch_size spectra crosses a window boundary)."""
     mz = np.asarray(precursor_mzs, f32)
     n = len(mz)
+    if n == 0:
+        # no spectrum, no rule to apply: the reference's [0, 0] (cluster.py:188 + 208), which the set below would fold to [0]
+        return get_precursor_mz_splits(mz, tol, mode, batch_size)
     if mz_interval and mz_interval > 0 and n > 1:
         # [build rule] fixed precursor windows: the reference's rule (+ the chunked last block) runs INSIDE every window, so a
         # window's buckets depend on its own spectra only (the unit the multi-GPU job deals out, SURVEY 8e)
@@ -818,7 +821,7 @@ def generate_clusters(mz, intensity, indptr, precursor_mz, rt, *, eps=0.1, precu
         C, asg, perm, off = ivf_build(Xb, nl, kmeans_iters)
         sim[a:b], idx[a:b] = ivf_search(Xb, C, asg, perm, off, n_probe, n_neighbors_ann, base=a)
 
-    buckets = list(zip(splits[:-1], splits[1:]))
+    buckets = [ab for ab in zip(splits[:-1], splits[1:]) if ab[1] > ab[0]]     # (an empty dataset: [0, 0], no bucket)
     if n_jobs > 1 and _klib() is not None:
         # buckets on a thread pool, like the reference's joblib threading backend over its blocks (cluster.py:115-136);
         # the C helper then runs one thread per call (ctypes releases the GIL)
