@@ -13,8 +13,11 @@
 //   3. clusters of one row become noise (-1: the reference's _postprocess_cluster drops groups < 2, cluster.py:441-454),
 //      the others are numbered by their lowest row -- the interface of the DBSCAN stage (a9), so a10..a12 follow
 //      unchanged.
-// fastcluster is not available and scipy's tie order is not specified: PARITY UNPINNED for exact ties (the partition is
-// identical whenever merge heights are distinct; tests/test_gpu_linkage.py against scipy.cluster.hierarchy).
+// fastcluster is not available and scipy's tie order is not specified: PARITY with them stays UNPINNED for exact ties (the
+// partition is identical whenever merge heights are distinct; tests/test_gpu_linkage.py against scipy.cluster.hierarchy).
+// The order this file states for itself -- smallest height, ties -> lowest (a, b) in the group's ascending-row numbering,
+// float64 updates -- IS pinned: tests/linkage_cases.py restates it in numpy, tests/test_gpu_linkage_ties.py holds both
+// agglomeration kernels to it on inputs made of ties, label for label.
 #include <math.h>
 #include <algorithm>
 #include "common.h"
@@ -256,6 +259,12 @@ __global__ __launch_bounds__(64) void lk_agglomerate_kernel(const int32_t* __res
 // minimum with the (value, a, b) tie order is a reduction over m cached entries; after a merge only the rows whose cached
 // partner was one of the merged pair are searched again (a wave per row), the others are updated in place (a new value can
 // only tie the cached one: complete and average linkage are reducible, d(a + b, c) >= min(d(a, c), d(b, c))).
+// In exact arithmetic the in-place branch below replaces nothing: before the merge D[c][ba] > nnv[c] or nni[c] < ba, the
+// same for bb, and a reducible update cannot go below the smaller of the two (the sequential port in tests/linkage_cases.py
+// counts zero on heights that are binary fractions or few float32 values).  In float64 it is LIVE: the average of two equal
+// heights, (sa * x + sb * x) / (sa + sb), rounds one ulp below x for some sizes (x = 0.04097352393619469, sa = 25, sb = 37),
+// which is below the cached nnv[c] = x -- exact mode's cosines and float32 distances after a few unequal means give such
+// heights (tests/test_linkage_cpu.py keeps inputs where it fires).  The cache's (value, lowest b) invariant depends on it.
 __global__ __launch_bounds__(1024) void lk_agglomerate_big_kernel(const int32_t* __restrict__ nb_idx, const float* __restrict__ nb_dist,
                                                                   int64_t n, int k, const int64_t* __restrict__ csr_ptr,
                                                                   const int32_t* __restrict__ csr_idx, const double* __restrict__ csr_dist,

@@ -540,7 +540,8 @@ def linkage_clusters(nb_idx: np.ndarray, nb_dist: np.ndarray, t: float, method: 
     """Hierarchical clustering of the sparse neighbour graph cut at distance t: the snapshot's
     `fcluster(fastcluster.linkage(pdist, linkage), distance_threshold, "distance")` (cluster.py:283-290) with
     "missing pair = distance 1" (cluster.py:621-626); scipy's `linkage` stands in for fastcluster (absent; same
-    dendrogram up to the order of equal heights -- PARITY UNPINNED for exact ties).  Only the connected components of
+    dendrogram up to the order of equal heights -- PARITY with either UNPINNED for exact ties; the tie order of the
+    library's own kernels, lowest (a, b), is pinned by tests/linkage_cases.py, not here).  Only the connected components of
     the edges with d <= t can merge below t < 1, so the dense matrix is built per component.
     d(i, j) = the smaller of the stored directions.  -> labels int32[n]: clusters numbered by lowest row, groups of
     one row = -1 (what _postprocess_cluster makes of them, cluster.py:441-454) -- the contract of `dbscan_components`."""

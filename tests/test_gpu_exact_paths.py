@@ -16,6 +16,7 @@ import numpy as np
 import pytest
 
 from oracle import falcon_oracle as fo
+from tests import linkage_cases as lc
 from tests import peakmatch_cases as pc
 from tests import test_gpu_exact as base
 from tests.test_gpu_exact import _block_matrix, _expected_csr, _gpu_clusters, _peaks, _restate, _scipy_labels, _sorted, _to_np
@@ -410,10 +411,11 @@ def _three_rows(n_side):
 
 def _hand_csr(ctx, D):
     import torch
-    ptr = torch.tensor([0, 1, 3, 4], dtype=torch.int64, device=ctx.tdev)
-    idx = torch.tensor([1, 0, 2, 1], dtype=torch.int32, device=ctx.tdev)
-    dist = torch.tensor([D[0, 1], D[1, 0], D[1, 2], D[2, 1]], dtype=torch.float64, device=ctx.tdev)
-    return ptr, idx, dist
+    assert D[0, 1] == D[1, 0] and D[1, 2] == D[2, 1]
+    ptr, idx, dist = lc.pairs_to_csr(3, [0, 1], [1, 2], [D[0, 1], D[1, 2]])    # the pairs (0, 1) and (1, 2), not (0, 2)
+    assert ptr.tolist() == [0, 1, 3, 4] and idx.tolist() == [1, 0, 2, 1]
+    assert dist.tolist() == [D[0, 1], D[1, 0], D[1, 2], D[2, 1]]
+    return tuple(torch.from_numpy(x).to(ctx.tdev) for x in (ptr, idx, dist))
 
 
 def test_component_of_exactly_32_through_every_consumer(ctx):
