@@ -15,8 +15,10 @@ LIB_PATH = os.path.join(_HERE, "libfalcon_hip.so")
 FAL_DTYPE_F32, FAL_DTYPE_F16, FAL_DTYPE_SPLIT16, FAL_OUT_F32_F16, FAL_OUT_F16_IMAGE = 0, 1, 2, 3, 4
 # fal_decode_peaks: array flags and per-spectrum status bits (include/falcon_hip.h)
 PEAK_F64, PEAK_ZLIB, PEAK_BIG_ENDIAN, PEAK_PAIRS = 1, 2, 4, 8
+PEAK_NUMPRESS_LINEAR, PEAK_NUMPRESS_PIC, PEAK_NUMPRESS_SLOF, PEAK_NUMPRESS_MASK = 16, 32, 48, 48      # a 2-bit codec field
 PEAK_STATUS = {1: "bad descriptor", 2: "bad base64", 4: "bad zlib header", 8: "bad deflate stream", 16: "more values than declared",
-               32: "fewer values than declared", 64: "Adler-32 mismatch", 128: "decode buffer too small"}
+               32: "fewer values than declared", 64: "Adler-32 mismatch", 128: "decode buffer too small",
+               256: "bad MS-Numpress stream"}
 # fal_mgf_index / fal_mgf_parse: flags of a text the host reader has to read, and the per-spectrum status (include/falcon_hip.h)
 MGF_FLAG_BYTES, MGF_FLAG_LINES, MGF_ST_HOST = 1, 2, 1
 # fal_consensus_spectra: per-cluster status bits, and the pooled peaks one workgroup sorts in LDS (include/falcon_hip.h)

@@ -221,9 +221,11 @@ static __host__ __device__ void inflate_stored(Inflater& z) {
     z.in_pos += len;
 }
 
-// one zlib stream (in[0 .. in_len)) into out[0 .. out_cap): 0, or FAL_PEAK_ST_* bits.  Host-callable as well: tests/test_inflate_cpu.py
-// builds this header with the host compiler and checks it against zlib (good, corrupted and truncated streams).
-static __host__ __device__ int inflate_stream(const uint8_t* in, int64_t in_len, uint8_t* out, int64_t out_cap, HuffLds& h) {
+// one zlib stream (in[0 .. in_len)) into out[0 .. out_cap): 0, or FAL_PEAK_ST_* bits; *out_len = the bytes written.  `exact`:
+// an output shorter than out_cap is FAL_PEAK_ST_SHORT; otherwise out_cap is an upper bound only (a stream whose inflated size
+// is not declared: MS-Numpress) and the caller takes the length.
+static __host__ __device__ int inflate_stream_upto(const uint8_t* in, int64_t in_len, uint8_t* out, int64_t out_cap, bool exact,
+                                                   int64_t* out_len, HuffLds& h) {
     Inflater z;
     z.in = in;
     z.in_len = in_len;
@@ -237,6 +239,7 @@ static __host__ __device__ int inflate_stream(const uint8_t* in, int64_t in_len,
     z.s2 = 0;
     z.err = 0;
     // RFC 1950 header: CM = 8, CINFO <= 7, FCHECK, no preset dictionary
+    *out_len = 0;
     if (in_len < 2) return FAL_PEAK_ST_HEADER;
     const uint32_t cmf = in[0], flg = in[1];
     if ((cmf & 15) != 8 || (cmf >> 4) > 7 || ((cmf << 8) | flg) % 31 != 0 || (flg & 0x20)) return FAL_PEAK_ST_HEADER;
@@ -251,7 +254,8 @@ static __host__ __device__ int inflate_stream(const uint8_t* in, int64_t in_len,
         else if (type == 2) inflate_dynamic(z, h);
         else z.err |= FAL_PEAK_ST_CODE;
     }
-    if (!z.err && z.out_pos != z.out_cap) z.err |= FAL_PEAK_ST_SHORT;
+    *out_len = z.out_pos;
+    if (!z.err && exact && z.out_pos != z.out_cap) z.err |= FAL_PEAK_ST_SHORT;
     if (!z.err) {
         const int64_t p = z.in_pos;                                     // the bit buffer holds < 8 bits: the trailer is byte aligned
         if (in_len - p < 4) return FAL_PEAK_ST_ADLER;
@@ -259,6 +263,13 @@ static __host__ __device__ int inflate_stream(const uint8_t* in, int64_t in_len,
         if (want != ((z.s2 << 16) | z.s1)) z.err |= FAL_PEAK_ST_ADLER;
     }
     return z.err;
+}
+
+// the declared-size form: the stream must fill out[0 .. out_cap) exactly.  Host-callable as well: tests/test_inflate_cpu.py
+// builds this header with the host compiler and checks it against zlib (good, corrupted and truncated streams).
+static __host__ __device__ int inflate_stream(const uint8_t* in, int64_t in_len, uint8_t* out, int64_t out_cap, HuffLds& h) {
+    int64_t n;
+    return inflate_stream_upto(in, in_len, out, out_cap, true, &n, h);
 }
 
 }  // namespace fal

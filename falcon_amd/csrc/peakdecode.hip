@@ -2,8 +2,10 @@
 // peak CSR that fal_process_spectra takes (indptr i64, m/z f64, intensity f32, peaks sorted by m/z inside every spectrum).
 //
 // The host reader keeps the XML structure; every binary array arrives as a range of one contiguous payload buffer plus a
-// descriptor row (offset, base64 length, declared value count, flags).  Five launches, no host round trip:
-//   arrays  : one thread per array: validate the row, inflate capacity (declared count x element size, 8-byte rounded);
+// descriptor row (offset, base64 length, declared value count, flags).  Six launches, no host round trip:
+//   arrays  : one thread per array: validate the row, its slot of the inflate buffer (inflated capacity -- declared count x
+//             element size, or the longest numpress stream of that count -- plus the float64 values of a numpress array, each
+//             8-byte rounded);
 //   counts  : one thread per spectrum: its peak count (the declared count of its m/z array); two device scans give the output
 //             indptr and the per-array offsets of the inflate buffer;
 //   base64  : one wave per array, 4 characters -> 3 bytes per lane; the decoded bytes land at the array's own payload offset in
@@ -11,7 +13,11 @@
 //   inflate : one thread per zlib array (RFC 1950/1951: stored, fixed- and dynamic-Huffman blocks, overlapping copies, header and
 //             Adler-32 checks).  Canonical-code tables of the thread in LDS (puff-style count / symbol form, 896 B per thread:
 //             64 threads = 56 KB per block); output bytes go straight to the array's slot, bounded by its declared capacity;
-//   convert : one wave per spectrum: byte swap (mzXML is big-endian), widen / narrow to f64 m/z and f32 intensity, de-interleave
+//   numpress: MS-Numpress arrays (numpress.h) -> float64 in the array's slot, behind its inflated bytes.  Every wave takes 64
+//             arrays: linear and pic are sequential per stream, one lane each; slof values are independent, so the wave
+//             then walks its slof arrays together, one value per lane;
+//   convert : one wave per spectrum: byte swap (mzXML is big-endian), widen / narrow to f64 m/z and f32 intensity (a numpress
+//             array is little-endian f64 in the scratch by now), de-interleave
 //             the mzXML pairs, stable sort by m/z (what np.lexsort does in falcon._raw_csr: NaN last, ties in input order) --
 //             already-sorted spectra (nearly all) are copied, the rest ranked within the wave (peaksort.h, shared with the
 //             MGF reader).
@@ -22,6 +28,7 @@
 #include "common.h"
 #include "inflate.h"
 #include "ivf.h"
+#include "numpress.h"
 #include "peaksort.h"
 #include "util.h"
 
@@ -36,6 +43,18 @@ __host__ __device__ __forceinline__ int64_t array_bytes(const int64_t* d) {     
     return d[2] * elem_bytes(d[3]) * ((d[3] & FAL_PEAK_PAIRS) ? 2 : 1);
 }
 
+__host__ __device__ __forceinline__ int64_t codec_of(int64_t flags) { return flags & FAL_PEAK_NUMPRESS_MASK; }
+
+// bytes a zlib array may inflate to: the declared size, or (its size is not declared) the longest numpress stream of the count
+__host__ __device__ __forceinline__ int64_t inflate_cap(const int64_t* d) {
+    return codec_of(d[3]) ? numpress_max_bytes(codec_of(d[3]), d[2]) : array_bytes(d);
+}
+
+__host__ __device__ __forceinline__ int64_t round8(int64_t v) { return (v + 7) & ~(int64_t)7; }
+
+// a numpress array's float64 values sit behind its inflated bytes
+__host__ __device__ __forceinline__ int64_t values_offset(const int64_t* d) { return (d[3] & FAL_PEAK_ZLIB) ? round8(inflate_cap(d)) : 0; }
+
 // ---- launch 1: descriptors ------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void pd_arrays_kernel(const int64_t* __restrict__ desc, int64_t n_arrays, int64_t payload_bytes,
                                                         int32_t* __restrict__ arr_status, int64_t* __restrict__ cap) {
@@ -44,9 +63,10 @@ __global__ __launch_bounds__(256) void pd_arrays_kernel(const int64_t* __restric
         const int64_t off = d[0], len = d[1], cnt = d[2], flags = d[3];
         const bool ok = off >= 0 && len >= 0 && (off & 7) == 0 && (len & 3) == 0 && off <= payload_bytes &&
                         len <= payload_bytes - off && cnt >= 0 && cnt < (int64_t(1) << 40) &&
-                        (flags & ~(int64_t)(FAL_PEAK_F64 | FAL_PEAK_ZLIB | FAL_PEAK_BIG_ENDIAN | FAL_PEAK_PAIRS)) == 0;
+                        (flags & ~(int64_t)(FAL_PEAK_F64 | FAL_PEAK_ZLIB | FAL_PEAK_BIG_ENDIAN | FAL_PEAK_PAIRS | FAL_PEAK_NUMPRESS_MASK)) == 0 &&
+                        !(codec_of(flags) && (flags & (FAL_PEAK_F64 | FAL_PEAK_BIG_ENDIAN | FAL_PEAK_PAIRS)));
         arr_status[a] = ok ? 0 : FAL_PEAK_ST_DESC;
-        cap[a] = ok && (flags & FAL_PEAK_ZLIB) ? (array_bytes(d) + 7) & ~(int64_t)7 : 0;
+        cap[a] = ok ? values_offset(d) + (codec_of(flags) ? cnt * 8 : 0) : 0;
     }
 }
 
@@ -105,7 +125,7 @@ __global__ __launch_bounds__(256) void pd_base64_kernel(const uint8_t* __restric
             const int64_t n = groups * 3 - (groups ? total_pad : 0);
             dec_len[a] = n;
             int st = any_bad ? FAL_PEAK_ST_BASE64 : 0;
-            if (!any_bad && !(d[3] & FAL_PEAK_ZLIB)) {
+            if (!any_bad && !(d[3] & (FAL_PEAK_ZLIB | FAL_PEAK_NUMPRESS_MASK))) {      // else the stream's decoder counts
                 const int64_t want = array_bytes(d);
                 st = n > want ? FAL_PEAK_ST_OVERFLOW : n < want ? FAL_PEAK_ST_SHORT : 0;
             }
@@ -116,7 +136,7 @@ __global__ __launch_bounds__(256) void pd_base64_kernel(const uint8_t* __restric
 
 // ---- launch 4: inflate (the inflater itself: inflate.h) -------------------------------------------------------------------
 __global__ __launch_bounds__(kInflateBlock) void pd_inflate_kernel(const int64_t* __restrict__ desc, int64_t n_arrays,
-                                                                   const uint8_t* __restrict__ dec, const int64_t* __restrict__ dec_len,
+                                                                   const uint8_t* __restrict__ dec, int64_t* __restrict__ dec_len,
                                                                    const int64_t* __restrict__ raw_off, int64_t inflate_bytes,
                                                                    uint8_t* __restrict__ raw, int32_t* __restrict__ arr_status) {
     __shared__ HuffLds tables[kInflateBlock];
@@ -124,13 +144,80 @@ __global__ __launch_bounds__(kInflateBlock) void pd_inflate_kernel(const int64_t
     for (int64_t a = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; a < n_arrays; a += (int64_t)gridDim.x * blockDim.x) {
         const int64_t* d = desc + 4 * a;
         if (!(d[3] & FAL_PEAK_ZLIB) || arr_status[a]) continue;
-        const int64_t cap = array_bytes(d);
-        arr_status[a] = raw_off[a] + cap > inflate_bytes ? FAL_PEAK_ST_CAPACITY
-                                                         : inflate_stream(dec + d[0], dec_len[a], raw + raw_off[a], cap, h);
+        const int64_t cap = inflate_cap(d);
+        if (raw_off[a] + cap > inflate_bytes) {
+            arr_status[a] = FAL_PEAK_ST_CAPACITY;
+            continue;
+        }
+        int64_t got;                                                    // a numpress stream may be shorter than its bound
+        arr_status[a] = inflate_stream_upto(dec + d[0], dec_len[a], raw + raw_off[a], cap, !codec_of(d[3]), &got, h);
+        dec_len[a] = got;                                               // the stream the numpress stage reads
     }
 }
 
-// ---- launch 5: convert + sort ---------------------------------------------------------------------------------------------
+// ---- launch 5: MS-Numpress (the codecs themselves: numpress.h) ----------------------------------------------------------------
+struct NumpressJob {
+    const uint8_t* in;               // the stream: the array's inflated bytes, or its base64-decoded ones
+    int64_t len, count;
+    double* out;                     // count float64 values of the array's slot
+};
+
+// the array's stream and output; false (with *st set) when the slot ends behind the scratch
+__device__ __forceinline__ bool numpress_job(const int64_t* d, int64_t a, const uint8_t* dec, const int64_t* dec_len,
+                                             const int64_t* raw_off, int64_t inflate_bytes, uint8_t* raw, NumpressJob* j, int* st) {
+    const int64_t voff = raw_off[a] + values_offset(d);
+    if (voff + d[2] * 8 > inflate_bytes) {
+        *st = FAL_PEAK_ST_CAPACITY;
+        return false;
+    }
+    j->in = (d[3] & FAL_PEAK_ZLIB) ? raw + raw_off[a] : dec + d[0];
+    j->len = dec_len[a];
+    j->count = d[2];
+    j->out = reinterpret_cast<double*>(raw + voff);
+    return true;
+}
+
+__global__ __launch_bounds__(256) void numpress_decode_kernel(const int64_t* __restrict__ desc, int64_t n_arrays,
+                                                              const uint8_t* __restrict__ dec, const int64_t* __restrict__ dec_len,
+                                                              const int64_t* __restrict__ raw_off, int64_t inflate_bytes,
+                                                              uint8_t* raw, int32_t* __restrict__ arr_status) {
+    const int lane = threadIdx.x & 63;
+    const int64_t waves = (int64_t)gridDim.x * (blockDim.x >> 6);
+    for (int64_t g = blockIdx.x * (int64_t)(blockDim.x >> 6) + (threadIdx.x >> 6); g * 64 < n_arrays; g += waves) {
+        const int64_t a = g * 64 + lane;
+        const int64_t codec = a < n_arrays && !arr_status[a] ? codec_of(desc[4 * a + 3]) : 0;
+        if (codec == FAL_PEAK_NUMPRESS_LINEAR || codec == FAL_PEAK_NUMPRESS_PIC) {      // sequential streams: a lane each
+            NumpressJob j;
+            int st = 0;
+            if (numpress_job(desc + 4 * a, a, dec, dec_len, raw_off, inflate_bytes, raw, &j, &st)) {
+                int64_t n;
+                st = codec == FAL_PEAK_NUMPRESS_PIC ? numpress_pic(j.in, j.len, j.out, j.count, &n)
+                                                    : numpress_linear(j.in, j.len, j.out, j.count, &n);
+                if (!st && n < j.count) st = FAL_PEAK_ST_SHORT;
+            }
+            arr_status[a] = st;
+        }
+        unsigned long long todo = __ballot(codec == FAL_PEAK_NUMPRESS_SLOF);            // independent values: the wave per array
+        while (todo) {
+            const int64_t b = g * 64 + (__ffsll(todo) - 1);
+            todo &= todo - 1;
+            NumpressJob j;
+            int st = 0;
+            if (numpress_job(desc + 4 * b, b, dec, dec_len, raw_off, inflate_bytes, raw, &j, &st)) {
+                double fp;
+                int64_t n;
+                st = numpress_slof_header(j.in, j.len, &fp, &n);
+                if (!st) {
+                    for (int64_t i = lane; i < std::min(n, j.count); i += 64) j.out[i] = numpress_slof_value(j.in, fp, i);
+                    st = n > j.count ? FAL_PEAK_ST_OVERFLOW : n < j.count ? FAL_PEAK_ST_SHORT : 0;
+                }
+            }
+            if (lane == 0) arr_status[b] = st;
+        }
+    }
+}
+
+// ---- launch 6: convert + sort ---------------------------------------------------------------------------------------------
 __device__ __forceinline__ double load_value(const uint8_t* base, int64_t i, bool f64, bool be) {
     if (f64) {
         uint64_t u = reinterpret_cast<const uint64_t*>(base)[i];
@@ -189,8 +276,8 @@ __global__ __launch_bounds__(256) void pd_convert_kernel(const int64_t* __restri
         auto view = [&](int64_t a, int shift) {
             const int64_t* d = desc + 4 * a;
             ArrayView v;
-            v.base = (d[3] & FAL_PEAK_ZLIB) ? raw + raw_off[a] : dec + d[0];
-            v.f64 = (d[3] & FAL_PEAK_F64) != 0;
+            v.base = codec_of(d[3]) ? raw + raw_off[a] + values_offset(d) : (d[3] & FAL_PEAK_ZLIB) ? raw + raw_off[a] : dec + d[0];
+            v.f64 = (d[3] & FAL_PEAK_F64) != 0 || codec_of(d[3]);
             v.be = (d[3] & FAL_PEAK_BIG_ENDIAN) != 0;
             v.stride = (d[3] & FAL_PEAK_PAIRS) ? 2 : 1;
             v.shift = (d[3] & FAL_PEAK_PAIRS) ? shift : 0;
@@ -253,6 +340,9 @@ extern "C" int fal_decode_peaks(fal_ctx* ctx, const uint8_t* payload, int64_t pa
         FAL_CHECK_HIP(hipGetLastError());
         hipLaunchKernelGGL(pd_inflate_kernel, dim3(grid_for(n_arrays, kInflateBlock)), dim3(kInflateBlock), 0, ctx->stream, arrays,
                            n_arrays, dec, dec_len, raw_off, inflate_bytes, raw, arr_status);
+        FAL_CHECK_HIP(hipGetLastError());
+        hipLaunchKernelGGL(numpress_decode_kernel, dim3(grid_for(n_arrays, 256)), dim3(256), 0, ctx->stream, arrays, n_arrays, dec,
+                           dec_len, raw_off, inflate_bytes, raw, arr_status);
         FAL_CHECK_HIP(hipGetLastError());
     }
     hipLaunchKernelGGL(pd_convert_kernel, dim3(grid_for(n_spectra, 4)), dim3(256), 0, ctx->stream, arrays, n_arrays, spectra, n_spectra,

@@ -295,7 +295,8 @@ class Context:
     def decode_peaks(self, payload, arrays, spectra):
         """`fal_decode_peaks`: the binary arrays of mzML / mzXML spectra -> the raw CSR `process_spectra` takes, on the device.
         payload u8[] (base64 text, arrays at 8-byte aligned offsets), arrays i64[n_arrays, 4] (offset, base64 length, declared
-        count, `_lib.PEAK_*` flags), spectra i64[n, 2] (m/z array, intensity array).
+        count, `_lib.PEAK_*` flags: float width, zlib, byte order, pairs, or an MS-Numpress codec), spectra i64[n, 2] (m/z array,
+        intensity array).
         -> indptr i64[n+1], mz f64[nnz], intensity f32[nnz] (sorted by m/z per spectrum, as falcon._raw_csr), status i32[n]
         (0 = decoded; else `_lib.PEAK_STATUS` bits, and that spectrum's peaks are zeros).  Device tensors; no sync."""
         torch = _torch()
@@ -305,8 +306,15 @@ class Context:
         n = len(spectra)
         # sizes from the host copy of the tables (the kernels check every slot against them)
         flags, counts = arrays[:, 3], arrays[:, 2]
-        nbytes = np.maximum(counts, 0) * np.where(flags & _lib.PEAK_F64, 8, 4) * np.where(flags & _lib.PEAK_PAIRS, 2, 1)
-        inflate_bytes = int(((nbytes + 7) // 8 * 8)[(flags & _lib.PEAK_ZLIB) != 0].sum())
+        # inflate_bytes (falcon_hip.h): per array, 8-byte rounded, the inflated capacity of a zlib array -- the declared size,
+        # or the longest MS-Numpress stream of the count -- plus count x 8 for the float64 values of a numpress array
+        cnt = np.maximum(counts, 0)
+        codec = flags & _lib.PEAK_NUMPRESS_MASK
+        nbytes = cnt * np.where(flags & _lib.PEAK_F64, 8, 4) * np.where(flags & _lib.PEAK_PAIRS, 2, 1)
+        linear = np.where(cnt == 0, 8, np.where(cnt == 1, 12, 16 + (9 * (cnt - 2) + 1) // 2))
+        nbytes = np.select([codec == _lib.PEAK_NUMPRESS_LINEAR, codec == _lib.PEAK_NUMPRESS_PIC,
+                            codec == _lib.PEAK_NUMPRESS_SLOF], [linear, (9 * cnt + 1) // 2, 8 + 2 * cnt], nbytes)
+        inflate_bytes = int(((nbytes + 7) // 8 * 8)[(flags & _lib.PEAK_ZLIB) != 0].sum() + (cnt * 8)[codec != 0].sum())
         ma = spectra[:, 0]
         ok = (ma >= 0) & (ma < len(arrays))
         nnz = int(np.maximum(counts[ma[ok]], 0).sum()) if len(arrays) else 0

@@ -5,8 +5,14 @@ Fields as the reference reads them (falcon/ms_io/mzml_io.py:14-80, pyteomics und
 the first MS:1000633, else None; retention time = the first scan's MS:1000016 value as written (its unit is not applied, as the
 reference passes pyteomics' value through; PARITY UNPINNED), -1 when absent.  Parameters may come through
 `referenceableParamGroupRef` at every level.  A spectrum that lacks a required field is skipped silently, as the reference's
-`except (ValueError, KeyError)` does; one with arrays this build does not decode (MS-Numpress, other compressions) is skipped
-and counted in `PeakChunk.skipped`.  A parse error part-way logs a warning and keeps the spectra read before it.
+`except (ValueError, KeyError)` does; one with arrays this build does not decode (the MS-Numpress truncation terms
+MS:1003089-91, contradictory compression terms) is skipped and counted in `PeakChunk.skipped`.  A parse error part-way logs a
+warning and keeps the spectra read before it.
+
+MS-Numpress arrays are read: linear, pic and slof (MS:1002312-4), and the same followed by zlib (MS:1002746-8); the float-width
+term of such an array is ignored, its values are float64 (`numpress.py`, DESIGN.md "MS-Numpress"; parity with outside encoders
+UNPINNED).  A numpress term next to a second compression term (MS:1000574 zlib or MS:1000576 none) is contradictory and the
+spectrum is skipped under the codec's name -- so older files that mark numpress + zlib with two separate terms stay skipped.
 
 Elements are dropped once used, so memory follows the chunk's payload, not the file.  The binary arrays stay base64 text here:
 `PeakChunk` carries them to the device decoder (`fal_decode_peaks`) or decodes them on the host (`get_spectra`).
@@ -17,7 +23,7 @@ import logging
 import xml.etree.ElementTree as ET
 from typing import Dict, Iterator
 
-from .._lib import PEAK_F64, PEAK_ZLIB
+from .._lib import PEAK_F64, PEAK_NUMPRESS_LINEAR, PEAK_NUMPRESS_PIC, PEAK_NUMPRESS_SLOF, PEAK_ZLIB
 from .peak_payload import DEFAULT_CHUNK_BYTES, PeakChunk
 
 logger = logging.getLogger("falcon")
@@ -27,8 +33,14 @@ MZ_ARRAY, INTENSITY_ARRAY = "MS:1000514", "MS:1000515"
 FLOAT32, FLOAT64 = "MS:1000521", "MS:1000523"
 NO_COMPRESSION, ZLIB = "MS:1000576", "MS:1000574"
 NUMPRESS = {"MS:1002312": "MS-Numpress linear", "MS:1002313": "MS-Numpress pic", "MS:1002314": "MS-Numpress slof"}
-# every other compression term of the PSI-MS vocabulary (numpress combined with zlib, ...): MS:1000572 is "binary data compression type"
-_COMPRESSION_TERMS = {"MS:1002746", "MS:1002747", "MS:1002748", "MS:1003089", "MS:1003090", "MS:1003091"}
+# accession -> array flags: the plain numpress terms, and the terms for numpress followed by zlib
+_NUMPRESS_FLAGS = {"MS:1002312": PEAK_NUMPRESS_LINEAR, "MS:1002313": PEAK_NUMPRESS_PIC, "MS:1002314": PEAK_NUMPRESS_SLOF,
+                   "MS:1002746": PEAK_NUMPRESS_LINEAR | PEAK_ZLIB, "MS:1002747": PEAK_NUMPRESS_PIC | PEAK_ZLIB,
+                   "MS:1002748": PEAK_NUMPRESS_SLOF | PEAK_ZLIB}
+_NUMPRESS_NAME = dict(NUMPRESS, **{"MS:1002746": NUMPRESS["MS:1002312"], "MS:1002747": NUMPRESS["MS:1002313"],
+                                   "MS:1002748": NUMPRESS["MS:1002314"]})     # the skip reason names the codec
+# every other compression term of the PSI-MS vocabulary (numpress with truncation): MS:1000572 is "binary data compression type"
+_COMPRESSION_TERMS = {"MS:1003089", "MS:1003090", "MS:1003091"}
 
 
 def _local(tag: str) -> str:
@@ -69,16 +81,20 @@ def _array(chunk: PeakChunk, bda, groups, default_count: int):
     kind = MZ_ARRAY if MZ_ARRAY in p else INTENSITY_ARRAY if INTENSITY_ARRAY in p else None
     if kind is None:
         return None, -1
-    for acc, what in NUMPRESS.items():
-        if acc in p:
-            raise _Unsupported(what)
-    if any(acc in p for acc in _COMPRESSION_TERMS):
+    codecs = [acc for acc in _NUMPRESS_FLAGS if acc in p]
+    others = [acc for acc in (ZLIB, NO_COMPRESSION, *sorted(_COMPRESSION_TERMS)) if acc in p]
+    if codecs and (len(codecs) > 1 or others):                          # contradictory compression terms
+        raise _Unsupported(_NUMPRESS_NAME[codecs[0]])
+    if others and others[-1] in _COMPRESSION_TERMS:
         raise _Unsupported("unsupported compression")
-    flags = PEAK_ZLIB if ZLIB in p else 0
-    if FLOAT64 in p:
-        flags |= PEAK_F64
-    elif FLOAT32 not in p:
-        raise _Unsupported("unsupported binary data type")
+    if codecs:
+        flags = _NUMPRESS_FLAGS[codecs[0]]                              # float64 values whatever the float-width term says
+    else:
+        flags = PEAK_ZLIB if ZLIB in p else 0
+        if FLOAT64 in p:
+            flags |= PEAK_F64
+        elif FLOAT32 not in p:
+            raise _Unsupported("unsupported binary data type")
     count = int(bda.get("arrayLength", default_count))
     text = _first(bda, "binary").text or ""
     return kind, chunk.add_array("".join(text.split()).encode("ascii"), count, flags)

@@ -15,7 +15,8 @@ from typing import Dict, Iterator, List, Optional
 
 import numpy as np
 
-from .._lib import PEAK_BIG_ENDIAN, PEAK_F64, PEAK_PAIRS, PEAK_ZLIB
+from .._lib import PEAK_BIG_ENDIAN, PEAK_F64, PEAK_NUMPRESS_MASK, PEAK_PAIRS, PEAK_ZLIB
+from . import numpress
 
 # a chunk's payload is closed once it holds this many base64 bytes (one device call decodes one chunk)
 DEFAULT_CHUNK_BYTES = 1 << 30
@@ -62,8 +63,9 @@ class PeakChunk:
                 np.array(self._arrays, np.int64).reshape(-1, 4), np.array(self._spectra, np.int64).reshape(-1, 2))
 
     def host_values(self, row: int) -> np.ndarray:
-        """one array decoded on the host with the stdlib (base64, zlib): its values in their stored precision.
-        Raises ValueError on bad base64, a bad zlib stream or a value count other than the declared one."""
+        """one array decoded on the host with the stdlib (base64, zlib): its values in their stored precision; an MS-Numpress
+        array (base64, zlib if flagged, then the codec of `numpress`) as float64.
+        Raises ValueError on bad base64, a bad zlib or numpress stream or a value count other than the declared one."""
         off, ln, count, flags = self._arrays[row]
         try:
             raw = base64.b64decode(bytes(self._buf[off:off + ln]), validate=True)
@@ -71,6 +73,13 @@ class PeakChunk:
                 raw = zlib.decompress(raw)
         except (binascii.Error, zlib.error) as e:
             raise ValueError(str(e)) from e
+        if flags & PEAK_NUMPRESS_MASK:
+            if flags & (PEAK_F64 | PEAK_BIG_ENDIAN | PEAK_PAIRS):
+                raise ValueError("MS-Numpress together with a float width, byte order or pair flag")
+            v = numpress.decode(flags & PEAK_NUMPRESS_MASK, raw)
+            if len(v) != count:
+                raise ValueError(f"{len(v)} MS-Numpress values for {count} declared values")
+            return v
         dt = np.dtype(np.float64 if flags & PEAK_F64 else np.float32).newbyteorder(">" if flags & PEAK_BIG_ENDIAN else "<")
         per = 2 if flags & PEAK_PAIRS else 1
         if len(raw) != count * per * dt.itemsize:

@@ -396,8 +396,14 @@ int fal_process_spectra(fal_ctx* ctx, const double* mz, const float* intensity,
  * arrays:  i64[n_arrays][4] = {offset into payload (multiple of 8), base64 length (multiple of 4, no whitespace),
  *          declared value count (mzML defaultArrayLength / arrayLength, mzXML peaksCount = pairs), FAL_PEAK_* flags}.
  * spectra: i64[n_spectra][2] = {m/z array, intensity array} (rows of `arrays`; an mzXML pair array is named twice).
- * inflate_bytes: device scratch for the zlib arrays, at least the sum over zlib arrays of round_up(count x element size
- *          (x 2 for pairs), 8); nnz_cap: room of out_mz / out_intensity (the sum of the m/z arrays' counts).
+ * inflate_bytes: device scratch for the zlib and MS-Numpress arrays, at least the sum over arrays of two terms, each rounded
+ *          up to 8: the inflated capacity of a zlib array -- count x element size (x 2 for pairs); of a numpress stream, whose
+ *          inflated size is not declared, the longest stream of `count` values: linear 8 (count 0), 12 (count 1), else
+ *          16 + ceil(9 (count - 2) / 2); pic ceil(9 count / 2); slof 8 + 2 count -- and count x 8 for a numpress array (its
+ *          decoded float64 values).  nnz_cap: room of out_mz / out_intensity (the sum of the m/z arrays' counts).
+ * MS-Numpress (FAL_PEAK_NUMPRESS_*, DESIGN.md "MS-Numpress" states the format): the array's bytes (after base64, and after
+ *          zlib when FAL_PEAK_ZLIB is set as well) are a numpress stream of `count` values, decoded to float64 (m/z as is,
+ *          intensity rounded to float32).  A codec together with F64, BIG_ENDIAN or PAIRS is FAL_PEAK_ST_DESC.
  * -> out_indptr i64[n_spectra + 1] (the declared counts), out_mz f64, out_intensity f32 (sorted by m/z inside every spectrum,
  *    stable: the order of np.lexsort((mz, row))), status_out i32[n_spectra]: 0, or FAL_PEAK_ST_* bits (that spectrum's peaks
  *    are zeros).  A corrupt array never makes the call fail or write outside its slot. ------------------------------ [dev] */
@@ -405,6 +411,10 @@ int fal_process_spectra(fal_ctx* ctx, const double* mz, const float* intensity,
 #define FAL_PEAK_ZLIB        2   /* zlib stream (RFC 1950) */
 #define FAL_PEAK_BIG_ENDIAN  4   /* network byte order (mzXML) */
 #define FAL_PEAK_PAIRS       8   /* interleaved m/z-intensity pairs (mzXML) */
+#define FAL_PEAK_NUMPRESS_LINEAR 16 /* MS:1002312 linear prediction: fixed point + two values + half-byte second differences */
+#define FAL_PEAK_NUMPRESS_PIC    32 /* MS:1002313 positive integer: half-byte integers */
+#define FAL_PEAK_NUMPRESS_SLOF   48 /* MS:1002314 short logged float: fixed point + 16-bit logarithms */
+#define FAL_PEAK_NUMPRESS_MASK   48 /* the 2-bit codec field (0 = none); bit 64 is unassigned */
 #define FAL_PEAK_ST_DESC      1  /* bad descriptor: range outside the payload, misaligned, unknown flags, count mismatch */
 #define FAL_PEAK_ST_BASE64    2  /* a character outside the base64 alphabet, or misplaced padding */
 #define FAL_PEAK_ST_HEADER    4  /* bad zlib header */
@@ -413,6 +423,7 @@ int fal_process_spectra(fal_ctx* ctx, const double* mz, const float* intensity,
 #define FAL_PEAK_ST_SHORT    32  /* less data than the declared count */
 #define FAL_PEAK_ST_ADLER    64  /* Adler-32 trailer mismatch or missing */
 #define FAL_PEAK_ST_CAPACITY 128 /* inflate_bytes / nnz_cap too small */
+#define FAL_PEAK_ST_NUMPRESS 256 /* bad MS-Numpress stream: header length, fixed point, or the stream ends inside a value */
 int fal_decode_peaks(fal_ctx* ctx, const uint8_t* payload, int64_t payload_bytes,
                      const int64_t* arrays, int64_t n_arrays, const int64_t* spectra, int64_t n_spectra,
                      int64_t inflate_bytes, int64_t nnz_cap, int64_t* out_indptr, double* out_mz,

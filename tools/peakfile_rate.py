@@ -6,7 +6,7 @@ pairs, zlib, MS2 nested in MS1) and MGF, with an MS1 spectrum in front of every 
   xml_pass_s       the reader's streaming XML pass (`read_chunks`: metadata + base64 payload descriptors)
   host_decode_s    the same payload decoded with stdlib base64 + zlib on one host thread (`PeakChunk.host_spectra`)
   decode_call_ms   `fal_decode_peaks` (device events around the call after one warm-up, the payload already on the device;
-                   its five kernels and two scans), and GB/s of base64 in; decode_call_with_upload_ms also copies the payload
+                   its six kernels and two scans), and GB/s of base64 in; decode_call_with_upload_ms also copies the payload
   prepare_*        `falcon._prepare_spectra` end to end (read, decode, process_spectrum, partitions) in spectra/s, and the
                    MGF reader's on the same spectra
 and for MGF:
