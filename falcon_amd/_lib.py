@@ -114,6 +114,9 @@ _SIGNATURES = {
                        c_void_p, c_void_p, c_void_p, c_void_p], c_int),
     "fal_consensus_spectra": ([c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_double, c_double,
                                c_int64, c_void_p, c_void_p, c_void_p, c_void_p], c_int),
+    "fal_assign_nearest": ([c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p,
+                            c_void_p, c_void_p, c_int64, c_double, c_int, c_double, c_double, c_int, c_void_p, c_void_p,
+                            c_void_p], c_int),
 }
 
 

@@ -844,3 +844,28 @@ def consensus_spectra(dataset, labels, medoids, fragment_tol: float, min_fractio
     indptr, mz, intensity, status = pipe.ctx.consensus_spectra(dataset.mz, dataset.intensity, dataset.indptr, labels, medoids,
                                                                fragment_tol, min_fraction)
     return indptr.cpu().numpy(), mz.cpu().numpy(), intensity.cpu().numpy(), status.cpu().numpy()
+
+
+def assign_to_library(queries: SpectrumDataset, library: SpectrumDataset, eps: float, precursor_tol: float, mode: str,
+                      rt_tol: Optional[float], fragment_tol: float, min_matched_peaks: int,
+                      pipeline: Optional[ClusterPipeline] = None):
+    """Nearest representative of every spectrum of `queries` among the spectra of `library` (one precursor charge; both
+    preprocessed): `fal_assign_nearest` (DESIGN.md "Assigning to representatives").  A library row is a candidate when it passes
+    the neighbour filter's precursor (and RT) test with the new spectrum in the query role; the winner minimises (float32
+    matched-peak cosine distance, library precursor m/z, library row).  A spectrum is assigned when it has a candidate and
+    float32(best_dist) <= float32(eps) -- the comparison DBSCAN makes.
+
+    Returns (best_row int32[nq] library row or -1, best_dist float32[nq] (1.0 without a candidate), n_cand int32[nq],
+    assigned bool[nq])."""
+    global _default_pipeline
+    pipe = pipeline or _default_pipeline
+    if pipe is None:
+        pipe = _default_pipeline = ClusterPipeline()
+    if mode not in ("ppm", "Da"):
+        raise ValueError(f"unknown precursor tolerance mode {mode!r} (ppm or Da)")
+    row, dist, cand = pipe.ctx.assign_nearest(queries.mz, queries.intensity, queries.indptr, queries.precursor_mz,
+                                              queries.retention_time, library.mz, library.intensity, library.indptr,
+                                              library.precursor_mz, library.retention_time, precursor_tol, mode, rt_tol,
+                                              fragment_tol, min_matched_peaks)
+    row, dist, cand = row.cpu().numpy(), dist.cpu().numpy(), cand.cpu().numpy()
+    return row, dist, cand, (row >= 0) & (dist <= np.float32(eps))

@@ -41,6 +41,11 @@ class Config:
         p.add_argument("--consensus_min_fraction", type=float, default=0.25,
                        help="Consensus representatives: a merged peak is kept when at least this fraction of the cluster's "
                             "members' worth of peaks falls into it (0 < q <= 1, default: 0.25).")
+        p.add_argument("--assign_to", nargs="+", default=None, metavar="FILE",
+                       help="Representative MGF files of earlier runs (--export_representatives output, one CLUSTER= id per "
+                            "entry): a new spectrum whose nearest representative inside the precursor (and RT) tolerance lies "
+                            "within the distance threshold takes that cluster's id; the rest are clustered among themselves "
+                            "with ids above the files' largest.")
         # CLUSTERING  (config.py:76-124)
         p.add_argument("--precursor_tol", nargs=2, default=[20, "ppm"],
                        help='Precursor tolerance mass and mode (default: 20 ppm). Mode is "ppm" or "Da".')
@@ -176,6 +181,10 @@ class Config:
             self._parser.error(f"--mgf_reader {ns['mgf_reader']}: device or host")
         if ns["representatives"] == "consensus" and not ns["export_representatives"]:
             self._parser.error("--representatives consensus needs --export_representatives (there is no other output it changes)")
+        if ns["assign_to"] is not None and isinstance(ns["assign_to"], str):
+            ns["assign_to"] = [ns["assign_to"]]
+        if ns["assign_to"] and ns["distributed"]:
+            self._parser.error("--assign_to does not combine with --distributed (the assignment to representatives is not sharded)")
         if not 1 <= ns["low_dim"] <= 800:
             raise ValueError("low_dim must be an integer in [1, 800] (README.md:114-117; the widest rows the kernels hold)")
         if ns["n_neighbors_ann"] < ns["n_neighbors"]:

@@ -585,6 +585,36 @@ class Context:
         return labels, medoids[:int(nl.value)], lab_sorted, int(nc.value)
 
 
+    # ------------------------------------------------------------------ nearest representative
+    def assign_nearest(self, q_mz, q_intensity, q_indptr, q_precursor_mz, q_rt, l_mz, l_intensity, l_indptr, l_precursor_mz, l_rt,
+                       tol: float, mode: str, rt_tol, fragment_tol: float, min_matches: int):
+        """`fal_assign_nearest`: for every query spectrum the nearest library spectrum (matched-peak cosine, the query first)
+        among the library rows inside its precursor (and RT) tolerance.  Peaks f32 CSR per side, precursor m/z f32, RT f32 or
+        None (needed on both sides when `rt_tol` is given).
+        -> best_row i32[nq] (library row, -1 = no candidate), best_dist f32[nq] (1.0 then), n_cand i32[nq].  Device tensors;
+        synchronises once."""
+        torch = _torch()
+        q_pmz, l_pmz = self.to_dev(q_precursor_mz, torch.float32), self.to_dev(l_precursor_mz, torch.float32)
+        nq, nl = int(q_pmz.numel()), int(l_pmz.numel())
+        if rt_tol is not None and nq and nl and (q_rt is None or l_rt is None):
+            raise ValueError("assign_nearest: rt_tol needs the retention times of both sides")
+        q_mz, q_intensity, q_indptr, _ = self._peaks(q_mz, q_intensity, q_indptr, np.zeros(0, np.int64))
+        l_mz, l_intensity, l_indptr, _ = self._peaks(l_mz, l_intensity, l_indptr, np.zeros(0, np.int64))
+        if q_indptr.numel() != nq + 1 or l_indptr.numel() != nl + 1:
+            raise ValueError(f"assign_nearest: indptr has {q_indptr.numel()} / {l_indptr.numel()} entries for {nq} / {nl} spectra")
+        q_rt = None if q_rt is None or rt_tol is None else self.to_dev(q_rt, torch.float32)
+        l_rt = None if l_rt is None or rt_tol is None else self.to_dev(l_rt, torch.float32)
+        best_row = self.empty((nq,), torch.int32)
+        best_dist = self.empty((nq,), torch.float32)
+        n_cand = self.empty((nq,), torch.int32)
+        ptr = lambda t: self._p(t if t is not None and t.numel() else None)
+        check(self.lib.fal_assign_nearest(self._h, ptr(q_mz), ptr(q_intensity), ptr(q_indptr), ptr(q_pmz), ptr(q_rt), nq, ptr(l_mz),
+                                          ptr(l_intensity), ptr(l_indptr), ptr(l_pmz), ptr(l_rt), nl, float(tol), int(mode == "Da"),
+                                          -1.0 if rt_tol is None else float(rt_tol), float(fragment_tol), int(min_matches),
+                                          ptr(best_row), ptr(best_dist), ptr(n_cand)), "fal_assign_nearest")
+        return best_row, best_dist, n_cand
+
+
 class IvfIndex:
     """Opaque `fal_ivf` handle (keeps the vectors alive: the index borrows them)."""
 

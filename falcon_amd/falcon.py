@@ -61,6 +61,8 @@ def _option_lines() -> List[str]:
     # (the consensus options are listed only when chosen: the default header stays what it was)
     extra = ([f"representatives = {c.representatives}", f"consensus_min_fraction = {c.consensus_min_fraction:.3f}"]
              if c.representatives == "consensus" else [])
+    if c.assign_to:          # (likewise: without the option every output is what it was)
+        extra.append(f"assign_to = {' '.join(c.assign_to)}")
     return [
         f"work_dir = {c.work_dir}", f"overwrite = {c.overwrite}",
         f"export_representatives = {c.export_representatives}",
@@ -98,11 +100,18 @@ def _run(args) -> int:
 
     ann = _ann_params()
     rows_all, current_label, representatives = [], 0, []
+    library = {}
+    if config.assign_to:
+        library, current_label = _load_library(spectra_dir, pipe.ctx)
     for charge in charges:                                                                     # falcon.py:153
         part = np.load(os.path.join(spectra_dir, f"spectra_charge_{charge}.npz"))     # plain arrays: no pickle
         n = len(part["precursor_mz"])
         if n == 0:
             continue
+        if charge in library:
+            part = _assign_charge(pipe, part, charge, library[charge], rows_all)
+            if part is None:
+                continue                 # every spectrum of the charge went to an existing cluster
         ds = cluster.SpectrumDataset(part["precursor_mz"], part["retention_time"], part["mz"], part["intensity"],
                                      part["indptr"])
         labels, medoids = cluster.generate_clusters(
@@ -114,6 +123,59 @@ def _run(args) -> int:
     if rm_work_dir:
         shutil.rmtree(config.work_dir)
     return 0
+
+
+def _load_library(spectra_dir: str, ctx):
+    """`--assign_to`: the representatives of the files, preprocessed with the run's options (scaling off: exported peaks are
+    already scaled) and partitioned by charge like any input -> ({charge: arrays + `cluster` ids}, first id of a new cluster).
+    Each charge's library is also left in the work directory (`library_charge_<z>.npz`): what the run matched against."""
+    _, min_mz, max_mz = spectrum.get_dim(config.min_mz, config.max_mz, config.fragment_tol)
+    specs = mgf_io.read_library([os.path.abspath(fn) for fn in config.assign_to])
+    logger.info("Read %d cluster representatives from %d file(s)", len(specs), len(config.assign_to))
+    if not specs:
+        return {}, 0
+    first_new = max(s["cluster"] for s in specs) + 1
+    mz, it, indptr = _raw_csr(specs)
+    pmz = np.array([s["precursor_mz"] for s in specs], np.float64)
+    charge = np.array([int(s["precursor_charge"]) if s.get("precursor_charge") else 0 for s in specs], np.int32)
+    valid, oip, omz, oit = _process(ctx, mz, it, indptr, pmz, charge, min_mz, max_mz, scaling=None)
+    logger.info("Skipped %d representatives the preprocessing rejects", int((~valid).sum()))
+    ids = np.array([s["cluster"] for s in specs], np.int64)
+    rt = np.array([s.get("retention_time", -1) for s in specs], np.float32)
+    library = {}
+    for z in np.unique(charge[valid]):
+        rows = np.flatnonzero(valid & (charge == z))
+        pos, off = _take_rows(oip, rows)
+        key = "None" if z == 0 else str(int(z))
+        library[key] = dict(precursor_mz=pmz[rows].astype(np.float32), retention_time=rt[rows], mz=omz[pos].astype(np.float32),
+                            intensity=oit[pos].astype(np.float32), indptr=off, cluster=ids[rows])
+        np.savez(os.path.join(spectra_dir, f"library_charge_{key}.npz"), **library[key])
+    return library, first_new
+
+
+def _dataset(part):
+    return cluster.SpectrumDataset(part["precursor_mz"], part["retention_time"], part["mz"], part["intensity"], part["indptr"])
+
+
+def _assign_charge(pipe, part, charge, lib, rows_all):
+    """`--assign_to`, one charge: every spectrum whose nearest representative lies within the threshold takes that cluster's id
+    (its CSV row is written here) -> the partition of the spectra that are left (same columns, rows in order), None when
+    none is left"""
+    n = len(part["precursor_mz"])
+    best_row, _, _, assigned = cluster.assign_to_library(
+        _dataset(part), _dataset(lib), config.eps, config.precursor_tol[0], config.precursor_tol[1], config.rt_tol,
+        config.fragment_tol, config.min_matched_peaks, pipeline=pipe)
+    ids = lib["cluster"][best_row[assigned]]
+    logger.info("Charge %s: assigned %d of %d spectra to %d existing clusters", charge, int(assigned.sum()), n, len(np.unique(ids)))
+    for i, cid in zip(np.flatnonzero(assigned), ids):
+        rows_all.append((str(part["filename"][i]), str(part["identifier"][i]), charge, np.float32(part["precursor_mz"][i]),
+                         np.float32(part["retention_time"][i]), int(cid)))
+    rest = np.flatnonzero(~assigned)
+    if len(rest) == 0:
+        return None
+    pos, off = _take_rows(part["indptr"], rest)
+    return dict(identifier=part["identifier"][rest], filename=part["filename"][rest], precursor_mz=part["precursor_mz"][rest],
+                retention_time=part["retention_time"][rest], mz=part["mz"][pos], intensity=part["intensity"][pos], indptr=off)
 
 
 def _setup_work_dir():
@@ -328,12 +390,13 @@ def _take_rows(indptr: np.ndarray, rows: np.ndarray):
     return pos, out
 
 
-def _process(ctx, mz, it, indptr, pmz, charge, min_mz, max_mz):
+def _process(ctx, mz, it, indptr, pmz, charge, min_mz, max_mz, scaling="config"):
     """`fal_process_spectra` over one raw CSR (host or device arrays) -> valid, out indptr, mz, intensity as host arrays"""
+    if scaling == "config":
+        scaling = None if config.scaling == "off" else config.scaling
     valid, oip, omz, oit = ctx.process_spectra(
         mz, it, indptr, pmz, charge, config.min_peaks, config.min_mz_range, min_mz, max_mz,
-        config.remove_precursor_tol, config.min_intensity, config.max_peaks_used,
-        None if config.scaling == "off" else config.scaling)
+        config.remove_precursor_tol, config.min_intensity, config.max_peaks_used, scaling)
     return valid.cpu().numpy(), oip.cpu().numpy(), omz.cpu().numpy(), oit.cpu().numpy()
 
 

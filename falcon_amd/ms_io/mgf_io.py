@@ -70,6 +70,63 @@ def get_spectra(source) -> Iterator[Dict]:
             f.close()
 
 
+class MgfLibraryError(ValueError):
+    """a representative MGF (`--assign_to`) without a usable CLUSTER= id; the message names the file and the entry"""
+
+
+def get_library_spectra(filename: str) -> Iterator[Dict]:
+    """The spectra of a representative MGF (what `--export_representatives` writes): `get_spectra`'s dicts plus `cluster`, the
+    integer of the entry's CLUSTER= line.  Every BEGIN IONS .. END IONS entry goes through `get_spectra` itself (an entry it
+    skips is skipped here); an entry it accepts without CLUSTER=, or with a value that is no integer, raises MgfLibraryError."""
+    with open(filename, "r") as f:
+        lines, inside, entry = [], False, 0
+        for line in f:
+            t = line.strip()
+            if t == "BEGIN IONS":
+                lines, inside = [line], True
+                continue
+            if not inside:
+                continue
+            lines.append(line)
+            if t != "END IONS":
+                continue
+            inside = False
+            entry += 1
+            got = list(get_spectra(io.StringIO("".join(lines))))
+            if len(got) != 1:
+                continue
+            value = None
+            for l in lines[1:-1]:
+                l = l.strip()
+                if l and l[0] not in "#;!/" and "=" in l and not (l[0].isdigit() or l[0] == "."):
+                    k, v = l.split("=", 1)
+                    if k.strip().lower() == "cluster":
+                        value = v.strip()
+            where = f"{filename}: entry {entry} (TITLE={got[0]['identifier']})"
+            if value is None:
+                raise MgfLibraryError(f"{where} has no CLUSTER= line: not a file of cluster representatives")
+            try:
+                got[0]["cluster"] = int(value)
+            except ValueError:
+                raise MgfLibraryError(f"{where}: CLUSTER={value} is not an integer") from None
+            yield got[0]
+
+
+def read_library(filenames) -> list:
+    """every spectrum of the representative MGFs `filenames`, in order, each with `cluster` and `filename`; the same cluster id
+    twice (inside one file or across them) raises MgfLibraryError"""
+    out, seen = [], {}
+    for fn in filenames:
+        for k, s in enumerate(get_library_spectra(fn)):
+            if s["cluster"] in seen:
+                raise MgfLibraryError(f"{fn}: spectrum {k + 1} (TITLE={s['identifier']}) repeats CLUSTER={s['cluster']} of "
+                                      f"{seen[s['cluster']]}")
+            seen[s["cluster"]] = f"{fn} (TITLE={s['identifier']})"
+            s["filename"] = fn
+            out.append(s)
+    return out
+
+
 def raw_csr(specs):
     """spectra of one peak file -> raw CSR (mz f64, intensity f32, indptr i64), peaks sorted by m/z inside every spectrum
     (stable), which is what spectrum_utils does when the reference constructs an MsmsSpectrum"""

@@ -480,6 +480,24 @@ int fal_consensus_spectra(fal_ctx* ctx, const float* mz, const float* intensity,
                           double min_fraction, int64_t nnz_cap, int64_t* out_indptr, float* out_mz, float* out_intensity,
                           int32_t* status_out);
 
+/* ---- nearest representative: for every query spectrum the library spectrum with the smallest matched-peak cosine distance
+ *          among its candidates (DESIGN.md "Assigning to representatives").  Both sides: peaks CSR (mz / intensity f32, indptr
+ *          i64[n+1]), precursor m/z f32[n], retention time f32[n] or NULL; one precursor charge; nq, nl < 2^31.
+ *          Library row l is a candidate of query q when it passes the per-pair test of fal_filter_neighbors with q in the query
+ *          role: diff = f32(pmz_q - pmz_l); Da: |diff| <= tol; ppm: |f32(diff / pmz_l) * 1e6| <= tol; and, with rt_tol >= 0
+ *          (negative = none, as fal_filter_neighbors), |f32(rt_q - rt_l)| <= rt_tol.  Only candidates are scored.
+ *          d(q, l) = float32(1 - cosine(q's peaks, l's peaks)) with fal_rescore_neighbors' arithmetic, the query first (d = 1
+ *          below min_matches or without peaks).  The winner minimises (d, precursor m/z of l, row of l).
+ * -> best_row i32[nq] (library row, -1 without a candidate), best_dist f32[nq] (1.0 without one), n_cand i32[nq] (candidates).
+ *    A candidate pair whose peaks chain into a component of more than 32 peaks a side fails the call with FAL_EUNSUPPORTED.
+ *    nl = 0 is legal (all -1 / 1.0 / 0), nq = 0 a no-op.  One stream synchronisation (error word and solver-pair count;
+ *    fal_ctx_counter 9 = the pairs the Hungarian solver finished). ------------------------------------------------- [dev] */
+int fal_assign_nearest(fal_ctx* ctx, const float* q_mz, const float* q_intensity, const int64_t* q_indptr,
+                       const float* q_precursor_mz, const float* q_rt, int64_t nq, const float* l_mz, const float* l_intensity,
+                       const int64_t* l_indptr, const float* l_precursor_mz, const float* l_rt, int64_t nl, double tol,
+                       int tol_is_da, double rt_tol, double fragment_tol, int min_matches, int32_t* best_row, float* best_dist,
+                       int32_t* n_cand);
+
 /* ---- sort by precursor m/z (reference cluster.py:73-85 `.sort_values`): stable.
  *          order_out i64[n] (dataset row of sorted position), mz_sorted_out f32[n]. [dev] */
 int fal_sort_by_precursor(fal_ctx* ctx, const float* precursor_mz, int64_t n,
