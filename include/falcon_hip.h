@@ -302,7 +302,9 @@ int fal_refine_clusters(fal_ctx* ctx, int32_t* labels, int64_t n,
 /* ---- a11+a12 medoids (reference cluster.py:512-553 on the sparse graph) and label
  *          globalisation (cluster.py:556-590, 144-155): labels_sorted -> labels by DATASET
  *          row with noise renumbered n_clusters.. in dataset-row order; medoids[c] =
- *          dataset row of cluster c's medoid (c < n_clusters), then the noise rows. [dev] */
+ *          dataset row of cluster c's medoid (c < n_clusters), then the noise rows.
+ *          Every id in [0, n_clusters) must have a member: the kernel indexes row_order with
+ *          the cluster's best row unconditionally. ---------------------------------- [dev] */
 int fal_finalize(fal_ctx* ctx, const int32_t* labels_sorted, int64_t n, int64_t n_clusters,
                  const int64_t* row_order, const int32_t* nb_idx, const float* nb_dist, int k,
                  int32_t* labels_out, int32_t* medoids_out, int64_t* n_labels /*[host]*/);

@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 
 from oracle import falcon_oracle as fo
+from tests.tail_cases import labels_and_medoids
 from tests.util import assert_topk_close, assert_topk_exact
 
 pytestmark = pytest.mark.gpu
@@ -76,17 +77,8 @@ def _check_stages(ctx, d, ds, tol, mode, rt_tol, batch_size, p, pipe=None):
     n_cl = int(lab.max()) + 1
     assert L["n_clusters"] == n_cl
     # a11 medoids + a12 labels
-    member = lab >= 0
-    safe = np.where(member, lab, 0)
     score = fo.medoid_scores_sparse(lab, ni, nd)
-    o = np.lexsort((np.arange(N), score, safe))
-    o = o[member[o]]
-    first = np.concatenate([[True], safe[o][1:] != safe[o][:-1]]) if len(o) else np.zeros(0, bool)
-    ref_labels = np.empty(N, np.int32)
-    ref_labels[order] = lab
-    noise = ref_labels == -1
-    ref_labels[noise] = np.arange(n_cl, n_cl + noise.sum())
-    ref_med = np.concatenate([order[o[first]], np.flatnonzero(noise)]).astype(np.int32)
+    ref_labels, ref_med = labels_and_medoids(lab, score, order)      # (the lexsort rule, shared with the tail tests)
     assert np.array_equal(labels, ref_labels)
     assert np.array_equal(medoids, ref_med)
     # contract of the seam (cluster.py:152-156): no -1 left, labels dense, medoid belongs to its cluster
