@@ -21,6 +21,9 @@ PEAK_STATUS = {1: "bad descriptor", 2: "bad base64", 4: "bad zlib header", 8: "b
                256: "bad MS-Numpress stream"}
 # fal_mgf_index / fal_mgf_parse: flags of a text the host reader has to read, and the per-spectrum status (include/falcon_hip.h)
 MGF_FLAG_BYTES, MGF_FLAG_LINES, MGF_ST_HOST = 1, 2, 1
+# fal_mzml_index / fal_mzml_parse: the same for mzML text (include/falcon_hip.h)
+MZML_FLAG_STRUCT, MZML_FLAG_MARKUP, MZML_FLAG_TAGS = 1, 2, 4
+MZML_ST_OK, MZML_ST_SKIP, MZML_ST_HOST = 0, 1, 2
 # fal_consensus_spectra: per-cluster status bits, and the pooled peaks one workgroup sorts in LDS (include/falcon_hip.h)
 CONS_FALLBACK, CONS_GLOBAL, CONS_CAPACITY, CONS_LDS_PEAKS = 1, 2, 4, 4096
 STAGES = {"vectorize": 0, "build": 1, "coarse": 2, "scan": 3, "select": 4, "filter": 5, "dbscan": 6, "tail": 7,
@@ -112,6 +115,9 @@ _SIGNATURES = {
     "fal_mgf_index": ([c_void_p, c_void_p, c_int64, P(c_int64)], c_int),
     "fal_mgf_parse": ([c_void_p, c_void_p, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                        c_void_p, c_void_p, c_void_p, c_void_p], c_int),
+    "fal_mzml_index": ([c_void_p, c_void_p, c_int64, P(c_int64)], c_int),
+    "fal_mzml_parse": ([c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                        c_void_p, c_void_p], c_int),
     "fal_consensus_spectra": ([c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_double, c_double,
                                c_int64, c_void_p, c_void_p, c_void_p, c_void_p], c_int),
     "fal_assign_nearest": ([c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p,

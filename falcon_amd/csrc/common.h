@@ -37,7 +37,7 @@ void set_error(const char* fmt, ...);
     } while (0)
 
 constexpr int kNumStages = 9;
-constexpr int kNumSlots = 44;   // scratch slots of a context (ivf.h names them)
+constexpr int kNumSlots = 49;   // scratch slots of a context (ivf.h names them)
 enum Stage { ST_VECTORIZE = 0, ST_BUILD = 1, ST_COARSE = 2, ST_SCAN = 3, ST_SELECT = 4,
              ST_FILTER = 5, ST_DBSCAN = 6, ST_TAIL = 7,
              ST_KERNEL = 8 };   // the launches of the cosine kernel alone (dense_kernel / scan16_kernel / list16_kernel / ivf_list4_kernel;
@@ -85,6 +85,12 @@ struct fal_ctx {
         int64_t bytes = -1, spectra = 0, peaks = 0, cap_lines = 0, cap_spectra = 0;
         const void* blocks[4] = {nullptr, nullptr, nullptr, nullptr};
     } mgf;
+    // the same for fal_mzml_index / fal_mzml_parse (mzmlscan.hip, SLOT_MZML*)
+    struct MzmlIndex {
+        const void* text = nullptr;
+        int64_t bytes = -1, spectra = 0, cap_tags = 0, cap_spectra = 0;
+        const void* blocks[4] = {nullptr, nullptr, nullptr, nullptr};
+    } mzml;
 
     // caching device allocator for per-call objects (index arrays): blocks are recycled, never
     // returned to the driver before the context dies (hipMalloc / hipFree cost ~100 us each and

@@ -16,7 +16,8 @@ enum { SLOT_JOBS = 0, SLOT_SIMS = 1, SLOT_PROBES = 2, SLOT_PROBE_SIM = 3, SLOT_Q
        SLOT_FIN3 = 19, SLOT_INV = 20, SLOT_INVCNT = 21, SLOT_SIMS2 = 22, SLOT_TILEJOB = 23, SLOT_FUSED = 24, SLOT_FUSED2 = 25, SLOT_FUSED3 = 26, SLOT_JOBS3 = 27, SLOT_WIN = 28, SLOT_CURSORS = 29, SLOT_ITEMS = 30,
        SLOT_EXACT = 31, SLOT_EXACT2 = 32, SLOT_EXACT3 = 33, SLOT_EXACT4 = 34, SLOT_EXACT5 = 35, SLOT_EXACT6 = 36,   // exact.hip
        SLOT_MGF = 37, SLOT_MGF2 = 38, SLOT_MGF3 = 39, SLOT_MGF4 = 40, SLOT_MGF5 = 41,   // mgfparse.hip (37-40 live from fal_mgf_index to fal_mgf_parse)
-       SLOT_ASSIGN = 42, SLOT_ASSIGN2 = 43 };   // assignrep.hip
+       SLOT_ASSIGN = 42, SLOT_ASSIGN2 = 43,   // assignrep.hip
+       SLOT_MZML = 44, SLOT_MZML2 = 45, SLOT_MZML3 = 46, SLOT_MZML4 = 47, SLOT_MZML5 = 48 };   // mzmlscan.hip (44-47 live from fal_mzml_index to fal_mzml_parse)
 // out[0..n] = exclusive prefix sums of in[0..n) (out has n + 1 entries)
 int launch_exclusive_scan(fal_ctx* ctx, const int64_t* in, int64_t n, int64_t* out);
 }

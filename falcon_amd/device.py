@@ -375,6 +375,51 @@ class Context:
         return dict(flags=0, lines=lines, indptr=indptr, mz=mz, intensity=it, precursor_mz=pmz, charge=charge,
                     has_charge=has_charge.astype(bool), retention_time=rt, title=title, span=span, status=status)
 
+    def mzml_index(self, d_text):
+        """`fal_mzml_index` of mzML text on the device (uint8 tensor) -> (spectra, tags inside spectra, `_lib.MZML_FLAG_*` bits,
+        tags).  Synchronises once.  The tables stay in the context for the `mzml_parse` of the same tensor."""
+        counts = (C.c_int64 * 4)()
+        check(self.lib.fal_mzml_index(self._h, self._p(d_text) if d_text.numel() else None, d_text.numel(), counts), "fal_mzml_index")
+        return tuple(int(c) for c in counts)
+
+    def mzml_parse(self, d_text, n: int):
+        """`fal_mzml_parse` behind `mzml_index` of the same tensor -> device tensors payload u8[n_bytes + 16 n], status i32[n],
+        id i64[n, 2], span i64[n, 2], precursor_mz f64[n], charge i32[n], retention_time f64[n], arrays i64[2 n, 4].  No sync."""
+        torch = _torch()
+        m = max(n, 1)
+        payload = self.empty((d_text.numel() + 16 * n,), torch.uint8)
+        status, charge = self.empty((m,), torch.int32), self.empty((m,), torch.int32)
+        ident, span = self.empty((m, 2), torch.int64), self.empty((m, 2), torch.int64)
+        pmz, rt = self.empty((m,), torch.float64), self.empty((m,), torch.float64)
+        arrays = self.empty((2 * m, 4), torch.int64)
+        check(self.lib.fal_mzml_parse(self._h, self._p(d_text) if d_text.numel() else None, d_text.numel(), n,
+                                      self._p(payload) if payload.numel() else None, payload.numel(), self._p(status), self._p(ident),
+                                      self._p(span), self._p(pmz), self._p(charge), self._p(rt), self._p(arrays)), "fal_mzml_parse")
+        return payload, status[:n], ident[:n], span[:n], pmz[:n], charge[:n], rt[:n], arrays[:2 * n]
+
+    def scan_mzml(self, text):
+        """mzML text from a <spectrum ...> on (bytes, uint8 array or uint8 device tensor) -> dict: `flags` (`_lib.MZML_FLAG_*`;
+        non-zero: the text is the host reader's and only `tags` is set besides), else `payload` u8[] on the device and the host
+        arrays `status` i32[n] (`_lib.MZML_ST_*`), `id` / `span` i64[n, 2] (byte ranges of the id value and of the spectrum),
+        `precursor_mz` f64, `charge` i32 (0: none), `retention_time` f64 (-1 when absent), `arrays` i64[2 n, 4] (rows 2 s and
+        2 s + 1: the m/z and the intensity array of spectrum s for `decode_peaks`; zeros unless the status is OK), and `tags`,
+        `inside` (tags, and tags inside spectra).  DESIGN.md "mzML on the device" states the grammar."""
+        torch = _torch()
+        if isinstance(text, torch.Tensor):
+            d_text = self.to_dev(text, torch.uint8)
+        else:
+            raw = np.frombuffer(text, np.uint8) if isinstance(text, (bytes, bytearray, memoryview)) else np.asarray(text, np.uint8)
+            if not raw.flags.writeable:
+                raw = raw.copy()                 # (immutable bytes: torch takes writable arrays only)
+            d_text = self.to_dev(raw) if len(raw) else self.empty((0,), torch.uint8)
+        n, inside, flags, tags = self.mzml_index(d_text)
+        if flags:
+            return dict(flags=flags, tags=tags)
+        payload, *cols = self.mzml_parse(d_text, n)
+        status, ident, span, pmz, charge, rt, arrays = (c.cpu().numpy() for c in cols)
+        return dict(flags=0, tags=tags, inside=inside, payload=payload, status=status, id=ident, span=span, precursor_mz=pmz,
+                    charge=charge, retention_time=rt, arrays=arrays)
+
     def consensus_spectra(self, mz, intensity, indptr, labels, medoids, fragment_tol: float, min_fraction: float = 0.25,
                           nnz_cap: Optional[int] = None):
         """`fal_consensus_spectra`: every cluster's members merged peak by peak (DESIGN.md "Consensus representatives").

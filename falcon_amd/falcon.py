@@ -87,6 +87,7 @@ def _run(args) -> int:
     for line in _option_lines():
         logger.debug(line)
     logger.debug("mgf_reader = %s", config.mgf_reader)       # (no output depends on it: not an option line of the CSV header)
+    logger.debug("mzml_reader = %s", config.mzml_reader)     # (the same)
     if config.distributed:
         return _run_distributed()
 
@@ -473,8 +474,17 @@ def _prepare_spectra(spectra_dir: str, min_mz: float, max_mz: float, ctx) -> Lis
         fn = os.path.abspath(fn)
         read_chunks = ms_io.chunk_reader(fn)
         if read_chunks is not None:                      # mzML / mzXML: binary arrays decoded on the device (fal_decode_peaks)
-            for chunk in read_chunks(fn):
+            read_device = ms_io.device_chunk_reader(fn) if config.mzml_reader == "device" else None
+            if read_device is None:
+                for chunk in read_chunks(fn):
+                    low_quality += _prepare_chunk(chunk, fn, parts, min_mz, max_mz, ctx)
+                continue
+            n_device = n_host = 0                        # mzML: the structure scanned on the device too (fal_mzml_index / _parse)
+            for chunk in read_device(fn, ctx):
                 low_quality += _prepare_chunk(chunk, fn, parts, min_mz, max_mz, ctx)
+                n_device += getattr(chunk, "n_device", 0)
+                n_host += getattr(chunk, "n_host", len(chunk))
+            logger.debug("mzML file %s: %d spectra decided on the device, %d handed to the host reader", fn, n_device, n_host)
             continue
         read_mgf = ms_io.device_reader(fn) if config.mgf_reader == "device" else None
         if read_mgf is not None:                         # MGF: the text parsed on the device (fal_mgf_index / fal_mgf_parse)

@@ -1,7 +1,8 @@
 """Peak-file front door: pick the reader / writer by file extension (the role of the reference's
 falcon/ms_io/ms_io.py:11-66).  MGF, mzML and mzXML are read (the extension test is case-insensitive); only MGF is written.
 The XML readers also hand their binary arrays, still encoded, to the device decoder (`read_chunks`); MGF text is parsed on the
-device as a whole (`device_reader`), with `mgf_io.get_spectra` as the reader of record."""
+device as a whole (`device_reader`), with `mgf_io.get_spectra` as the reader of record; the structure of mzML is scanned on the
+device (`device_chunk_reader`), with `mzml_io.read_chunks` as the reader of record."""
 import os
 
 from . import mgf_io, mzml_io, mzxml_io
@@ -9,6 +10,7 @@ from . import mgf_io, mzml_io, mzxml_io
 _READERS = {".mgf": mgf_io.get_spectra, ".mzml": mzml_io.get_spectra, ".mzxml": mzxml_io.get_spectra}
 _CHUNK_READERS = {".mzml": mzml_io.read_chunks, ".mzxml": mzxml_io.read_chunks}
 _DEVICE_READERS = {".mgf": mgf_io.read_chunks}
+_DEVICE_CHUNK_READERS = {".mzml": mzml_io.read_chunks_device}
 _WRITERS = {".mgf": mgf_io.write_spectra}
 
 
@@ -34,6 +36,12 @@ def chunk_reader(filename: str):
 def device_reader(filename: str):
     """the `read_chunks(filename, ctx, max_bytes)` of an MGF file, whose text is parsed on the device; None for other types"""
     return _DEVICE_READERS.get(_extension(filename))
+
+
+def device_chunk_reader(filename: str):
+    """the `read_chunks_device(filename, ctx, max_bytes)` of an mzML file, whose structure is scanned on the device and whose chunks
+    are `chunk_reader`'s with the payload left on the device; None for other types (mzXML stays on its host reader)"""
+    return _DEVICE_CHUNK_READERS.get(_extension(filename))
 
 
 def write_spectra(filename: str, spectra) -> None:

@@ -16,12 +16,19 @@ spectrum is skipped under the codec's name -- so older files that mark numpress 
 
 Elements are dropped once used, so memory follows the chunk's payload, not the file.  The binary arrays stay base64 text here:
 `PeakChunk` carries them to the device decoder (`fal_decode_peaks`) or decodes them on the host (`get_spectra`).
+
+`read_chunks_device` is the same reader with the structure of the spectra scanned on the device (`fal_mzml_index` +
+`fal_mzml_parse`, DESIGN.md "mzML on the device"): `read_chunks` / `_spectrum` stay the reader of record for the header, for every
+spectrum and every file outside the device's byte grammar, and the oracle of that path.
 """
 from __future__ import annotations
 
 import logging
+import re
 import xml.etree.ElementTree as ET
 from typing import Dict, Iterator
+
+import numpy as np
 
 from .._lib import PEAK_F64, PEAK_NUMPRESS_LINEAR, PEAK_NUMPRESS_PIC, PEAK_NUMPRESS_SLOF, PEAK_ZLIB
 from .peak_payload import DEFAULT_CHUNK_BYTES, PeakChunk
@@ -125,14 +132,14 @@ def _spectrum(chunk: PeakChunk, sp, groups) -> None:
         pass
 
 
-def read_chunks(filename: str, max_bytes: int = DEFAULT_CHUNK_BYTES) -> Iterator[PeakChunk]:
-    """stream an mzML (or indexedmzML) file -> PeakChunks of at most about `max_bytes` of base64 payload each"""
+def _iterparse_chunks(source, filename: str, max_bytes: int) -> Iterator[PeakChunk]:
+    """`read_chunks` over `source`, a file name or an object with read(); `filename` is the name the warning gives"""
     groups: Dict[str, list] = {}
     chunk = PeakChunk()
     stack = []
     keep = 0                  # open elements whose subtree is still needed (spectrum, referenceableParamGroup)
     try:
-        for ev, el in ET.iterparse(filename, events=("start", "end")):
+        for ev, el in ET.iterparse(source, events=("start", "end")):
             tag = _local(el.tag)
             if ev == "start":
                 stack.append(el)
@@ -155,6 +162,218 @@ def read_chunks(filename: str, max_bytes: int = DEFAULT_CHUNK_BYTES) -> Iterator
     except ET.ParseError as e:
         logger.warning("Failed to read file %s: %s", filename, e)
     yield chunk
+
+
+def read_chunks(filename: str, max_bytes: int = DEFAULT_CHUNK_BYTES) -> Iterator[PeakChunk]:
+    """stream an mzML (or indexedmzML) file -> PeakChunks of at most about `max_bytes` of base64 payload each"""
+    yield from _iterparse_chunks(filename, filename, max_bytes)
+
+
+# ---- the device reader (DESIGN.md "mzML on the device") ---------------------------------------------------------------------------
+DEVICE_CHUNK_BYTES = 64 << 20        # text of one device call (the tag table takes 7 bytes per text byte)
+_HEADER_READ = 1 << 20
+_SPECTRUM_OPEN = re.compile(rb"<spectrum[ \t\r\n>/]")
+_DECLARATION = re.compile(rb"^(?:\xef\xbb\xbf)?<\?xml([^>]*)\?>")
+_ENCODING = re.compile(rb"encoding\s*=\s*[\"']([^\"']*)[\"']")
+_CLOSE = b"</spectrum>"
+
+
+class DeviceChunk:
+    """The MS2+ spectra of one stretch of an mzML file, in file order, with `PeakChunk`'s surface: the columns, `skipped`, and
+    `tables()` whose payload stays where the device reader left it (a device tensor).  `n_device` / `n_host`: the spectra the
+    device decided (kept or MS1) and the ones handed to the host reader."""
+
+    def __init__(self, identifier, precursor_mz, precursor_charge, retention_time, payload, arrays, spectra, skipped, n_device, n_host):
+        self.identifier, self.precursor_mz, self.precursor_charge = identifier, precursor_mz, precursor_charge
+        self.retention_time, self.skipped, self.n_device, self.n_host = retention_time, skipped, n_device, n_host
+        self._tables = (payload, arrays, spectra)
+
+    def __len__(self):
+        return len(self.identifier)
+
+    @property
+    def nbytes(self) -> int:
+        return int(len(self._tables[0]))
+
+    def tables(self):
+        """-> payload u8[] (device tensor), arrays i64[m, 4], spectra i64[n, 2]: the arguments of `Context.decode_peaks`"""
+        return self._tables
+
+
+def _device_encoding(head: bytes) -> bool:
+    """the XML declaration names no encoding, or UTF-8 / US-ASCII: the bytes the device grammar takes mean what they say"""
+    m = _DECLARATION.match(head)
+    if m is None:
+        return not head.startswith((b"\xff\xfe", b"\xfe\xff"))            # (UTF-16 needs no declaration)
+    enc = _ENCODING.search(m.group(1))
+    return enc is None or enc.group(1).lower() in (b"utf-8", b"us-ascii")
+
+
+def _header_groups(header: bytes):
+    """the referenceableParamGroups of everything in front of the first spectrum -> `groups` as `read_chunks` builds it; None
+    when the header does not parse"""
+    groups: Dict[str, list] = {}
+    parser = ET.XMLPullParser(events=("end",))
+    try:
+        parser.feed(header)
+        for _, el in parser.read_events():
+            if _local(el.tag) == "referenceableParamGroup":
+                groups[el.get("id")] = [(c.get("accession"), c.get("value")) for c in el if _local(c.tag) == "cvParam"]
+    except ET.ParseError:
+        return None
+    return groups
+
+
+class _Chain:
+    """read() over byte strings and then an open file: what `ET.iterparse` needs of a source"""
+
+    def __init__(self, parts, f):
+        self.parts, self.f = [memoryview(p) for p in parts if len(p)], f
+
+    def read(self, size: int = -1) -> bytes:
+        if self.parts:
+            if size < 0:
+                out = b"".join(self.parts) + self.f.read()
+                self.parts = []
+                return out
+            out = bytes(self.parts[0][:size])
+            self.parts[0] = self.parts[0][size:]
+            if not len(self.parts[0]):
+                self.parts.pop(0)
+            return out
+        return self.f.read(size)
+
+
+def _join_payload(payload, used: int, more: np.ndarray):
+    """payload[:used] (a device tensor or a host array) with the host bytes `more` behind it"""
+    if not len(more):
+        return payload[:used]
+    if isinstance(payload, np.ndarray):
+        return np.concatenate([payload[:used], more])
+    import torch
+    return torch.cat([payload[:used], torch.from_numpy(more.copy()).to(payload.device)])
+
+
+def _device_chunk(head, res, groups, filename: str):
+    """one scanned stretch -> (DeviceChunk, stopped): the device's OK spectra, every HOST spectrum read by `_spectrum` from
+    its own bytes and put at its place in file order, SKIP and host-rejected spectra removed.  stopped: a HOST spectrum did not
+    parse -- the host reader's pass ends there with a warning, and so does this one."""
+    from .._lib import MZML_ST_HOST, MZML_ST_OK
+    from .mgf_io import _identifiers
+    status = res["status"]
+    n = len(status)
+    host = PeakChunk()
+    keep = status == MZML_ST_OK
+    host_rows = np.flatnonzero(status == MZML_ST_HOST)
+    stopped = False
+    for i in host_rows:
+        a, b = res["span"][i]
+        try:
+            el = ET.fromstring(bytes(head[a:b]))
+        except ET.ParseError as e:
+            logger.warning("Failed to read file %s: %s", filename, e)
+            keep[i:] = False
+            stopped = True
+            break
+        before = len(host)
+        _spectrum(host, el, groups)
+        keep[i] = len(host) > before
+    rows = np.flatnonzero(keep)
+    from_host = status[rows] == MZML_ST_HOST
+    text = np.frombuffer(head, np.uint8)
+    ident = _identifiers(text, res["id"][rows])
+    pmz, rt = res["precursor_mz"][rows].copy(), res["retention_time"][rows].copy()
+    charge = res["charge"][rows].astype(object)
+    charge[res["charge"][rows] == 0] = None
+    arrays = res["arrays"].reshape(n, 2, 4).copy()
+    arrays[status != MZML_ST_OK] = 0
+    arrays = arrays.reshape(2 * n, 4)
+    used = int((arrays[:, 0] + (arrays[:, 1] + 7) // 8 * 8).max(initial=0))
+    spectra = np.stack([2 * rows, 2 * rows + 1], axis=1).astype(np.int64)
+    more = np.zeros(0, np.uint8)
+    if len(host):
+        more, host_arrays, host_spectra = host.tables()
+        host_arrays = host_arrays.copy()
+        host_arrays[:, 0] += used
+        arrays = np.concatenate([arrays, host_arrays])
+        spectra[from_host] = host_spectra + 2 * n
+        ident = ident.astype(object)
+        ident[from_host] = host.identifier
+        ident = np.array(list(ident), dtype=str)
+        pmz[from_host], rt[from_host] = host.precursor_mz, host.retention_time
+        charge[from_host] = host.precursor_charge
+    chunk = DeviceChunk(ident, pmz, list(charge), rt, _join_payload(res["payload"], used, more), arrays, spectra, host.skipped,
+                        n - len(host_rows), len(host_rows))
+    return chunk, stopped
+
+
+def read_chunks_device(filename: str, ctx, max_bytes: int = DEVICE_CHUNK_BYTES):
+    """The device reader: everything in front of the first <spectrum ...> stays on the host (its param groups are read with
+    ElementTree); the rest is cut directly behind </spectrum> into stretches of about `max_bytes` (a stretch grows when one
+    spectrum is larger), each scanned by `ctx.scan_mzml`; spectra with status HOST are read by `_spectrum` from their own
+    bytes.  A stretch outside the device grammar, and whatever follows the file's last </spectrum>, goes through the host
+    reader's own pass over the header plus the remaining bytes -- a well-formed prefix, at the same line and column, so a
+    truncated file gives `read_chunks`' warning and spectra.  A declared encoding other than UTF-8 / US-ASCII, a DOCTYPE, a
+    first <spectrum inside a comment or CDATA section, a header that does not parse or a file without spectra is `read_chunks`' as a whole.
+    Yields `DeviceChunk`s (and `PeakChunk`s from the host pass); all chunks together are `read_chunks(filename)`'s."""
+    with open(filename, "rb") as f:
+        buf = bytearray(f.read(_HEADER_READ))
+        m, final = None, False
+        if _device_encoding(bytes(buf[:4096])):
+            searched = 0
+            while True:
+                m = _SPECTRUM_OPEN.search(buf, max(searched - 16, 0))
+                if m is not None or final:
+                    break
+                searched = len(buf)
+                more = f.read(_HEADER_READ)
+                final = len(more) == 0
+                buf += more
+        header = bytes(buf[:m.start()]) if m is not None else b""
+        # a DOCTYPE may define entities; behind an open comment or CDATA section the match is no tag
+        plain = (m is not None and b"<!DOCTYPE" not in header and header.rfind(b"<!--") <= header.rfind(b"-->") and
+                 header.rfind(b"<![CDATA[") <= header.rfind(b"]]>"))
+        groups = _header_groups(header) if plain else None
+        if groups is None:
+            yield from read_chunks(filename)
+            return
+        del buf[:len(header)]
+        lines, column = 0, 0          # of the bytes consumed behind the header: the host pass sees as many line breaks and columns
+        final = False
+        while True:
+            if not final and len(buf) < max_bytes:
+                more = f.read(max(max_bytes - len(buf), 1 << 16))
+                final = len(more) == 0
+                buf += more
+                continue
+            cut = buf.rfind(_CLOSE, 0, max(max_bytes, len(_CLOSE)))
+            if cut < 0:
+                cut = buf.find(_CLOSE)             # one spectrum larger than the stretch
+            if cut < 0:
+                if final:
+                    break                          # what is left has no complete spectrum: the host pass
+                more = f.read(max(max_bytes, 1 << 16))
+                final = len(more) == 0
+                buf += more
+                continue
+            cut += len(_CLOSE)
+            if cut >= 0x7FFFFFFF:
+                break                              # one spectrum beyond the device's 2^31 - 2 bytes: the host pass
+            head = buf[:cut]
+            res = ctx.scan_mzml(head)
+            if res["flags"]:
+                break
+            chunk, stopped = _device_chunk(head, res, groups, filename)
+            yield chunk
+            if stopped:
+                return
+            last = head.rfind(b"\n")
+            lines += head.count(b"\n")
+            tail = head[last + 1:]
+            column = (column if last < 0 else 0) + len(tail) - sum(tail.count(bytes([c])) for c in range(0x80, 0xC0))
+            del buf[:cut]
+        filler = b"\n" * lines + b" " * column
+        yield from _iterparse_chunks(_Chain([header, filler, bytes(buf)], f), filename, DEFAULT_CHUNK_BYTES)
 
 
 def get_spectra(source: str) -> Iterator[Dict]:

@@ -457,6 +457,38 @@ int fal_mgf_parse(fal_ctx* ctx, const uint8_t* text, int64_t n_bytes, int64_t n_
                   int64_t* out_indptr, double* out_mz, float* out_intensity, double* precursor_mz, int32_t* charge,
                   int32_t* has_charge, double* retention_time, int64_t* title, int64_t* span, int32_t* status_out);
 
+/* ---- mzML structure -> per-spectrum columns + the tables of fal_decode_peaks (the device reader; DESIGN.md "mzML on the
+ *          device" states the grammar; falcon_amd/ms_io/mzml_io.read_chunks is the reader it mirrors and the one that decides
+ *          whatever it leaves open).
+ * text: u8[n_bytes] on the device, 16-byte aligned, n_bytes < 2^31 - 1 (the caller cuts larger files behind a </spectrum>).
+ * fal_mzml_index: tag table ('<' positions), one fixed-size record per tag (kind and form, cvParam accession code, value span,
+ *          array length, a not-decided bit) and the spectrum table (<spectrum ...> paired with the next </spectrum>)
+ *          -> counts_out[4] (host) = {spectra, tags inside spectra, FAL_MZML_FLAG_* bits, tags}.  One stream synchronisation.
+ *          A flag means "this text is the host reader's" (the spectrum count is then 0): STRUCT -- spectrum opens and closes do
+ *          not alternate, or an open has no close; MARKUP -- a <!, a <? or a prefixed tag or attribute name anywhere; TAGS --
+ *          more tags than one per 4 bytes (the tag table is sized before the count is known).
+ * fal_mzml_parse: fills the caller's outputs from the tables of the fal_mzml_index call before it, which stay in scratch slots
+ *          of the context (the call checks text, n_bytes and n_spectra against that index and fails with FAL_EINVAL when they
+ *          are not its own, or when fal_ctx_trim ran in between).
+ * -> status i32[n]: FAL_MZML_ST_OK, FAL_MZML_ST_SKIP (MS1 or no ms level: no spectrum, nothing else of it was read) or
+ *    FAL_MZML_ST_HOST (the host reader decides this spectrum from its bytes); id i64[n][2] / span i64[n][2]: byte ranges
+ *    [from, to) of the id attribute's value and of the spectrum from its '<' to behind its </spectrum>; precursor_mz f64[n],
+ *    charge i32[n] (0: none), retention_time f64[n] (-1 when absent); arrays i64[2n][4]: rows 2s (m/z) and 2s + 1 (intensity)
+ *    of spectrum s in fal_decode_peaks' format, their base64 text copied into payload u8[payload_cap] at 8-byte aligned offsets
+ *    (gaps zero-filled; payload_cap >= n_bytes + 16 n_spectra always suffices and is required).  The columns and rows of a
+ *    spectrum that is not OK are zeros.
+ * Malformed text never makes a call fail or write outside a slot.  No host work per spectrum, tag or attribute. --------- [dev] */
+#define FAL_MZML_FLAG_STRUCT 1
+#define FAL_MZML_FLAG_MARKUP 2
+#define FAL_MZML_FLAG_TAGS   4
+#define FAL_MZML_ST_OK   0
+#define FAL_MZML_ST_SKIP 1
+#define FAL_MZML_ST_HOST 2
+int fal_mzml_index(fal_ctx* ctx, const uint8_t* text, int64_t n_bytes, int64_t* counts_out);
+int fal_mzml_parse(fal_ctx* ctx, const uint8_t* text, int64_t n_bytes, int64_t n_spectra, uint8_t* payload, int64_t payload_cap,
+                   int32_t* status_out, int64_t* id, int64_t* span, double* precursor_mz, int32_t* charge,
+                   double* retention_time, int64_t* arrays);
+
 /* ---- consensus representatives: the members of every cluster merged peak by peak (the reference exports medoids only,
  *          falcon.py:198-203; DESIGN.md "Consensus representatives" states the definition).
  * mz / intensity f32, indptr i64[n+1]: the preprocessed peaks in dataset-row order (fewer than 2^31 in all); labels i32[n]:
