@@ -78,19 +78,15 @@ struct fal_ctx {
     int32_t* zero_dev = nullptr;          // 16 zero words on the device (stream-ordered resets of fb_host)
     int64_t counters[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
 
-    // the tables fal_mgf_index left in the SLOT_MGF* slots for fal_mgf_parse (mgfparse.hip): the text they describe, the slot
-    // blocks they live in (fal_ctx_trim frees them: the pointers then differ) and the counts the host read back
-    struct MgfIndex {
+    // the tables fal_mgf_index / fal_mzml_index left in their slots (SLOT_MGF .. SLOT_MGF4, SLOT_MZML .. SLOT_MZML4) for
+    // fal_mgf_parse / fal_mzml_parse: the text they describe, the counts the host read back (extra: MGF's peaks), the capacities
+    // of the line / tag table and of the spectrum table, and the slot blocks they live in (fal_ctx_trim frees them: the
+    // pointers then differ).  textscan.h has the helpers.
+    struct TextIndex {
         const void* text = nullptr;
-        int64_t bytes = -1, spectra = 0, peaks = 0, cap_lines = 0, cap_spectra = 0;
+        int64_t bytes = -1, spectra = 0, extra = 0, cap_table = 0, cap_spectra = 0;
         const void* blocks[4] = {nullptr, nullptr, nullptr, nullptr};
-    } mgf;
-    // the same for fal_mzml_index / fal_mzml_parse (mzmlscan.hip, SLOT_MZML*)
-    struct MzmlIndex {
-        const void* text = nullptr;
-        int64_t bytes = -1, spectra = 0, cap_tags = 0, cap_spectra = 0;
-        const void* blocks[4] = {nullptr, nullptr, nullptr, nullptr};
-    } mzml;
+    } mgf, mzml;
 
     // caching device allocator for per-call objects (index arrays): blocks are recycled, never
     // returned to the driver before the context dies (hipMalloc / hipFree cost ~100 us each and

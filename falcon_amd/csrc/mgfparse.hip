@@ -3,9 +3,8 @@
 // grammar is DESIGN.md's "MGF on the device"; falcon_amd/ms_io/mgf_io.get_spectra is the reader all of this mirrors.
 //
 // fal_mgf_index (one synchronisation, at its end):
-//   newlines : 16 bytes per lane, 4 KB per block: '\n' count per block, and the byte check of the device grammar;
-//              a device scan of the block counts gives every block's first line;
-//   lines    : the same walk writes the line table: start[k] = first byte of line k (i32), start[lines] = n + 1;
+//   newlines : textscan.h's count walk over '\n', with the byte check of the device grammar; a device scan of the tile counts;
+//   lines    : textscan.h's table walk (Shift 1): start[k] = first byte of line k (i32), start[lines] = n + 1;
 //   classify : a block takes 256 consecutive lines, stages their bytes -- one contiguous range, so lines never straddle a tile --
 //              into LDS with 16-byte loads per lane and classifies a line per thread from there (a range that does not fit the
 //              tile is read from global memory); per block: first / last BEGIN-END marker and the spectra closed inside it;
@@ -31,11 +30,10 @@
 namespace fal {
 namespace {
 
-constexpr int kTileBytes = 4096;                 // newline passes: 256 lanes x 16 bytes
 constexpr int kBlockLines = 256;                 // classify / spectra passes: a line per thread
 constexpr int kStageBytes = 16384;               // classify: LDS tile of a block's 256 lines (64 bytes a line on average)
 constexpr int kWaveStage = 4096;                 // parse: LDS tile of a wave's 64 lines
-enum { META_LINES = 0, META_FLAGS = 1, META_SPECTRA = 2, META_PEAKS = 3, META_WORDS = 4 };
+enum { META_LINES = META_COUNT, META_SPECTRA = 2, META_PEAKS = 3 };
 
 // ---- newlines per 4 KB block + the byte grammar ------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void mgf_newlines_kernel(const uint8_t* __restrict__ text, int64_t n, int32_t* __restrict__ block_nl,
@@ -45,17 +43,14 @@ __global__ __launch_bounds__(256) void mgf_newlines_kernel(const uint8_t* __rest
     // the byte behind this lane's 16: the next lane's first (the last lane of a wave reads it)
     uint32_t next = __shfl_down(v.x & 0xFF, 1, 64);
     if ((threadIdx.x & 63) == 63) next = pos + 16 < n ? text[pos + 16] : 0;
-    int cnt = 0;
     bool bad = false;
 #pragma unroll
     for (int j = 0; j < 16; ++j) {
         const uint32_t c = byte_of(v, j), c1 = j < 15 ? byte_of(v, j + 1) : next;
-        const bool in = pos + j < n;
-        cnt += in && c == '\n';
-        bad |= in && !(c == '\t' || c == '\n' || (c >= 0x20 && c <= 0x7E) || (c == '\r' && pos + j + 1 < n && c1 == '\n'));
+        bad |= pos + j < n && !(c == '\t' || c == '\n' || (c >= 0x20 && c <= 0x7E) || (c == '\r' && pos + j + 1 < n && c1 == '\n'));
     }
     int total;
-    block_prefix(cnt, &total);
+    block_prefix(count_marks<'\n'>(v, n, pos), &total);
     if (threadIdx.x == 0) block_nl[blockIdx.x] = total;
     if (__ballot(bad) != 0 && (threadIdx.x & 63) == 0) atomicOr(&meta[META_FLAGS], (unsigned long long)FAL_MGF_FLAG_BYTES);
 }
@@ -64,26 +59,7 @@ __global__ __launch_bounds__(256) void mgf_newlines_kernel(const uint8_t* __rest
 __global__ __launch_bounds__(256) void mgf_lines_kernel(const uint8_t* __restrict__ text, int64_t n, const int64_t* __restrict__ block_base,
                                                         int64_t n_blocks, int32_t* __restrict__ start, int64_t cap_lines,
                                                         unsigned long long* __restrict__ meta) {
-    const int64_t pos = blockIdx.x * (int64_t)kTileBytes + threadIdx.x * 16;
-    const uint4 v = load16(text, n, pos);
-    int cnt = 0;
-#pragma unroll
-    for (int j = 0; j < 16; ++j) cnt += pos + j < n && byte_of(v, j) == '\n';
-    int total;
-    int64_t line = block_base[blockIdx.x] + block_prefix(cnt, &total) + 1;        // the line that starts behind this lane's first '\n'
-#pragma unroll
-    for (int j = 0; j < 16; ++j)
-        if (pos + j < n && byte_of(v, j) == '\n') {
-            if (line <= cap_lines) start[line] = (int32_t)(pos + j + 1);
-            ++line;
-        }
-    if (blockIdx.x == 0 && threadIdx.x == 0) {
-        const int64_t lines = block_base[n_blocks] + 1;
-        start[0] = 0;
-        meta[META_LINES] = (unsigned long long)lines;
-        if (lines <= cap_lines) start[lines] = (int32_t)(n + 1);
-        else atomicOr(&meta[META_FLAGS], (unsigned long long)FAL_MGF_FLAG_LINES);
-    }
+    mark_table_pass<'\n', 1, FAL_MGF_FLAG_LINES>(text, n, block_base, n_blocks, start, cap_lines, meta);
 }
 
 __device__ __forceinline__ int64_t indexed_lines(const unsigned long long* meta) {      // 0 when the table overflowed
@@ -388,13 +364,9 @@ using namespace fal;
 
 extern "C" int fal_mgf_index(fal_ctx* ctx, const uint8_t* text, int64_t n_bytes, int64_t* counts_out) {
     fal::CallScope _call(ctx);
-    FAL_REQUIRE(ctx && counts_out && n_bytes >= 0 && n_bytes < 0x7FFFFFFF, FAL_EINVAL, "fal_mgf_index: bad argument");
-    FAL_REQUIRE(n_bytes == 0 || (text && ((uintptr_t)text & 15) == 0), FAL_EINVAL, "fal_mgf_index: text NULL or not 16-byte aligned");
-    ctx->mgf = fal_ctx::MgfIndex{};
-    for (int i = 0; i < 4; ++i) counts_out[i] = 0;
+    FAL_TRY(text_index_begin("fal_mgf_index", ctx, &fal_ctx::mgf, text, n_bytes, counts_out));
     if (n_bytes == 0) {
-        ctx->mgf.text = text;
-        ctx->mgf.bytes = 0;
+        counts_out[3] = 1;                                                      // (lines = '\n' + 1, as for every other text)
         return FAL_OK;
     }
     const int64_t n_tiles = ceil_div(n_bytes, kTileBytes);
@@ -420,24 +392,19 @@ extern "C" int fal_mgf_index(fal_ctx* ctx, const uint8_t* text, int64_t n_bytes,
     hipLaunchKernelGGL(mgf_lines_kernel, dim3((unsigned)n_tiles), dim3(256), 0, ctx->stream, text, n_bytes, block_base, n_tiles, start,
                        cap_lines, meta);
     FAL_CHECK_HIP(hipGetLastError());
-    const auto grid_for = [&](int64_t items, int per_block) {
-        return (unsigned)std::max<int64_t>(1, std::min<int64_t>(ceil_div(items, per_block), (int64_t)ctx->num_cus * 16));
-    };
-    hipLaunchKernelGGL(mgf_classify_kernel, dim3(grid_for(cap_lines, kBlockLines)), dim3(256), 0, ctx->stream, text, n_bytes, start, meta,
-                       cls, summary);
+    const unsigned line_grid = capped_grid(ctx, cap_lines, kBlockLines);
+    hipLaunchKernelGGL(mgf_classify_kernel, dim3(line_grid), dim3(256), 0, ctx->stream, text, n_bytes, start, meta, cls, summary);
     FAL_CHECK_HIP(hipGetLastError());
     hipLaunchKernelGGL(mgf_blocks_kernel, dim3(1), dim3(64), 0, ctx->stream, summary, carry, meta);
     FAL_CHECK_HIP(hipGetLastError());
-    hipLaunchKernelGGL(mgf_spectra_kernel, dim3(grid_for(cap_lines, kBlockLines)), dim3(256), 0, ctx->stream, cls, meta, carry, cap_spectra,
-                       spec_begin, spec_end);
+    hipLaunchKernelGGL(mgf_spectra_kernel, dim3(line_grid), dim3(256), 0, ctx->stream, cls, meta, carry, cap_spectra, spec_begin,
+                       spec_end);
     FAL_CHECK_HIP(hipGetLastError());
-    hipLaunchKernelGGL(mgf_counts_kernel, dim3(grid_for(cap_spectra, 4)), dim3(256), 0, ctx->stream, cls, meta, cap_spectra, spec_begin,
-                       spec_end, spec_count);
+    hipLaunchKernelGGL(mgf_counts_kernel, dim3(capped_grid(ctx, cap_spectra, 4)), dim3(256), 0, ctx->stream, cls, meta, cap_spectra,
+                       spec_begin, spec_end, spec_count);
     FAL_CHECK_HIP(hipGetLastError());
-    unsigned long long* h = nullptr;
-    FAL_TRY(ctx->pinned_reserve(sizeof(unsigned long long) * META_WORDS, (void**)&h));
-    FAL_CHECK_HIP(hipMemcpyAsync(h, meta, sizeof(unsigned long long) * META_WORDS, hipMemcpyDeviceToHost, ctx->stream));
-    FAL_CHECK_HIP(hipStreamSynchronize(ctx->stream));
+    const unsigned long long* h = nullptr;
+    FAL_TRY(read_meta(ctx, meta, &h));
     const int64_t flags = (int64_t)h[META_FLAGS];
     const bool overflow = (flags & FAL_MGF_FLAG_LINES) != 0;
     FAL_REQUIRE(overflow || (int64_t)h[META_SPECTRA] <= cap_spectra, FAL_EINTERNAL, "fal_mgf_index: more spectra than 20-byte slots");
@@ -445,16 +412,7 @@ extern "C" int fal_mgf_index(fal_ctx* ctx, const uint8_t* text, int64_t n_bytes,
     counts_out[1] = overflow ? 0 : (int64_t)h[META_PEAKS];
     counts_out[2] = flags;
     counts_out[3] = (int64_t)h[META_LINES];
-    ctx->mgf.text = text;
-    ctx->mgf.bytes = n_bytes;
-    ctx->mgf.spectra = counts_out[0];
-    ctx->mgf.peaks = counts_out[1];
-    ctx->mgf.cap_lines = cap_lines;
-    ctx->mgf.cap_spectra = cap_spectra;
-    ctx->mgf.blocks[0] = start;
-    ctx->mgf.blocks[1] = cls;
-    ctx->mgf.blocks[2] = small;
-    ctx->mgf.blocks[3] = spec;
+    store_index(ctx->mgf, text, n_bytes, counts_out[0], counts_out[1], cap_lines, cap_spectra, start, cls, small, spec);
     return FAL_OK;
 }
 
@@ -463,32 +421,29 @@ extern "C" int fal_mgf_parse(fal_ctx* ctx, const uint8_t* text, int64_t n_bytes,
                              int32_t* has_charge, double* retention_time, int64_t* title, int64_t* span, int32_t* status_out) {
     fal::CallScope _call(ctx);
     FAL_REQUIRE(ctx && out_indptr && n_spectra >= 0 && nnz_cap >= 0, FAL_EINVAL, "fal_mgf_parse: bad argument");
-    const fal_ctx::MgfIndex& ix = ctx->mgf;
-    bool mine = ix.bytes == n_bytes && ix.text == text && ix.spectra == n_spectra;
-    if (mine && n_bytes > 0)
-        mine = ix.blocks[0] && ix.blocks[0] == ctx->scratch[SLOT_MGF].ptr && ix.blocks[1] == ctx->scratch[SLOT_MGF2].ptr &&
-               ix.blocks[2] == ctx->scratch[SLOT_MGF3].ptr && ix.blocks[3] == ctx->scratch[SLOT_MGF4].ptr;
-    FAL_REQUIRE(mine, FAL_EINVAL, "fal_mgf_parse: not the text, length and spectrum count of the last fal_mgf_index of this context");
+    const fal_ctx::TextIndex& ix = ctx->mgf;
+    FAL_REQUIRE(matches(ctx, ix, SLOT_MGF, text, n_bytes, n_spectra), FAL_EINVAL,
+                "fal_mgf_parse: not the text, length and spectrum count of the last fal_mgf_index of this context");
     if (n_spectra == 0) {
         FAL_CHECK_HIP(hipMemsetAsync(out_indptr, 0, sizeof(int64_t), ctx->stream));
         return FAL_OK;
     }
-    FAL_REQUIRE(nnz_cap >= ix.peaks, FAL_EINVAL, "fal_mgf_parse: nnz_cap %lld below the indexed peak count %lld", (long long)nnz_cap,
-                (long long)ix.peaks);
+    FAL_REQUIRE(nnz_cap >= ix.extra, FAL_EINVAL, "fal_mgf_parse: nnz_cap %lld below the indexed peak count %lld", (long long)nnz_cap,
+                (long long)ix.extra);
     FAL_REQUIRE(precursor_mz && charge && has_charge && retention_time && title && span && status_out, FAL_EINVAL,
                 "fal_mgf_parse: NULL column");
-    FAL_REQUIRE(ix.peaks == 0 || (out_mz && out_intensity), FAL_EINVAL, "fal_mgf_parse: NULL peaks");
+    FAL_REQUIRE(ix.extra == 0 || (out_mz && out_intensity), FAL_EINVAL, "fal_mgf_parse: NULL peaks");
     const int32_t* start = static_cast<const int32_t*>(ix.blocks[0]);
     const uint8_t* cls = static_cast<const uint8_t*>(ix.blocks[1]);
     const int32_t* spec = static_cast<const int32_t*>(ix.blocks[3]);
     const int32_t *spec_begin = spec, *spec_end = spec + ix.cap_spectra, *spec_count = spec + 2 * ix.cap_spectra;
     uint8_t* tmp = nullptr;
-    const size_t mz_bytes = sizeof(double) * (size_t)ix.peaks;
-    FAL_TRY(ctx->reserve(SLOT_MGF5, mz_bytes + sizeof(float) * (size_t)ix.peaks + 64, (void**)&tmp));
+    const size_t mz_bytes = sizeof(double) * (size_t)ix.extra;
+    FAL_TRY(ctx->reserve(SLOT_MGF5, mz_bytes + sizeof(float) * (size_t)ix.extra + 64, (void**)&tmp));
     double* tmp_mz = reinterpret_cast<double*>(tmp);
     float* tmp_it = reinterpret_cast<float*>(tmp + mz_bytes);
     FAL_TRY(device_scan_i32(ctx, spec_count, n_spectra, out_indptr, SLOT_SORT));
-    const unsigned grid = (unsigned)std::max<int64_t>(1, std::min<int64_t>(ceil_div(n_spectra, 4), (int64_t)ctx->num_cus * 16));
+    const unsigned grid = capped_grid(ctx, n_spectra, 4);
     const MgfOut out{precursor_mz, charge, has_charge, retention_time, title, span, status_out};
     hipLaunchKernelGGL(mgf_parse_kernel, dim3(grid), dim3(256), 0, ctx->stream, text, n_bytes, start, cls, spec_begin, spec_end, n_spectra,
                        out_indptr, nnz_cap, tmp_mz, tmp_it, out);

@@ -3,8 +3,8 @@
 // falcon_amd/ms_io/mzml_io.read_chunks is the reader all of this mirrors.
 //
 // fal_mzml_index (one synchronisation, at its end):
-//   count    : 16 bytes per lane, 4 KB per block: '<' count per block; a device scan gives every block's first tag;
-//   tags     : the same walk writes the tag table: pos[k] = the '<' of tag k (i32), pos[tags] = n;
+//   count    : textscan.h's count walk over '<'; a device scan of the tile counts;
+//   tags     : textscan.h's table walk (Shift 0): pos[k] = the '<' of tag k (i32), pos[tags] = n;
 //   classify : a block takes 256 consecutive tags, stages their bytes -- one contiguous range -- into LDS with 16-byte loads per
 //              lane and classifies a tag per thread from there: name, form, the quote-aware walk to '>', the attributes (a
 //              range that does not fit the tile, because binary text lies in it, is read from global memory).  Every tag
@@ -35,46 +35,20 @@ static_assert(fal::MZ_ST_OK == FAL_MZML_ST_OK && fal::MZ_ST_SKIP == FAL_MZML_ST_
 namespace fal {
 namespace {
 
-constexpr int kTileBytes = 4096;                 // count / tags passes: 256 lanes x 16 bytes
 constexpr int kBlockTags = 256;                  // classify / spectra passes: a tag per thread
 constexpr int kStageBytes = 32768;               // classify: LDS tile of a block's 256 tags
-enum { META_TAGS = 0, META_FLAGS = 1, META_SPECTRA = 2, META_INSIDE = 3, META_WORDS = 4 };
+enum { META_TAGS = META_COUNT, META_SPECTRA = 2, META_INSIDE = 3 };
 
 // ---- '<' per 4 KB block ----------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void mzml_count_kernel(const uint8_t* __restrict__ text, int64_t n, int32_t* __restrict__ tile_cnt) {
-    const int64_t pos = blockIdx.x * (int64_t)kTileBytes + threadIdx.x * 16;
-    const uint4 v = load16(text, n, pos);
-    int cnt = 0;
-#pragma unroll
-    for (int j = 0; j < 16; ++j) cnt += pos + j < n && byte_of(v, j) == '<';
-    int total;
-    block_prefix(cnt, &total);
-    if (threadIdx.x == 0) tile_cnt[blockIdx.x] = total;
+    mark_count_pass<'<'>(text, n, tile_cnt);
 }
 
 // ---- the tag table -----------------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void mzml_tags_kernel(const uint8_t* __restrict__ text, int64_t n, const int64_t* __restrict__ tile_base,
                                                         int64_t n_tiles, int32_t* __restrict__ tag_pos, int64_t cap_tags,
                                                         unsigned long long* __restrict__ meta) {
-    const int64_t pos = blockIdx.x * (int64_t)kTileBytes + threadIdx.x * 16;
-    const uint4 v = load16(text, n, pos);
-    int cnt = 0;
-#pragma unroll
-    for (int j = 0; j < 16; ++j) cnt += pos + j < n && byte_of(v, j) == '<';
-    int total;
-    int64_t tag = tile_base[blockIdx.x] + block_prefix(cnt, &total);
-#pragma unroll
-    for (int j = 0; j < 16; ++j)
-        if (pos + j < n && byte_of(v, j) == '<') {
-            if (tag < cap_tags) tag_pos[tag] = (int32_t)(pos + j);
-            ++tag;
-        }
-    if (blockIdx.x == 0 && threadIdx.x == 0) {
-        const int64_t tags = tile_base[n_tiles];
-        meta[META_TAGS] = (unsigned long long)tags;
-        if (tags <= cap_tags) tag_pos[tags] = (int32_t)n;
-        else atomicOr(&meta[META_FLAGS], (unsigned long long)FAL_MZML_FLAG_TAGS);
-    }
+    mark_table_pass<'<', 0, FAL_MZML_FLAG_TAGS>(text, n, tile_base, n_tiles, tag_pos, cap_tags, meta);
 }
 
 __device__ __forceinline__ int64_t indexed_tags(const unsigned long long* meta) {      // 0 when the table overflowed
@@ -269,15 +243,8 @@ using namespace fal;
 
 extern "C" int fal_mzml_index(fal_ctx* ctx, const uint8_t* text, int64_t n_bytes, int64_t* counts_out) {
     fal::CallScope _call(ctx);
-    FAL_REQUIRE(ctx && counts_out && n_bytes >= 0 && n_bytes < 0x7FFFFFFF, FAL_EINVAL, "fal_mzml_index: bad argument");
-    FAL_REQUIRE(n_bytes == 0 || (text && ((uintptr_t)text & 15) == 0), FAL_EINVAL, "fal_mzml_index: text NULL or not 16-byte aligned");
-    ctx->mzml = fal_ctx::MzmlIndex{};
-    for (int i = 0; i < 4; ++i) counts_out[i] = 0;
-    if (n_bytes == 0) {
-        ctx->mzml.text = text;
-        ctx->mzml.bytes = 0;
-        return FAL_OK;
-    }
+    FAL_TRY(text_index_begin("fal_mzml_index", ctx, &fal_ctx::mzml, text, n_bytes, counts_out));
+    if (n_bytes == 0) return FAL_OK;
     const int64_t n_tiles = ceil_div(n_bytes, kTileBytes);
     const int64_t cap_tags = n_bytes / 4 + 2, cap_spectra = n_bytes / 21 + 2, cap_blocks = ceil_div(cap_tags, kBlockTags);
     int32_t *tag_pos = nullptr, *spec = nullptr;
@@ -302,7 +269,7 @@ extern "C" int fal_mzml_index(fal_ctx* ctx, const uint8_t* text, int64_t n_bytes
     hipLaunchKernelGGL(mzml_tags_kernel, dim3((unsigned)n_tiles), dim3(256), 0, ctx->stream, text, n_bytes, tile_base, n_tiles, tag_pos,
                        cap_tags, meta);
     FAL_CHECK_HIP(hipGetLastError());
-    const unsigned grid = (unsigned)std::max<int64_t>(1, std::min<int64_t>(cap_blocks, (int64_t)ctx->num_cus * 16));
+    const unsigned grid = capped_grid(ctx, cap_tags, kBlockTags);
     hipLaunchKernelGGL(mzml_classify_kernel, dim3(grid), dim3(256), 0, ctx->stream, text, n_bytes, tag_pos, meta, recs, block_cnt);
     FAL_CHECK_HIP(hipGetLastError());
     ctx->release(SLOT_SORT);                                                    // (the first scan's block is no longer held here)
@@ -310,25 +277,15 @@ extern "C" int fal_mzml_index(fal_ctx* ctx, const uint8_t* text, int64_t n_bytes
     hipLaunchKernelGGL(mzml_spectra_kernel, dim3(grid), dim3(256), 0, ctx->stream, recs, meta, block_base, cap_blocks, cap_spectra,
                        spec_open, spec_close);
     FAL_CHECK_HIP(hipGetLastError());
-    unsigned long long* h = nullptr;
-    FAL_TRY(ctx->pinned_reserve(sizeof(unsigned long long) * META_WORDS, (void**)&h));
-    FAL_CHECK_HIP(hipMemcpyAsync(h, meta, sizeof(unsigned long long) * META_WORDS, hipMemcpyDeviceToHost, ctx->stream));
-    FAL_CHECK_HIP(hipStreamSynchronize(ctx->stream));
+    const unsigned long long* h = nullptr;
+    FAL_TRY(read_meta(ctx, meta, &h));
     const int64_t flags = (int64_t)h[META_FLAGS];
     FAL_REQUIRE(flags != 0 || (int64_t)h[META_SPECTRA] <= cap_spectra, FAL_EINTERNAL, "fal_mzml_index: more spectra than 21-byte slots");
     counts_out[0] = flags ? 0 : (int64_t)h[META_SPECTRA];
     counts_out[1] = flags ? 0 : (int64_t)h[META_INSIDE];
     counts_out[2] = flags;
     counts_out[3] = (int64_t)h[META_TAGS];
-    ctx->mzml.text = text;
-    ctx->mzml.bytes = n_bytes;
-    ctx->mzml.spectra = counts_out[0];
-    ctx->mzml.cap_tags = cap_tags;
-    ctx->mzml.cap_spectra = cap_spectra;
-    ctx->mzml.blocks[0] = tag_pos;
-    ctx->mzml.blocks[1] = recs;
-    ctx->mzml.blocks[2] = small;
-    ctx->mzml.blocks[3] = spec;
+    store_index(ctx->mzml, text, n_bytes, counts_out[0], 0, cap_tags, cap_spectra, tag_pos, recs, small, spec);
     return FAL_OK;
 }
 
@@ -337,12 +294,9 @@ extern "C" int fal_mzml_parse(fal_ctx* ctx, const uint8_t* text, int64_t n_bytes
                               double* retention_time, int64_t* arrays) {
     fal::CallScope _call(ctx);
     FAL_REQUIRE(ctx && n_spectra >= 0 && payload_cap >= 0, FAL_EINVAL, "fal_mzml_parse: bad argument");
-    const fal_ctx::MzmlIndex& ix = ctx->mzml;
-    bool mine = ix.bytes == n_bytes && ix.text == text && ix.spectra == n_spectra;
-    if (mine && n_bytes > 0)
-        mine = ix.blocks[0] && ix.blocks[0] == ctx->scratch[SLOT_MZML].ptr && ix.blocks[1] == ctx->scratch[SLOT_MZML2].ptr &&
-               ix.blocks[2] == ctx->scratch[SLOT_MZML3].ptr && ix.blocks[3] == ctx->scratch[SLOT_MZML4].ptr;
-    FAL_REQUIRE(mine, FAL_EINVAL, "fal_mzml_parse: not the text, length and spectrum count of the last fal_mzml_index of this context");
+    const fal_ctx::TextIndex& ix = ctx->mzml;
+    FAL_REQUIRE(matches(ctx, ix, SLOT_MZML, text, n_bytes, n_spectra), FAL_EINVAL,
+                "fal_mzml_parse: not the text, length and spectrum count of the last fal_mzml_index of this context");
     if (n_spectra == 0) return FAL_OK;
     FAL_REQUIRE(payload && payload_cap >= n_bytes + 16 * n_spectra && ((uintptr_t)payload & 7) == 0, FAL_EINVAL,
                 "fal_mzml_parse: payload NULL, not 8-byte aligned or smaller than n_bytes + 16 n_spectra");
@@ -363,7 +317,7 @@ extern "C" int fal_mzml_parse(fal_ctx* ctx, const uint8_t* text, int64_t n_bytes
                        spec_close, n_spectra, src, rlen, out);
     FAL_CHECK_HIP(hipGetLastError());
     FAL_TRY(device_scan_i32(ctx, rlen, n_spectra, offs, SLOT_SORT));
-    const unsigned grid = (unsigned)std::max<int64_t>(1, std::min<int64_t>(ceil_div(n_spectra, 4), (int64_t)ctx->num_cus * 16));
+    const unsigned grid = capped_grid(ctx, n_spectra, 4);
     hipLaunchKernelGGL(mzml_gather_kernel, dim3(grid), dim3(256), 0, ctx->stream, text, n_bytes, src, offs, n_spectra, payload, payload_cap,
                        out);
     FAL_CHECK_HIP(hipGetLastError());

@@ -1,6 +1,9 @@
-// Byte-streaming helpers shared by the text readers on the device (mgfparse.hip, mzmlscan.hip): 16-byte loads that stop at the
-// end of the text, a block-wide prefix sum and the copy of a byte range into an LDS tile.
+// What the text readers on the device (mgfparse.hip, mzmlscan.hip) share.  Device side: 16-byte loads that stop at the end of
+// the text, a block-wide prefix sum, the copy of a byte range into an LDS tile, and the two passes that build a text's mark
+// table (the positions of one byte value: the line starts of MGF, the '<' of mzML).  Host side (at the bottom): the index
+// handle fal_ctx::TextIndex that carries the tables from fal_*_index to fal_*_parse.
 #pragma once
+#include <algorithm>
 #include "common.h"
 
 namespace fal {
@@ -42,6 +45,107 @@ __device__ __forceinline__ void stage_bytes(const uint8_t* __restrict__ text, in
                                             int step) {
     const int64_t a0 = b0 & ~(int64_t)15;
     for (int64_t off = lane * 16; a0 + off < b1; off += step * 16) *reinterpret_cast<uint4*>(tile + off) = load16(text, n, a0 + off);
+}
+
+// ---- the mark table ----------------------------------------------------------------------------------------------------------------
+// Two walks over the text, 16 bytes per lane and kTileBytes per block of 256, with a device scan of the tile counts between
+// them (tile_base[0 .. n_tiles], the last entry the total).  Of the meta words both passes need two: meta[META_COUNT] = the
+// table's entries, whatever its capacity, and meta[META_FLAGS], where Flag is set when they exceed it.
+constexpr int kTileBytes = 4096;
+enum { META_COUNT = 0, META_FLAGS = 1, META_WORDS = 4 };
+
+// how many of the lane's 16 bytes v = load16(text, n, pos) are Mark
+template <char Mark>
+__device__ __forceinline__ int count_marks(const uint4 v, int64_t n, int64_t pos) {
+    int cnt = 0;
+#pragma unroll
+    for (int j = 0; j < 16; ++j) cnt += pos + j < n && byte_of(v, j) == Mark;
+    return cnt;
+}
+
+// first walk: tile_cnt[tile] = its marks
+template <char Mark>
+__device__ __forceinline__ void mark_count_pass(const uint8_t* __restrict__ text, int64_t n, int32_t* __restrict__ tile_cnt) {
+    const int64_t pos = blockIdx.x * (int64_t)kTileBytes + threadIdx.x * 16;
+    const uint4 v = load16(text, n, pos);
+    int total;
+    block_prefix(count_marks<Mark>(v, n, pos), &total);
+    if (threadIdx.x == 0) tile_cnt[blockIdx.x] = total;
+}
+
+// second walk: the table (i32, cap + 1 entries), closed by a sentinel behind its last entry.
+//   Shift 0: entry k = the position of mark k; `marks` entries; sentinel n          (a tag begins at its '<')
+//   Shift 1: entry 0 = 0, entry k + 1 = the byte behind mark k; `marks + 1` entries; sentinel n + 1   (a line begins behind a '\n')
+// More entries than cap: the table's first cap are written, the sentinel is not, and Flag is set.
+template <char Mark, int Shift, unsigned Flag>
+__device__ __forceinline__ void mark_table_pass(const uint8_t* __restrict__ text, int64_t n, const int64_t* __restrict__ tile_base,
+                                                int64_t n_tiles, int32_t* __restrict__ table, int64_t cap,
+                                                unsigned long long* __restrict__ meta) {
+    const int64_t pos = blockIdx.x * (int64_t)kTileBytes + threadIdx.x * 16;
+    const uint4 v = load16(text, n, pos);
+    int total;
+    int64_t k = tile_base[blockIdx.x] + block_prefix(count_marks<Mark>(v, n, pos), &total) + Shift;      // the lane's first entry
+#pragma unroll
+    for (int j = 0; j < 16; ++j)
+        if (pos + j < n && byte_of(v, j) == Mark) {
+            if (k < cap + Shift) table[k] = (int32_t)(pos + j + Shift);
+            ++k;
+        }
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        const int64_t entries = tile_base[n_tiles] + Shift;
+        if (Shift) table[0] = 0;
+        meta[META_COUNT] = (unsigned long long)entries;
+        if (entries <= cap) table[entries] = (int32_t)(n + Shift);
+        else atomicOr(&meta[META_FLAGS], (unsigned long long)Flag);
+    }
+}
+
+// ---- host side: the index handle -----------------------------------------------------------------------------------------------------
+// `who` is the entry point's name in the messages.
+
+// the opening of fal_*_index: argument checks, the handle and the counts reset; a zero-byte text is indexed by that alone
+inline int text_index_begin(const char* who, fal_ctx* ctx, fal_ctx::TextIndex fal_ctx::*which, const uint8_t* text, int64_t n_bytes,
+                            int64_t* counts_out) {
+    FAL_REQUIRE(ctx && counts_out && n_bytes >= 0 && n_bytes < 0x7FFFFFFF, FAL_EINVAL, "%s: bad argument", who);
+    FAL_REQUIRE(n_bytes == 0 || (text && ((uintptr_t)text & 15) == 0), FAL_EINVAL, "%s: text NULL or not 16-byte aligned", who);
+    fal_ctx::TextIndex& ix = ctx->*which;
+    ix = fal_ctx::TextIndex{};
+    for (int i = 0; i < 4; ++i) counts_out[i] = 0;
+    if (n_bytes == 0) {
+        ix.text = text;
+        ix.bytes = 0;
+    }
+    return FAL_OK;
+}
+
+// the META_WORDS meta words on the host, through the pinned buffer; synchronises
+inline int read_meta(fal_ctx* ctx, const unsigned long long* meta, const unsigned long long** host) {
+    unsigned long long* h = nullptr;
+    FAL_TRY(ctx->pinned_reserve(sizeof(unsigned long long) * META_WORDS, (void**)&h));
+    FAL_CHECK_HIP(hipMemcpyAsync(h, meta, sizeof(unsigned long long) * META_WORDS, hipMemcpyDeviceToHost, ctx->stream));
+    FAL_CHECK_HIP(hipStreamSynchronize(ctx->stream));
+    *host = h;
+    return FAL_OK;
+}
+
+inline void store_index(fal_ctx::TextIndex& ix, const void* text, int64_t n_bytes, int64_t spectra, int64_t extra, int64_t cap_table,
+                        int64_t cap_spectra, const void* b0, const void* b1, const void* b2, const void* b3) {
+    ix = fal_ctx::TextIndex{text, n_bytes, spectra, extra, cap_table, cap_spectra, {b0, b1, b2, b3}};
+}
+
+// is `ix` the index of this text, length and spectrum count, its tables still in the slots first_slot .. first_slot + 3?
+inline bool matches(const fal_ctx* ctx, const fal_ctx::TextIndex& ix, int first_slot, const void* text, int64_t n_bytes, int64_t n_spectra) {
+    bool mine = ix.bytes == n_bytes && ix.text == text && ix.spectra == n_spectra;
+    if (mine && n_bytes > 0) {
+        mine = ix.blocks[0] != nullptr;
+        for (int i = 0; i < 4; ++i) mine = mine && ix.blocks[i] == ctx->scratch[first_slot + i].ptr;
+    }
+    return mine;
+}
+
+// blocks of a grid-stride kernel over `items`, `per_block` to a block: at least one, at most 16 a compute unit
+inline unsigned capped_grid(const fal_ctx* ctx, int64_t items, int per_block) {
+    return (unsigned)std::max<int64_t>(1, std::min<int64_t>(ceil_div(items, per_block), (int64_t)ctx->num_cus * 16));
 }
 
 }  // namespace fal

@@ -330,12 +330,26 @@ class Context:
                                         self._p(status)), "fal_decode_peaks")
         return indptr, mz[:nnz], it[:nnz], status[:n]
 
+    def _text_to_dev(self, text):
+        """bytes, bytearray, memoryview, uint8 array or uint8 tensor -> uint8 device tensor"""
+        torch = _torch()
+        if isinstance(text, torch.Tensor):
+            return self.to_dev(text, torch.uint8)
+        raw = np.frombuffer(text, np.uint8) if isinstance(text, (bytes, bytearray, memoryview)) else np.asarray(text, np.uint8)
+        if not raw.flags.writeable:
+            raw = raw.copy()                     # (immutable bytes: torch takes writable arrays only)
+        return self.to_dev(raw) if len(raw) else self.empty((0,), torch.uint8)
+
+    def _text_index(self, name, d_text):
+        """`fal_mgf_index` / `fal_mzml_index` (`name`) of a uint8 device tensor -> its four counts"""
+        counts = (C.c_int64 * 4)()
+        check(getattr(self.lib, name)(self._h, self._p(d_text) if d_text.numel() else None, d_text.numel(), counts), name)
+        return tuple(int(c) for c in counts)
+
     def mgf_index(self, d_text):
         """`fal_mgf_index` of MGF text on the device (uint8 tensor) -> (spectra, peaks, `_lib.MGF_FLAG_*` bits, lines).
         Synchronises once.  The tables stay in the context for the `mgf_parse` of the same tensor."""
-        counts = (C.c_int64 * 4)()
-        check(self.lib.fal_mgf_index(self._h, self._p(d_text) if d_text.numel() else None, d_text.numel(), counts), "fal_mgf_index")
-        return tuple(int(c) for c in counts)
+        return self._text_index("fal_mgf_index", d_text)
 
     def mgf_parse(self, d_text, n: int, nnz: int):
         """`fal_mgf_parse` behind `mgf_index` of the same tensor -> device tensors indptr i64[n+1], mz f64[nnz], intensity
@@ -359,14 +373,7 @@ class Context:
         `charge` i32, `has_charge` bool, `retention_time` f64 (-1 when absent), `title` / `span` i64[n, 2] (byte ranges of the
         title value and of the spectrum), `status` i32 (0, or `_lib.MGF_ST_HOST`: the host reader decides that spectrum; its
         slot has the right size and placeholder values).  DESIGN.md "MGF on the device" states the grammar."""
-        torch = _torch()
-        if isinstance(text, torch.Tensor):
-            d_text = self.to_dev(text, torch.uint8)
-        else:
-            raw = np.frombuffer(text, np.uint8) if isinstance(text, (bytes, bytearray, memoryview)) else np.asarray(text, np.uint8)
-            if not raw.flags.writeable:
-                raw = raw.copy()                 # (immutable bytes: torch takes writable arrays only)
-            d_text = self.to_dev(raw) if len(raw) else self.empty((0,), torch.uint8)
+        d_text = self._text_to_dev(text)
         n, nnz, flags, lines = self.mgf_index(d_text)
         if flags:
             return dict(flags=flags, lines=lines)
@@ -378,9 +385,7 @@ class Context:
     def mzml_index(self, d_text):
         """`fal_mzml_index` of mzML text on the device (uint8 tensor) -> (spectra, tags inside spectra, `_lib.MZML_FLAG_*` bits,
         tags).  Synchronises once.  The tables stay in the context for the `mzml_parse` of the same tensor."""
-        counts = (C.c_int64 * 4)()
-        check(self.lib.fal_mzml_index(self._h, self._p(d_text) if d_text.numel() else None, d_text.numel(), counts), "fal_mzml_index")
-        return tuple(int(c) for c in counts)
+        return self._text_index("fal_mzml_index", d_text)
 
     def mzml_parse(self, d_text, n: int):
         """`fal_mzml_parse` behind `mzml_index` of the same tensor -> device tensors payload u8[n_bytes + 16 n], status i32[n],
@@ -404,14 +409,7 @@ class Context:
         `precursor_mz` f64, `charge` i32 (0: none), `retention_time` f64 (-1 when absent), `arrays` i64[2 n, 4] (rows 2 s and
         2 s + 1: the m/z and the intensity array of spectrum s for `decode_peaks`; zeros unless the status is OK), and `tags`,
         `inside` (tags, and tags inside spectra).  DESIGN.md "mzML on the device" states the grammar."""
-        torch = _torch()
-        if isinstance(text, torch.Tensor):
-            d_text = self.to_dev(text, torch.uint8)
-        else:
-            raw = np.frombuffer(text, np.uint8) if isinstance(text, (bytes, bytearray, memoryview)) else np.asarray(text, np.uint8)
-            if not raw.flags.writeable:
-                raw = raw.copy()                 # (immutable bytes: torch takes writable arrays only)
-            d_text = self.to_dev(raw) if len(raw) else self.empty((0,), torch.uint8)
+        d_text = self._text_to_dev(text)
         n, inside, flags, tags = self.mzml_index(d_text)
         if flags:
             return dict(flags=flags, tags=tags)

@@ -69,19 +69,23 @@ def have_compiler() -> bool:
     return _compiler() is not None
 
 
-def build(tmp_dir, extra_flags=()):
-    """compile the shim into `tmp_dir` -> ctypes library with argument types set"""
+def compile_shim(tmp_dir, name, source, extra_flags=()):
+    """`source` written to `tmp_dir`/`name`.cpp and compiled into lib`name`.so with the host build's flags -> ctypes library"""
     cc = _compiler()
     assert cc is not None, "no host C++ compiler and no hipcc"
-    argv, _ = cc
-    src = os.path.join(str(tmp_dir), "host_shim.cpp")
-    so = os.path.join(str(tmp_dir), "libhost_shim.so")
+    src = os.path.join(str(tmp_dir), name + ".cpp")
+    so = os.path.join(str(tmp_dir), "lib" + name + ".so")
     with open(src, "w") as f:
-        f.write(SHIM)
-    cmd = argv + ["-O1", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-I", CSRC, *extra_flags, src, "-o", so]
+        f.write(source)
+    cmd = cc[0] + ["-O1", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-I", CSRC, *extra_flags, src, "-o", so]
     r = subprocess.run(cmd, capture_output=True, text=True)
     assert r.returncode == 0, f"{' '.join(cmd)}\n{r.stderr[-4000:]}"
-    lib = C.CDLL(so)
+    return C.CDLL(so)
+
+
+def build(tmp_dir, extra_flags=()):
+    """compile the shim into `tmp_dir` -> ctypes library with argument types set"""
+    lib = compile_shim(tmp_dir, "host_shim", SHIM, extra_flags)
     p = C.c_void_p
     lib.t_max_comp.restype = C.c_int
     lib.t_pair_scores.argtypes = [p, p, p, C.c_int64, C.c_double, p, p, p]

@@ -2,12 +2,10 @@
 C++ compiler behind `extern "C"` entry points.  Compiler discovery and flags as in tests/hostbuild.py (`-ffp-contract=off`:
 the float32 difference and division must not fuse)."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 
-from tests.hostbuild import CSRC, _compiler, have_compiler  # noqa: F401
+from tests.hostbuild import compile_shim, have_compiler  # noqa: F401
 
 SHIM = r"""
 #include <stdint.h>
@@ -95,17 +93,7 @@ int t_assign(const float* q_mz, const float* q_it, const int64_t* q_ptr, const f
 
 def build(tmp_dir, extra_flags=()):
     """compile the shim into `tmp_dir` -> ctypes library with argument types set"""
-    cc = _compiler()
-    assert cc is not None, "no host C++ compiler and no hipcc"
-    argv, _ = cc
-    src = os.path.join(str(tmp_dir), "assign_shim.cpp")
-    so = os.path.join(str(tmp_dir), "libassign_shim.so")
-    with open(src, "w") as f:
-        f.write(SHIM)
-    cmd = argv + ["-O1", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-I", CSRC, *extra_flags, src, "-o", so]
-    r = subprocess.run(cmd, capture_output=True, text=True)
-    assert r.returncode == 0, f"{' '.join(cmd)}\n{r.stderr[-4000:]}"
-    lib = C.CDLL(so)
+    lib = compile_shim(tmp_dir, "assign_shim", SHIM, extra_flags)
     p = C.c_void_p
     lib.t_candidates.argtypes = [p, p, p, p, C.c_int64, C.c_double, C.c_int, C.c_int, C.c_double, p]
     lib.t_candidates.restype = None

@@ -3,12 +3,10 @@ C++ compiler behind one `extern "C"` entry point that pools, sorts (by the heade
 header's functions.  Compiler discovery and flags as in tests/hostbuild.py (`-ffp-contract=off`: products and sums must not
 fuse)."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 
-from tests.hostbuild import CSRC, _compiler, have_compiler  # noqa: F401
+from tests.hostbuild import compile_shim, have_compiler  # noqa: F401
 
 SHIM = r"""
 #include <stdint.h>
@@ -80,17 +78,7 @@ int64_t t_consensus(const float* mz, const float* it, const int64_t* ptr, int64_
 
 def build(tmp_dir, extra_flags=()):
     """compile the shim into `tmp_dir` -> ctypes library with argument types set"""
-    cc = _compiler()
-    assert cc is not None, "no host C++ compiler and no hipcc"
-    argv, _ = cc
-    src = os.path.join(str(tmp_dir), "consensus_shim.cpp")
-    so = os.path.join(str(tmp_dir), "libconsensus_shim.so")
-    with open(src, "w") as f:
-        f.write(SHIM)
-    cmd = argv + ["-O1", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-I", CSRC, *extra_flags, src, "-o", so]
-    r = subprocess.run(cmd, capture_output=True, text=True)
-    assert r.returncode == 0, f"{' '.join(cmd)}\n{r.stderr[-4000:]}"
-    lib = C.CDLL(so)
+    lib = compile_shim(tmp_dir, "consensus_shim", SHIM, extra_flags)
     p = C.c_void_p
     lib.t_cons_lds_peaks.restype = C.c_int
     lib.t_consensus.argtypes = [p, p, p, C.c_int64, p, p, C.c_int64, C.c_double, C.c_double, p, p, p, p]

@@ -2,12 +2,10 @@
 fast form) for the CPU tests: the header the kernels include, compiled by the host C++ compiler behind `extern "C"` entry points
 (`tests/hostbuild.py`'s compiler choice and flags, `-ffp-contract=off` included)."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 
-from tests.hostbuild import CSRC, _compiler, _p, have_compiler  # noqa: F401
+from tests.hostbuild import _p, compile_shim, have_compiler  # noqa: F401
 
 SHIM = r"""
 #include <stdint.h>
@@ -59,16 +57,7 @@ KEYS = {0: None, 1: "title", 2: "pepmass", 3: "charge", 4: "rtinseconds"}
 
 def build(tmp_dir):
     """compile the shim into `tmp_dir` -> ctypes library with argument types set"""
-    cc = _compiler()
-    assert cc is not None, "no host C++ compiler and no hipcc"
-    src = os.path.join(str(tmp_dir), "mgf_shim.cpp")
-    so = os.path.join(str(tmp_dir), "libmgf_shim.so")
-    with open(src, "w") as f:
-        f.write(SHIM)
-    cmd = cc[0] + ["-O1", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-I", CSRC, src, "-o", so]
-    r = subprocess.run(cmd, capture_output=True, text=True)
-    assert r.returncode == 0, f"{' '.join(cmd)}\n{r.stderr[-4000:]}"
-    lib = C.CDLL(so)
+    lib = compile_shim(tmp_dir, "mgf_shim", SHIM)
     p = C.c_void_p
     lib.t_max_line.restype = C.c_int
     lib.t_parse_doubles.argtypes = [p, p, C.c_int64, p, p]

@@ -4,12 +4,10 @@ host loop -- find every '<', classify every tag, pair the spectrum markers, walk
 (`tests/hostbuild.py`'s compiler choice and flags).  `scan` returns what `Context.scan_mzml` returns, the payload as a host array;
 `FakeContext` stands in for a device context in `mzml_io.read_chunks_device`."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 
-from tests.hostbuild import CSRC, _compiler, _p, have_compiler  # noqa: F401
+from tests.hostbuild import _p, compile_shim, have_compiler  # noqa: F401
 
 SHIM = r"""
 #include <stdint.h>
@@ -97,16 +95,7 @@ OK, SKIP, HOST = 0, 1, 2
 
 def build(tmp_dir):
     """compile the shim into `tmp_dir` -> ctypes library with argument types set"""
-    cc = _compiler()
-    assert cc is not None, "no host C++ compiler and no hipcc"
-    src = os.path.join(str(tmp_dir), "mzml_shim.cpp")
-    so = os.path.join(str(tmp_dir), "libmzml_shim.so")
-    with open(src, "w") as f:
-        f.write(SHIM)
-    cmd = cc[0] + ["-O1", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-I", CSRC, src, "-o", so]
-    r = subprocess.run(cmd, capture_output=True, text=True)
-    assert r.returncode == 0, f"{' '.join(cmd)}\n{r.stderr[-4000:]}"
-    lib = C.CDLL(so)
+    lib = compile_shim(tmp_dir, "mzml_shim", SHIM)
     lib.t_mzml_scan.argtypes = [C.c_void_p, C.c_int64, C.c_int64] + [C.c_void_p] * 8
     lib.t_mzml_scan.restype = None
     return lib

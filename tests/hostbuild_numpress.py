@@ -2,12 +2,10 @@
 upper-bound form for the CPU tests, as `hostbuild.py` builds `inflate.h`: the headers the kernels include, compiled with the
 host C++ compiler into a small shared object behind `extern "C"` entry points.  `-ffp-contract=off` as in the library's build."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 
-from tests.hostbuild import CSRC, _compiler, _p, have_compiler  # noqa: F401
+from tests.hostbuild import _p, compile_shim, have_compiler  # noqa: F401
 
 SHIM = r"""
 #include <stdint.h>
@@ -35,16 +33,7 @@ GUARD = 8                     # float64 slots behind the output
 
 def build(tmp_dir):
     """compile the shim into `tmp_dir` -> ctypes library with argument types set"""
-    cc = _compiler()
-    assert cc is not None, "no host C++ compiler and no hipcc"
-    src = os.path.join(str(tmp_dir), "numpress_shim.cpp")
-    so = os.path.join(str(tmp_dir), "libnumpress_shim.so")
-    with open(src, "w") as f:
-        f.write(SHIM)
-    cmd = cc[0] + ["-O1", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-I", CSRC, src, "-o", so]
-    r = subprocess.run(cmd, capture_output=True, text=True)
-    assert r.returncode == 0, f"{' '.join(cmd)}\n{r.stderr[-4000:]}"
-    lib = C.CDLL(so)
+    lib = compile_shim(tmp_dir, "numpress_shim", SHIM)
     p = C.c_void_p
     lib.t_numpress.argtypes = [C.c_int64, p, C.c_int64, p, C.c_int64, p]
     lib.t_numpress.restype = C.c_int
