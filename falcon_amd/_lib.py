@@ -21,6 +21,9 @@ PEAK_STATUS = {1: "bad descriptor", 2: "bad base64", 4: "bad zlib header", 8: "b
                256: "bad MS-Numpress stream"}
 # fal_mgf_index / fal_mgf_parse: flags of a text the host reader has to read, and the per-spectrum status (include/falcon_hip.h)
 MGF_FLAG_BYTES, MGF_FLAG_LINES, MGF_ST_HOST = 1, 2, 1
+# fal_mgf_write: the most bytes one number takes (csrc/mgfwrite.h kMgfNumMax)
+MGF_NUM_MAX = 23
+FAL_EINVAL = -1
 # fal_mzml_index / fal_mzml_parse: the same for mzML text (include/falcon_hip.h)
 MZML_FLAG_STRUCT, MZML_FLAG_MARKUP, MZML_FLAG_TAGS = 1, 2, 4
 MZML_ST_OK, MZML_ST_SKIP, MZML_ST_HOST = 0, 1, 2
@@ -115,6 +118,10 @@ _SIGNATURES = {
     "fal_mgf_index": ([c_void_p, c_void_p, c_int64, P(c_int64)], c_int),
     "fal_mgf_parse": ([c_void_p, c_void_p, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                        c_void_p, c_void_p, c_void_p, c_void_p], c_int),
+    "fal_mgf_write_sizes": ([c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_void_p,
+                             c_void_p, c_void_p, c_int64, c_void_p, c_void_p, P(c_int64)], c_int),
+    "fal_mgf_write": ([c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_void_p,
+                       c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int64, c_void_p, c_int64, c_void_p], c_int),
     "fal_mzml_index": ([c_void_p, c_void_p, c_int64, P(c_int64)], c_int),
     "fal_mzml_parse": ([c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                         c_void_p, c_void_p], c_int),

@@ -846,6 +846,36 @@ def consensus_spectra(dataset, labels, medoids, fragment_tol: float, min_fractio
     return indptr.cpu().numpy(), mz.cpu().numpy(), intensity.cpu().numpy(), status.cpu().numpy()
 
 
+def write_representatives(filename: str, dataset: SpectrumDataset, medoids, cluster_ids, identifiers, charge: int = 0,
+                          consensus=None, pipeline: Optional[ClusterPipeline] = None) -> str:
+    """Write the representatives of `dataset`'s clusters to the MGF file `filename`, formatted on the device
+    (`fal_mgf_write_sizes` / `fal_mgf_write`; DESIGN.md "MGF out of the device"): byte for byte the file
+    `ms_io.write_spectra` writes for the same entries.  Entry c carries the peaks of row medoids[c] -- or, with `consensus`
+    (indptr, mz, intensity as `consensus_spectra` returns them), the consensus peaks of cluster c -- the precursor m/z and
+    retention time of row medoids[c], TITLE=identifiers[c] (a str array, one per cluster), CLUSTER=cluster_ids[c] and, unless
+    `charge` is 0, CHARGE=`charge`.  -> "device", or "host" where the titles are outside what the device path mirrors
+    (`mgf_io.title_blob`) and the host writer wrote the file."""
+    global _default_pipeline
+    from ..ms_io import ms_io
+    pipe = pipeline or _default_pipeline
+    if pipe is None:
+        pipe = _default_pipeline = ClusterPipeline()
+    if dataset.retention_time is None:
+        raise ValueError("write_representatives: the dataset has no retention times")
+    ctx = pipe.ctx
+    import torch
+    m = ctx.to_dev(medoids, torch.int64)
+    n = int(m.shape[0])
+    if consensus is None:
+        indptr, mz, intensity, rows = dataset.indptr, dataset.mz, dataset.intensity, m.to(torch.int32)
+    else:
+        indptr, mz, intensity = consensus
+        rows = np.arange(n, dtype=np.int32)
+    pmz, rt = ctx.to_dev(dataset.precursor_mz, torch.float32)[m], ctx.to_dev(dataset.retention_time, torch.float32)[m]
+    return ms_io.write_representatives(filename, ctx, mz, intensity, indptr, rows, pmz, rt, np.full(n, int(charge), np.int32),
+                                       cluster_ids, np.asarray(identifiers, dtype=str))
+
+
 def assign_to_library(queries: SpectrumDataset, library: SpectrumDataset, eps: float, precursor_tol: float, mode: str,
                       rt_tol: Optional[float], fragment_tol: float, min_matched_peaks: int,
                       pipeline: Optional[ClusterPipeline] = None):

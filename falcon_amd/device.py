@@ -382,6 +382,81 @@ class Context:
         return dict(flags=0, lines=lines, indptr=indptr, mz=mz, intensity=it, precursor_mz=pmz, charge=charge,
                     has_charge=has_charge.astype(bool), retention_time=rt, title=title, span=span, status=status)
 
+    def _mgf_entries(self, mz, intensity, indptr, rows, precursor_mz, retention_time, charge, cluster, title, title_ptr):
+        """the writer's columns as device tensors of the entry points' types, checked against each other"""
+        torch = _torch()
+        cols = dict(mz=self.to_dev(mz, torch.float32), intensity=self.to_dev(intensity, torch.float32),
+                    indptr=self.to_dev(indptr, torch.int64), rows=self.to_dev(rows, torch.int32),
+                    precursor_mz=self.to_dev(precursor_mz, torch.float32), retention_time=self.to_dev(retention_time, torch.float32),
+                    charge=self.to_dev(charge, torch.int32), cluster=self.to_dev(cluster, torch.int64),
+                    title=self._text_to_dev(title), title_ptr=self.to_dev(title_ptr, torch.int64))
+        n = int(cols["rows"].shape[0])
+        for name in ("precursor_mz", "retention_time", "charge", "cluster"):
+            if cols[name].shape[0] != n:
+                raise ValueError(f"format_mgf: {name} has {cols[name].shape[0]} entries for {n} rows")
+        if cols["title_ptr"].shape[0] != n + 1 or cols["indptr"].shape[0] < 1 or cols["mz"].shape != cols["intensity"].shape:
+            raise ValueError("format_mgf: title_ptr needs one entry more than rows, indptr at least one, mz and intensity the same size")
+        return cols
+
+    def _mgf_entry_args(self, c, with_title: bool):
+        head = [self._p(c["mz"]), self._p(c["intensity"]), self._p(c["indptr"]), c["indptr"].shape[0] - 1, c["mz"].shape[0],
+                self._p(c["rows"]), c["rows"].shape[0], self._p(c["precursor_mz"]), self._p(c["retention_time"]), self._p(c["charge"]),
+                self._p(c["cluster"])]
+        return head + ([self._p(c["title"])] if with_title else []) + [self._p(c["title_ptr"]), c["title"].numel()]
+
+    def mgf_write_sizes(self, cols):
+        """`fal_mgf_write_sizes` of `_mgf_entries` columns -> (sizes i64[n], offsets i64[n + 1] on the device, total bytes).
+        Synchronises once."""
+        torch = _torch()
+        n = int(cols["rows"].shape[0])
+        sizes, offsets = self.empty((max(n, 1),), torch.int64), self.empty((n + 1,), torch.int64)
+        total = C.c_int64(0)
+        check(self.lib.fal_mgf_write_sizes(self._h, *self._mgf_entry_args(cols, False), self._p(sizes), self._p(offsets),
+                                           C.byref(total)), "fal_mgf_write_sizes")
+        return sizes[:n], offsets, int(total.value)
+
+    def mgf_write(self, cols, offsets, first: int, last: int, out, host_out=None):
+        """`fal_mgf_write`: the text of entries [first, last) into the uint8 device tensor (or view) `out`; `host_out`: a pinned
+        uint8 host tensor of the same size that receives a copy.  Synchronises once.  FalconHipError (code `_lib.FAL_EINVAL`,
+        nothing written) when `out` is too small."""
+        if host_out is not None and (not host_out.is_pinned() or host_out.numel() != out.numel()):
+            raise ValueError("mgf_write: host_out must be pinned and of out's size")
+        check(self.lib.fal_mgf_write(self._h, *self._mgf_entry_args(cols, True), self._p(offsets), int(first), int(last),
+                                     self._p(out) if out.numel() else None, out.numel(),
+                                     self._p(host_out) if host_out is not None and out.numel() else None), "fal_mgf_write")
+
+    def format_mgf(self, mz, intensity, indptr, rows, precursor_mz, retention_time, charge, cluster, title, title_ptr,
+                   max_bytes: Optional[int] = None, copy: bool = True):
+        """The MGF text of n entries, byte for byte what `mgf_io.write_spectra` writes for them (DESIGN.md "MGF out of the
+        device"), as a generator of uint8 host arrays that together are the file.  Peaks CSR mz / intensity f32, indptr i64;
+        rows i32[n]: the CSR row of entry k (any order, repeats allowed); precursor_mz / retention_time f32[n], charge i32[n]
+        (0: no CHARGE line), cluster i64[n]; title: the entries' encoded title bytes, title_ptr i64[n + 1] their offsets.
+        Arrays or device tensors.  Chunks are cut on entry boundaries at about `max_bytes` (default
+        `mgf_io.DEFAULT_CHUNK_BYTES`); one larger entry grows its chunk.  Every chunk is formatted into one device buffer and
+        copied through one pinned host buffer, with one stream synchronisation; `copy=False` yields views of that pinned
+        buffer, valid until the next chunk is asked for."""
+        torch = _torch()
+        if max_bytes is None:
+            from .ms_io.mgf_io import DEFAULT_CHUNK_BYTES as max_bytes
+        cols = self._mgf_entries(mz, intensity, indptr, rows, precursor_mz, retention_time, charge, cluster, title, title_ptr)
+        n = int(cols["rows"].shape[0])
+        if n == 0:
+            return
+        _, offsets, total = self.mgf_write_sizes(cols)
+        off = offsets.cpu().numpy()
+        cuts = [0]                                   # (a loop over the chunks, not over the entries)
+        while cuts[-1] < n:
+            last = int(np.searchsorted(off, off[cuts[-1]] + max(int(max_bytes), 1), side="right")) - 1
+            cuts.append(min(max(last, cuts[-1] + 1), n))
+        cap = int(max(off[b] - off[a] for a, b in zip(cuts[:-1], cuts[1:])))
+        d_out = self.empty((max(cap, 1),), torch.uint8)
+        h_out = torch.empty((max(cap, 1),), dtype=torch.uint8, pin_memory=True)
+        for a, b in zip(cuts[:-1], cuts[1:]):
+            need = int(off[b] - off[a])
+            self.mgf_write(cols, offsets, a, b, d_out[:need], h_out[:need])
+            chunk = h_out[:need].numpy()
+            yield chunk.copy() if copy else chunk
+
     def mzml_index(self, d_text):
         """`fal_mzml_index` of mzML text on the device (uint8 tensor) -> (spectra, tags inside spectra, `_lib.MZML_FLAG_*` bits,
         tags).  Synchronises once.  The tables stay in the context for the `mzml_parse` of the same tensor."""

@@ -88,6 +88,7 @@ def _run(args) -> int:
         logger.debug(line)
     logger.debug("mgf_reader = %s", config.mgf_reader)       # (no output depends on it: not an option line of the CSV header)
     logger.debug("mzml_reader = %s", config.mzml_reader)     # (the same)
+    logger.debug("mgf_writer = %s", config.mgf_writer)       # (the same)
     if config.distributed:
         return _run_distributed()
 
@@ -120,7 +121,7 @@ def _run(args) -> int:
             config.precursor_tol[1], config.rt_tol, config.fragment_tol, config.batch_size, ann=ann, pipeline=pipe)
         current_label = _emit_charge(part, charge, labels, medoids, current_label, rows_all, representatives,
                                      _consensus(pipe.ctx, part, charge, labels, medoids))
-    _write_outputs(rows_all, representatives)
+    _write_outputs(rows_all, representatives, pipe.ctx)
     if rm_work_dir:
         shutil.rmtree(config.work_dir)
     return 0
@@ -252,8 +253,8 @@ def _consensus(ctx, part, charge, labels, medoids):
 
 
 def _emit_charge(part, charge, labels, medoids, current_label, rows_all, representatives, consensus=None) -> int:
-    """one charge's labels (by row of its partition) and medoid rows -> CSV rows and representatives; -> the next label.
-    consensus (indptr, mz, intensity by cluster): the representatives' peaks; everything else stays the medoid's"""
+    """one charge's labels (by row of its partition) and medoid rows -> CSV rows and the charge's block of representatives; ->
+    the next label.  consensus (indptr, mz, intensity by cluster): the representatives' peaks; everything else stays the medoid's"""
     n = len(part["precursor_mz"])
     labels = labels + current_label                                                            # falcon.py:189-193
     current_label = int(labels.max()) + 1
@@ -262,35 +263,69 @@ def _emit_charge(part, charge, labels, medoids, current_label, rows_all, represe
         rows_all.append((str(part["filename"][i]), str(part["identifier"][i]), charge,
                          np.float32(part["precursor_mz"][i]), np.float32(part["retention_time"][i]), int(labels[i])))
     if config.export_representatives:                                                          # falcon.py:198-203
-        ip = part["indptr"]
-        for c, m in enumerate(medoids):
-            representatives.append({
-                "identifier": str(part["identifier"][m]), "precursor_mz": float(part["precursor_mz"][m]),
-                "precursor_charge": None if charge == "None" else int(charge),
-                "retention_time": float(part["retention_time"][m]),
-                "mz": part["mz"][ip[m]:ip[m + 1]] if consensus is None else consensus[1][consensus[0][c]:consensus[0][c + 1]],
-                "intensity": (part["intensity"][ip[m]:ip[m + 1]] if consensus is None
-                              else consensus[2][consensus[0][c]:consensus[0][c + 1]]),
-                "cluster": int(labels[m])})
+        # one block of arrays per charge: the peaks CSR (the partition's, with the medoid rows; or the consensus, one row per
+        # cluster) and the medoids' columns
+        m = np.asarray(medoids, np.int64)
+        if consensus is None:
+            indptr, mz, intensity, rows = part["indptr"], part["mz"], part["intensity"], m.astype(np.int32)
+        else:
+            indptr, mz, intensity = consensus
+            rows = np.arange(len(m), dtype=np.int32)
+        representatives.append(dict(
+            indptr=indptr, mz=mz, intensity=intensity, rows=rows, identifier=part["identifier"][m],
+            precursor_mz=part["precursor_mz"][m], retention_time=part["retention_time"][m],
+            charge=None if charge == "None" else int(charge), cluster=labels[m].astype(np.int64)))
     return current_label
 
 
-def _write_outputs(rows_all, representatives) -> None:
-    """falcon.py:206-244: the CSV (+ the MGF of representatives), written on two threads"""
+def _block_columns(b):
+    """a block of `_emit_charge` -> the columns `mgf_io.write_representatives` / `mgf_io.entry_dicts` take in front of the titles"""
+    return (b["mz"], b["intensity"], b["indptr"], b["rows"], b["precursor_mz"], b["retention_time"],
+            np.full(len(b["rows"]), b["charge"] or 0, np.int32), b["cluster"])
+
+
+def _representative_spectra(blocks):
+    """the blocks of `_emit_charge` -> the dicts the host writer takes, in the blocks' order"""
+    for b in blocks:
+        yield from mgf_io.entry_dicts(*_block_columns(b), b["identifier"])
+
+
+def _device_writable(blocks) -> bool:
+    """the device writer formats float32 columns and int32 charges: the partitions' own types"""
+    f32 = all(np.asarray(b[c]).dtype == np.float32 for b in blocks for c in ("mz", "intensity", "precursor_mz", "retention_time"))
+    return f32 and all(b["charge"] is None or (b["charge"] != 0 and abs(b["charge"]) < 2 ** 31) for b in blocks)
+
+
+def _write_representatives(filename: str, blocks, ctx) -> None:
+    """the MGF of representatives: block after block through the device writer (`--mgf_writer device`, with `ctx`), or every
+    entry through the host writer (also where a title is outside what the device path mirrors); the same bytes"""
+    blobs = None
+    if config.mgf_writer == "device" and ctx is not None and _device_writable(blocks):
+        blobs = [mgf_io.title_blob(b["identifier"]) for b in blocks]
+    if blobs is None or any(t is None for t in blobs):
+        ms_io.write_spectra(filename, _representative_spectra(blocks))
+        return
+    open(filename, "wb").close()
+    for b, titles in zip(blocks, blobs):
+        ms_io.write_representatives(filename, ctx, *_block_columns(b), titles, append=True)
+
+
+def _write_outputs(rows_all, representatives, ctx=None) -> None:
+    """falcon.py:206-244: the CSV on a worker thread, the MGF of representatives on the calling one (the device writer runs on
+    `ctx`; a new thread would not inherit the device)"""
     rows_all.sort(key=lambda r: (_natural_key(r[0]), _natural_key(r[1])))                      # falcon.py:206-208
     n_clusters = len({r[5] for r in rows_all})
     logger.info("Export cluster assignments of %d spectra to %d unique clusters to output file %s",
                 len(rows_all), n_clusters, f"{config.output_filename}.csv")
     csv_worker = threading.Thread(target=_write_cluster_info, args=(rows_all,), daemon=True)
     csv_worker.start()
-    if config.export_representatives:
-        logger.info("Export %d cluster representative spectra to output file %s", len(representatives),
-                    f"{config.output_filename}.mgf")
-        mgf_worker = threading.Thread(target=ms_io.write_spectra,
-                                      args=(f"{config.output_filename}.mgf", representatives), daemon=True)
-        mgf_worker.start()
-        mgf_worker.join()
-    csv_worker.join()
+    try:
+        if config.export_representatives:
+            logger.info("Export %d cluster representative spectra to output file %s",
+                        sum(len(b["rows"]) for b in representatives), f"{config.output_filename}.mgf")
+            _write_representatives(f"{config.output_filename}.mgf", representatives, ctx)
+    finally:
+        csv_worker.join()
 
 
 def _run_distributed() -> int:
@@ -355,19 +390,21 @@ def _run_distributed() -> int:
             runner.close()
         if rank == 0:
             rows_all, current_label, representatives = [], 0, []
-            cons_ctx = None
-            if config.representatives == "consensus":     # a context of rank 0's own, as for the preparation of the partitions
+            # a context of rank 0's own for the consensus and for the device writer, as for the preparation of the partitions
+            out_ctx = None
+            if config.export_representatives and (config.representatives == "consensus" or config.mgf_writer == "device"):
                 from .device import Context
-                cons_ctx = Context(device)
+                out_ctx = Context(device)
             try:
                 for charge, part, (labels, medoids) in zip(charges, parts, merged):
                     if len(labels):
-                        cons = _consensus(cons_ctx, part, charge, labels, medoids) if cons_ctx is not None else None
+                        cons = (_consensus(out_ctx, part, charge, labels, medoids)
+                                if out_ctx is not None and config.representatives == "consensus" else None)
                         current_label = _emit_charge(part, charge, labels, medoids, current_label, rows_all, representatives, cons)
+                _write_outputs(rows_all, representatives, out_ctx)
             finally:
-                if cons_ctx is not None:
-                    cons_ctx.close()
-            _write_outputs(rows_all, representatives)
+                if out_ctx is not None:
+                    out_ctx.close()
         dist.barrier()
         if rank == 0 and state[2]:
             shutil.rmtree(config.work_dir)

@@ -8,7 +8,9 @@ mgf_io.py:85-116 (TITLE, PEPMASS, CHARGE, RTINSECONDS, peaks).
 from __future__ import annotations
 
 import io
-from typing import Dict, Iterable, Iterator
+import locale
+import os
+from typing import Dict, Iterable, Iterator, Optional
 
 import numpy as np
 
@@ -289,3 +291,66 @@ def write_spectra(filename: str, spectra: Iterable[Dict]) -> None:
             for m, i in zip(s["mz"], s["intensity"]):
                 out.write(f"{m} {i}\n")
             out.write("END IONS\n\n")
+
+
+_PLAIN = "BEGIN IONS\nTITLE=PEPMASS CHARGE RTINSECONDS CLUSTER END 0123456789.e+-naif"     # every character the writer emits itself
+
+
+def title_blob(titles, encoding: Optional[str] = None):
+    """str array -> (u8 blob of the encoded titles back to back, i64 offsets[n + 1]), without a Python loop over the entries: one
+    join and one encode, the offsets from the separators' positions in the blob.  None when the text layer of
+    `open(filename, "w")` would not write plain bytes (an encoding that is no superset of ASCII, a platform that translates
+    newlines), when a title contains a newline, or when a title cannot be encoded (the host writer then raises)."""
+    n = len(titles)
+    encoding = encoding or locale.getpreferredencoding(False)
+    try:
+        if os.linesep != "\n" or _PLAIN.encode(encoding) != _PLAIN.encode("ascii"):
+            return None
+        joined = "\n".join(np.asarray(titles, dtype=str).tolist()).encode(encoding)
+    except (UnicodeEncodeError, LookupError):
+        return None
+    raw = np.frombuffer(joined, np.uint8)
+    sep = np.flatnonzero(raw == 0x0A)
+    if len(sep) != max(n - 1, 0):
+        return None
+    ptr = np.zeros(n + 1, np.int64)
+    ptr[1:n] = sep - np.arange(n - 1)                  # (title k begins behind separator k - 1, less the k - 1 taken out before it)
+    ptr[n] = len(raw) - len(sep) if n else 0
+    return raw[raw != 0x0A] if len(sep) else raw, ptr
+
+
+def entry_dicts(mz, intensity, indptr, rows, precursor_mz, retention_time, charge, cluster, titles):
+    """the columns of `write_representatives` (host arrays or tensors) -> the dicts `write_spectra` takes, entry by entry"""
+    host = [np.asarray(a.cpu() if hasattr(a, "cpu") else a) for a in (mz, intensity, indptr, rows, precursor_mz, retention_time, charge, cluster)]
+    mz, intensity, indptr, rows, precursor_mz, retention_time, charge, cluster = host
+    for k, r in enumerate(rows):
+        a, b = indptr[r], indptr[r + 1]
+        yield {"identifier": str(titles[k]), "precursor_mz": float(precursor_mz[k]), "precursor_charge": int(charge[k]) if charge[k] else None,
+               "retention_time": float(retention_time[k]), "mz": mz[a:b], "intensity": intensity[a:b], "cluster": int(cluster[k])}
+
+
+def _f32(a):
+    return a.float() if hasattr(a, "cpu") else np.asarray(a, np.float32)
+
+
+def write_representatives(filename: str, ctx, mz, intensity, indptr, rows, precursor_mz, retention_time, charge, cluster, titles,
+                          max_bytes: int = DEFAULT_CHUNK_BYTES, append: bool = False) -> str:
+    """The device writer: the file `write_spectra` writes for n entries, byte for byte, formatted by `ctx.format_mgf` (DESIGN.md
+    "MGF out of the device").  Peaks CSR mz / intensity (float32), indptr; rows[k]: the CSR row whose peaks entry k carries;
+    precursor_mz / retention_time (float32), charge (int, 0: no CHARGE line), cluster (int) per entry -- numpy arrays or device
+    tensors -- and `titles`, a str array (or what `title_blob` made of one).  The titles are encoded as `open(filename, "w")`
+    encodes them; where that cannot be mirrored (`title_blob`) the whole file is `write_spectra`'s.  `append`: add to the file instead of replacing it.
+    -> "device" or "host": the writer that wrote it."""
+    blob = titles if isinstance(titles, tuple) else title_blob(titles)
+    if blob is None:
+        if append:
+            raise ValueError("write_representatives: the host writer cannot append")
+        # (float32 columns, as the device formats them)
+        write_spectra(filename, entry_dicts(_f32(mz), _f32(intensity), indptr, rows, _f32(precursor_mz), _f32(retention_time), charge,
+                                            cluster, titles))
+        return "host"
+    with open(filename, "ab" if append else "wb") as out:
+        for chunk in ctx.format_mgf(mz, intensity, indptr, rows, precursor_mz, retention_time, charge, cluster, blob[0], blob[1],
+                                    max_bytes=max_bytes, copy=False):
+            out.write(memoryview(chunk))
+    return "device"

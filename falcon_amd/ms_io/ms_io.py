@@ -50,3 +50,11 @@ def write_spectra(filename: str, spectra) -> None:
     if writer is None:
         raise ValueError("Unsupported output file format (only MGF can be written)")
     writer(filename, spectra)
+
+
+def write_representatives(filename: str, ctx, *columns, **options) -> str:
+    """Write cluster representatives held as columns (`mgf_io.write_representatives`: peaks CSR, rows, precursor m/z, retention
+    time, charge, cluster id, titles) to a peak file, formatted on the device; only MGF can be written."""
+    if _extension(filename) != ".mgf":
+        raise ValueError("Unsupported output file format (only MGF can be written)")
+    return mgf_io.write_representatives(filename, ctx, *columns, **options)

@@ -457,6 +457,30 @@ int fal_mgf_parse(fal_ctx* ctx, const uint8_t* text, int64_t n_bytes, int64_t n_
                   int64_t* out_indptr, double* out_mz, float* out_intensity, double* precursor_mz, int32_t* charge,
                   int32_t* has_charge, double* retention_time, int64_t* title, int64_t* span, int32_t* status_out);
 
+/* ---- peak CSR + per-entry columns -> MGF text (the device writer; DESIGN.md "MGF out of the device" states the layout and the
+ *          number form; falcon_amd/ms_io/mgf_io.write_spectra is the writer it mirrors: for the same entries the bytes are equal).
+ * mz / intensity f32[nnz], indptr i64[n_rows + 1]: the peaks; rows i32[n]: the CSR row whose peaks entry k carries (any order,
+ * repeats allowed); precursor_mz f32[n], retention_time f32[n], charge i32[n] (0: no CHARGE line; negative: printed with '-'),
+ * cluster i64[n]; title u8[title_bytes] with title_ptr i64[n + 1]: entry k's title bytes [title_ptr[k], title_ptr[k + 1]).
+ * Entry k: "BEGIN IONS\nTITLE=<title>\nPEPMASS=<num>\n[CHARGE=<|z|><+ or ->\n]RTINSECONDS=<num>\nCLUSTER=<id>\n", one
+ * "<mz> <intensity>\n" per peak, "END IONS\n\n".  <num> of a float32 x: Python's repr(float(x)), at most 23 bytes.
+ * fal_mgf_write_sizes -> sizes_out i64[n] (every entry's bytes), offsets_out i64[n + 1] (their exclusive scan, the total last)
+ *          and *total_out (host).  One stream synchronisation.  FAL_EINVAL when a row lies outside the CSR or indptr / title_ptr
+ *          do not ascend inside their arrays (such an entry counts as one without peaks / title).
+ * fal_mgf_write: the text of entries [first, last) into out[0, out_bytes) at offsets[k] - offsets[first] (offsets: the array
+ *          fal_mgf_write_sizes filled for the same columns).  out needs no alignment.  FAL_EINVAL, and nothing written, when
+ *          out_bytes < offsets[last] - offsets[first]; no byte outside an entry's own range is ever stored, whatever the
+ *          offsets hold.  host_out: NULL, or pinned host memory of out_bytes bytes that receives a copy of out before the call's
+ *          one stream synchronisation.  No host work per entry or per peak. ----------------------------------------- [dev] */
+int fal_mgf_write_sizes(fal_ctx* ctx, const float* mz, const float* intensity, const int64_t* indptr, int64_t n_rows, int64_t nnz,
+                        const int32_t* rows, int64_t n, const float* precursor_mz, const float* retention_time,
+                        const int32_t* charge, const int64_t* cluster, const int64_t* title_ptr, int64_t title_bytes,
+                        int64_t* sizes_out, int64_t* offsets_out, int64_t* total_out);
+int fal_mgf_write(fal_ctx* ctx, const float* mz, const float* intensity, const int64_t* indptr, int64_t n_rows, int64_t nnz,
+                  const int32_t* rows, int64_t n, const float* precursor_mz, const float* retention_time, const int32_t* charge,
+                  const int64_t* cluster, const uint8_t* title, const int64_t* title_ptr, int64_t title_bytes,
+                  const int64_t* offsets, int64_t first, int64_t last, uint8_t* out, int64_t out_bytes, uint8_t* host_out);
+
 /* ---- mzML structure -> per-spectrum columns + the tables of fal_decode_peaks (the device reader; DESIGN.md "mzML on the
  *          device" states the grammar; falcon_amd/ms_io/mzml_io.read_chunks is the reader it mirrors and the one that decides
  *          whatever it leaves open).
