@@ -7,6 +7,7 @@
 #include "hash.h"
 #include "scan.h"
 #include "ivf.h"
+#include "tiles.h"
 #include <algorithm>
 
 #include <chrono>
@@ -308,6 +309,9 @@ int fal_ctx_plan(fal_ctx* c, int64_t n, int low_dim, int k_ann, int n_probe, int
     }
     // per-row arrays of the graph stages (graph.hip, tail.hip): labels, parents, segment tables
     for (int slot : {SLOT_DB, SLOT_DB2, SLOT_TAIL, SLOT_TAIL2, SLOT_FIN, SLOT_FIN2}) FAL_TRY(c->reserve(slot, 8 * nn + 4096, &p));
+    // the tile tables of the tiled graph tail (tail.hip): at most 2 n / kTileRows + 1 tiles (two neighbours together exceed kTileRows),
+    // ten 4-byte entries each
+    FAL_TRY(c->reserve(SLOT_TILES, 40 * (2 * nn / (size_t)kTileRows + 4) + 4096, &p));
     for (int slot = 0; slot < fal::kNumSlots; ++slot) c->release(slot);      // (no pointer is held: the passes may still grow them)
     return FAL_OK;
 }
@@ -349,7 +353,7 @@ int fal_ctx_enable_timing(fal_ctx* c, int on) {
 }
 
 int fal_ctx_counter(fal_ctx* c, int which, int64_t* value) {
-    FAL_REQUIRE(c && value && which >= 0 && which < 10, FAL_EINVAL, "fal_ctx_counter: bad argument");
+    FAL_REQUIRE(c && value && which >= 0 && which < 11, FAL_EINVAL, "fal_ctx_counter: bad argument");
     *value = c->counters[which];
     if (which == 5) *value = c->fb_host ? (int64_t)c->fb_host[0] + (int64_t)c->fb_host[2] : 0;   // fallback queries of the last prefiltered search: flat + IVF buckets (after a sync)
     return FAL_OK;

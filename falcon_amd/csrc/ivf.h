@@ -18,7 +18,8 @@ enum { SLOT_JOBS = 0, SLOT_SIMS = 1, SLOT_PROBES = 2, SLOT_PROBE_SIM = 3, SLOT_Q
        SLOT_MGF = 37, SLOT_MGF2 = 38, SLOT_MGF3 = 39, SLOT_MGF4 = 40, SLOT_MGF5 = 41,   // mgfparse.hip (37-40 live from fal_mgf_index to fal_mgf_parse)
        SLOT_ASSIGN = 42, SLOT_ASSIGN2 = 43,   // assignrep.hip
        SLOT_MZML = 44, SLOT_MZML2 = 45, SLOT_MZML3 = 46, SLOT_MZML4 = 47, SLOT_MZML5 = 48,   // mzmlscan.hip (44-47 live from fal_mzml_index to fal_mzml_parse)
-       SLOT_MGFW = 49 };   // mgfwrite.hip
+       SLOT_MGFW = 49,     // mgfwrite.hip
+       SLOT_TILES = 50 };  // tail.hip: the tile tables of fal_cluster_graph_tiled
 static_assert(SLOT_MGF2 == SLOT_MGF + 1 && SLOT_MGF3 == SLOT_MGF + 2 && SLOT_MGF4 == SLOT_MGF + 3 && SLOT_MZML2 == SLOT_MZML + 1 &&
                   SLOT_MZML3 == SLOT_MZML + 2 && SLOT_MZML4 == SLOT_MZML + 3,
               "fal::matches (textscan.h) addresses the four slots of an index as first + i");

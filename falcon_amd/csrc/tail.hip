@@ -10,8 +10,11 @@
 // offsets (clusters are tiny on average, so this stays in L2); every loop is strided over the
 // 64 lanes, so one huge cluster costs O(m^2 / 64), not O(m^2).
 #include <math.h>
+#include <stdlib.h>
+#include <algorithm>
 #include "common.h"
 #include "ivf.h"
+#include "tiles.h"
 #include "util.h"
 
 namespace fal {
@@ -194,12 +197,13 @@ __device__ __forceinline__ void sort_rows(int32_t* __restrict__ rows, int32_t* _
 }
 
 // one wave per DBSCAN cluster c (grid-stride; the cluster count lives on the device):
-// rows[seg[c] .. seg[c+1]) are its members, scattered in arbitrary order by member_scatter_kernel.
+// rows[seg[c] .. seg[c+1]) are its members, scattered in arbitrary order by member_scatter_kernel (sorted = 0) or in
+// ascending row order by tile_members_kernel (sorted = 1).
 __global__ __launch_bounds__(64) void refine_kernel(int32_t* __restrict__ rows, const int64_t* __restrict__ seg,
                                                     const int64_t* __restrict__ d_count,
                                                     const float* __restrict__ mz, const float* __restrict__ rt,
                                                     double tol, int is_da, double rt_tol, RefineScratch S,
-                                                    int32_t* __restrict__ sub, int32_t* __restrict__ n_sub) {
+                                                    int32_t* __restrict__ sub, int32_t* __restrict__ n_sub, int sorted) {
     const int lane = threadIdx.x;
     const int64_t C = *d_count;
     const bool use_rt = rt != nullptr && rt_tol >= 0.0;
@@ -275,7 +279,8 @@ __global__ __launch_bounds__(64) void refine_kernel(int32_t* __restrict__ rows, 
         const bool small = m <= kLdsMembers;
         const RefineScratch& W = small ? L : S;        // work arrays of this cluster ...
         const int64_t wo = small ? 0 : o;              // ... and where they start
-        sort_rows(rows + o, W.stack + wo, m, lane);    // members in ascending (precursor-sorted) row order
+        if (!sorted) sort_rows(rows + o, W.stack + wo, m, lane);    // members in ascending (precursor-sorted) row order
+                                                                    // (sorted: tile_members_kernel wrote them so)
         int32_t* A = W.t_a + wo;
         for (int e = lane; e < m; e += 64) W.val[wo + e] = mz[rows[o + e]];
         __syncthreads();
@@ -476,37 +481,417 @@ __global__ void finalize_kernel(const int32_t* __restrict__ labels, int64_t n, c
     }
 }
 
+// ------------------------------------------------------------------------------------------
+// The tail per bucket tile (tiles.h): one workgroup per tile, every per-row array in LDS
+// ------------------------------------------------------------------------------------------
+// No neighbour pair leaves a precursor bucket, so a9's components, a10's clusters and a11's medoids are tile-local; what is
+// global is their numbering, and that is a tile-local rank plus the count of the tiles in front (tile_scan_kernel between the
+// kernels).  No workgroup waits for another: the order between tiles comes from the kernel boundaries alone.  A stored id inside
+// [0, n) but outside the row's tile breaks the contract: it is never dereferenced (it counts as "no neighbour") and sets the
+// tile's error word, which the call reads back with its two counts.
+constexpr int kTileThreads = 512;
+constexpr int32_t kCore = -2;                  // vote[] of a core row; a non-core row's holds its lowest core in-neighbour
+constexpr int32_t kNoVote = 0x7fffffff;
+
+// exclusive prefix of v over the workgroup in thread order, *total = the sum; s_w: kTileThreads / 64 words of LDS
+__device__ __forceinline__ int block_excl_scan(int v, int* s_w, int* total) {
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    const int inc = wave_prefix_sum(v);
+    if (lane == 63) s_w[w] = inc;
+    __syncthreads();
+    int off = 0, tot = 0;
+#pragma unroll
+    for (int q = 0; q < kTileThreads / 64; ++q) {
+        const int s = s_w[q];
+        off += q < w ? s : 0;
+        tot += s;
+    }
+    __syncthreads();                           // (s_w is written again by the next call)
+    *total = tot;
+    return off + inc - v;
+}
+
+// graph.hip's union-find on a tile's parent[] in LDS (tile-local rows): links only ever point to smaller rows
+__device__ __forceinline__ int32_t tile_find(int32_t* parent, int32_t x) {
+    int32_t p = __hip_atomic_load(&parent[x], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+    while (p != x) {
+        const int32_t g = __hip_atomic_load(&parent[p], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        if (g != p) __hip_atomic_store(&parent[x], g, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        x = p;
+        p = g;
+    }
+    return x;
+}
+// read-only: the finds after the last union (why: graph.hip uf_find_final)
+__device__ __forceinline__ int32_t tile_find_final(const int32_t* parent, int32_t x) {
+    int32_t p = __hip_atomic_load(&parent[x], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+    while (p != x) {
+        x = p;
+        p = __hip_atomic_load(&parent[x], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+    }
+    return x;
+}
+__device__ __forceinline__ void tile_union(int32_t* parent, int32_t a, int32_t b) {
+    while (true) {                             // (the one loop bounded by other waves' progress: every retry follows a link to a smaller row)
+        a = tile_find(parent, a);
+        b = tile_find(parent, b);
+        if (a == b) return;
+        if (a < b) { const int32_t t = a; a = b; b = t; }
+        if (atomicCAS(&parent[a], a, b) == a) return;
+    }
+}
+
+// a9 of one tile.  -> labels[row] = the cluster's rank among the TILE's clusters (by lowest core row) or -1;
+// cnt[0][t] = clusters, cnt[1][t] = labelled rows, cnt[2][t] = 1 when a stored id lies outside the tile.
+// LDS: 16 B per row (parent, vote, rank, row length) + the edge list (what is left of lds_words 4-byte words).
+__global__ __launch_bounds__(kTileThreads) void tile_dbscan_kernel(const int32_t* __restrict__ nb_idx, const float* __restrict__ nb_dist,
+                                                                   const int32_t* __restrict__ count, int64_t n, int k, float eps,
+                                                                   const int32_t* __restrict__ tile_row, int nt, int lds_words,
+                                                                   int32_t* __restrict__ labels, int32_t* __restrict__ cnt) {
+    extern __shared__ __align__(16) int32_t tile_lds[];
+    __shared__ int s_w[kTileThreads / 64];
+    __shared__ int s_err, s_nlab, s_ne;
+    const int tid = threadIdx.x, lane = tid & 63, sub = tid & 7;
+    const int t = blockIdx.x;
+    const int r0 = tile_row[t], m = tile_row[t + 1] - r0;
+    int32_t *parent = tile_lds, *vote = tile_lds + m, *rank = tile_lds + 2 * m, *ext_l = tile_lds + 3 * m;
+    uint32_t* edges = reinterpret_cast<uint32_t*>(tile_lds + 4 * m);      // (source << 16 | target) of the eps-edges, tile rows
+    const int cap = lds_words - 4 * m;
+    if (tid == 0) s_err = s_nlab = s_ne = 0;
+    // the rows' lengths first, coalesced: the pass over the rows then waits for ONE level of global loads per step (a row's
+    // ids and distances together) instead of three in a chain -- the kernel is bound by that latency, not by bytes
+    for (int li = tid; li < m; li += kTileThreads) ext_l[li] = min(count[r0 + li], k);
+    __syncthreads();
+    // The one pass over the rows.  core(i) <=> a stored slot below count[i] holds another row of the tile within eps; eight
+    // threads per row, whole waves, a wave-uniform trip count.  Every eps-edge found goes to the edge list in LDS (one LDS
+    // atomic per wave and step), so that the union pass does not read the rows again -- a tile's rows do not stay in L2 behind
+    // the other tiles' (measured: the second pass cost as much as the first).
+    // Four rows a thread and step (e, e + 512, ...): their loads are in flight together -- a tile's time is the chain of its
+    // threads' load latencies, 16 steps deep at 1,024 rows without this.
+    constexpr int U = 4;
+    for (int e0 = tid; e0 < (m + 7) / 8 * 64; e0 += U * kTileThreads) {
+        int li[U], ext[U], most = 0;
+        bool c[U];
+        bool bad = false;
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            li[u] = (e0 + u * kTileThreads) >> 3;
+            ext[u] = li[u] < m ? ext_l[li[u]] : 0;
+            most = max(most, ext[u]);
+            c[u] = false;
+        }
+        for (int s = sub; __any(s < most); s += 8) {
+            int32_t j[U];
+            float d[U];
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                const bool on = s < ext[u];
+                j[u] = on ? nb_idx[(int64_t)(r0 + li[u]) * k + s] : -1;
+                d[u] = on ? nb_dist[(int64_t)(r0 + li[u]) * k + s] : INFINITY;
+            }
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                bool edge = false;
+                int lj = 0;
+                if (j[u] >= 0 && (int64_t)j[u] < n) {
+                    lj = j[u] - r0;
+                    if (lj < 0 || lj >= m) bad = true;
+                    else edge = lj != li[u] && d[u] <= eps;
+                }
+                const uint64_t em = __ballot(edge);
+                if (em) {                                        // (wave-uniform)
+                    int base = 0;
+                    if (lane == 0) base = atomicAdd(&s_ne, __popcll(em));
+                    base = __shfl(base, 0, 64);
+                    const int pos = base + __popcll(em & ((1ull << lane) - 1ull));
+                    if (edge && pos < cap) edges[pos] = ((uint32_t)li[u] << 16) | (uint32_t)lj;
+                }
+                c[u] = c[u] || edge;
+            }
+        }
+        if (bad) s_err = 1;
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const uint64_t any = __ballot(c[u]);
+            if (sub == 0 && li[u] < m) {
+                parent[li[u]] = li[u];
+                vote[li[u]] = ((any >> (lane & ~7)) & 0xffull) ? kCore : kNoVote;
+            }
+        }
+    }
+    __syncthreads();
+    // the eps-edges (their sources are core by definition): core -> core united, core -> border votes for the border's lowest
+    // core in-neighbour
+    const int ne = s_ne;
+    if (ne <= cap) {
+        for (int e = tid; e < ne; e += kTileThreads) {
+            const int li = (int)(edges[e] >> 16), lj = (int)(edges[e] & 0xFFFFu);
+            if (__hip_atomic_load(&vote[lj], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) == kCore) tile_union(parent, li, lj);
+            else atomicMin(&vote[lj], li);
+        }
+    } else {
+        // more eps-edges than the list holds: the rows of the core points once more
+        for (int e = tid; e < m * 8; e += kTileThreads) {
+            const int li = e >> 3;
+            if (vote[li] != kCore) continue;
+            const int64_t i = r0 + li;
+            const int ext = ext_l[li];
+            for (int s = sub; s < ext; s += 8) {
+                const int32_t j = nb_idx[i * k + s];
+                const float d = nb_dist[i * k + s];
+                if (j < 0 || (int64_t)j >= n) continue;
+                const int lj = j - r0;
+                if (lj < 0 || lj >= m || lj == li || !(d <= eps)) continue;
+                if (__hip_atomic_load(&vote[lj], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) == kCore) tile_union(parent, li, lj);
+                else atomicMin(&vote[lj], li);
+            }
+        }
+    }
+    __syncthreads();
+    for (int li = tid; li < m; li += kTileThreads)
+        if (vote[li] == kCore)
+            __hip_atomic_store(&parent[li], tile_find_final(parent, li), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+    __syncthreads();
+    // rank of every root among the tile's roots
+    int n_roots = 0;
+    for (int base = 0; base < m; base += kTileThreads) {
+        const int li = base + tid;
+        const int f = li < m && vote[li] == kCore && parent[li] == li;
+        int tot;
+        const int ex = block_excl_scan(f, s_w, &tot);
+        if (li < m) rank[li] = n_roots + ex;
+        n_roots += tot;
+    }
+    __syncthreads();
+    int mine = 0;
+    for (int li = tid; li < m; li += kTileThreads) {
+        const int32_t v = vote[li];
+        int32_t lab = -1;
+        if (v == kCore) lab = rank[parent[li]];
+        else if (v != kNoVote) lab = rank[parent[v]];
+        labels[r0 + li] = lab;
+        mine += lab >= 0;
+    }
+    if (mine) atomicAdd(&s_nlab, mine);
+    __syncthreads();
+    if (tid == 0) {
+        cnt[t] = n_roots;
+        cnt[nt + t] = s_nlab;
+        cnt[2 * nt + t] = s_err;
+    }
+}
+
+// out[c][0 .. nt] = exclusive prefix of in[c][0 .. nt), totals[c] = the sum, for c < ncol: one workgroup
+__global__ __launch_bounds__(kTileThreads) void tile_scan_kernel(const int32_t* __restrict__ in, int nt, int ncol,
+                                                                 int32_t* __restrict__ out, int64_t* __restrict__ totals) {
+    __shared__ int s_w[kTileThreads / 64];
+    for (int c = 0; c < ncol; ++c) {
+        int carry = 0;
+        for (int base = 0; base < nt; base += kTileThreads) {
+            const int t = base + (int)threadIdx.x;
+            const int v = t < nt ? in[(int64_t)c * nt + t] : 0;
+            int tot;
+            const int ex = block_excl_scan(v, s_w, &tot);
+            if (t < nt) out[(int64_t)c * (nt + 1) + t] = carry + ex;
+            carry += tot;
+        }
+        if (threadIdx.x == 0) {
+            out[(int64_t)c * (nt + 1) + nt] = carry;
+            totals[c] = carry;
+        }
+    }
+}
+
+// member lists of one tile's DBSCAN clusters: the (tile label, tile row) keys sorted in LDS (bitonic, noise rows last) ARE the
+// lists, ascending rows inside each cluster.  labels become global (cluster base of the tile + tile label), seg / rows as
+// label_hist + scan + member_scatter leave them, but ordered.  base = [cluster base | member base], nt + 1 each.
+__global__ __launch_bounds__(kTileThreads) void tile_members_kernel(const int32_t* __restrict__ tile_row, const int32_t* __restrict__ base,
+                                                                    int nt, int32_t* __restrict__ labels, int64_t* __restrict__ seg,
+                                                                    int32_t* __restrict__ rows) {
+    extern __shared__ __align__(16) int32_t tile_lds[];
+    uint32_t* keys = reinterpret_cast<uint32_t*>(tile_lds);
+    const int tid = threadIdx.x, t = blockIdx.x;
+    const int r0 = tile_row[t], m = tile_row[t + 1] - r0;
+    const int c0 = base[t], m0 = base[nt + 1 + t], n_lab = base[nt + 1 + t + 1] - m0;
+    int P = 2;
+    while (P < m) P <<= 1;
+    for (int li = tid; li < P; li += kTileThreads) {
+        uint32_t key = 0xFFFFFFFFu;
+        if (li < m) {
+            const int32_t l = labels[r0 + li];
+            if (l >= 0) {
+                key = ((uint32_t)l << 16) | (uint32_t)li;
+                labels[r0 + li] = c0 + l;
+            }
+        }
+        keys[li] = key;
+    }
+    __syncthreads();
+    for (int k2 = 2; k2 <= P; k2 <<= 1)
+        for (int j = k2 >> 1; j > 0; j >>= 1) {
+            for (int x = tid; x < P / 2; x += kTileThreads) {
+                const int a = ((x & ~(j - 1)) << 1) | (x & (j - 1)), b = a | j;
+                const uint32_t ka = keys[a], kb = keys[b];
+                if ((ka > kb) == ((a & k2) == 0)) {
+                    keys[a] = kb;
+                    keys[b] = ka;
+                }
+            }
+            __syncthreads();
+        }
+    for (int p = tid; p < n_lab; p += kTileThreads) {
+        const uint32_t key = keys[p];
+        rows[m0 + p] = r0 + (int32_t)(key & 0xFFFFu);
+        if (p == 0 || (keys[p - 1] >> 16) != (key >> 16)) seg[c0 + (int32_t)(key >> 16)] = m0 + p;
+    }
+    if (t == nt - 1 && tid == 0) seg[base[nt]] = base[nt + 1 + nt];      // one past the last cluster: the member count
+}
+
+// clusters a10 kept per tile: the sum of n_sub over the tile's DBSCAN clusters
+__global__ __launch_bounds__(256) void tile_kept_kernel(const int32_t* __restrict__ cbase, const int32_t* __restrict__ n_sub,
+                                                        int32_t* __restrict__ kept) {
+    __shared__ int s_sum;
+    const int t = blockIdx.x, c0 = cbase[t], c1 = cbase[t + 1];
+    if (threadIdx.x == 0) s_sum = 0;
+    __syncthreads();
+    int v = 0;
+    for (int c = c0 + (int)threadIdx.x; c < c1; c += 256) v += n_sub[c];
+    if (v) atomicAdd(&s_sum, v);
+    __syncthreads();
+    if (threadIdx.x == 0) kept[t] = s_sum;
+}
+
+// a10's numbering applied and a11 of one tile: final label = (clusters kept by the tiles in front) + (kept by the tile's earlier
+// DBSCAN clusters) + sub id; sizes by an LDS histogram; score_i exactly as medoid_score_rows_kernel (float32, slot order, 1.0 per
+// member the row does not store); best = minimum of (score bits, row) per cluster in LDS.  Also the noise flags by dataset row.
+// LDS: 16 B per row (label, size, 64-bit best).
+__global__ __launch_bounds__(kTileThreads) void tile_medoid_kernel(const int32_t* __restrict__ nb_idx, const float* __restrict__ nb_dist,
+                                                                   const int32_t* __restrict__ count, int64_t n, int k,
+                                                                   const int32_t* __restrict__ tile_row, const int32_t* __restrict__ base,
+                                                                   const int32_t* __restrict__ fbase, int nt,
+                                                                   const int32_t* __restrict__ n_sub, const int32_t* __restrict__ rows,
+                                                                   const int32_t* __restrict__ sub, int32_t* __restrict__ labels,
+                                                                   const int64_t* __restrict__ row_order, int32_t* __restrict__ noise,
+                                                                   unsigned long long* __restrict__ best) {
+    extern __shared__ __align__(16) int32_t tile_lds[];
+    __shared__ int s_w[kTileThreads / 64];
+    const int tid = threadIdx.x, t = blockIdx.x;
+    const int r0 = tile_row[t], m = tile_row[t + 1] - r0;
+    const int c0 = base[t], nc = base[t + 1] - c0, m0 = base[nt + 1 + t], nm = base[nt + 1 + t + 1] - m0;
+    const int fb = fbase[t], nf = fbase[t + 1] - fb;
+    int32_t *flab = tile_lds, *size = tile_lds + m;          // size[] first holds the kept-cluster prefix of the tile's DBSCAN clusters
+    unsigned long long* bestl = reinterpret_cast<unsigned long long*>(tile_lds + 2 * m);
+    int carry = 0;
+    for (int b = 0; b < nc; b += kTileThreads) {
+        const int c = b + tid;
+        const int v = c < nc ? n_sub[c0 + c] : 0;
+        int tot;
+        const int ex = block_excl_scan(v, s_w, &tot);
+        if (c < nc) size[c] = carry + ex;
+        carry += tot;
+    }
+    for (int li = tid; li < m; li += kTileThreads) flab[li] = -1;
+    __syncthreads();
+    for (int p = tid; p < nm; p += kTileThreads) {
+        const int32_t s = sub[m0 + p];
+        if (s >= 0) {
+            const int32_t row = rows[m0 + p];
+            flab[row - r0] = size[labels[row] - c0] + s;
+        }
+    }
+    __syncthreads();
+    for (int c = tid; c < nf; c += kTileThreads) {
+        size[c] = 0;
+        bestl[c] = ~0ull;
+    }
+    __syncthreads();
+    for (int li = tid; li < m; li += kTileThreads) {
+        const int32_t f = flab[li];
+        const int64_t i = r0 + li;
+        labels[i] = f >= 0 ? fb + f : -1;
+        noise[row_order[i]] = f < 0;
+        if (f >= 0) atomicAdd(&size[f], 1);
+    }
+    __syncthreads();
+    for (int li = tid; li < m; li += kTileThreads) {
+        const int32_t f = flab[li];
+        if (f < 0) continue;
+        const int64_t i = r0 + li;
+        float s = 0.f;
+        int same = 0;
+        const int ext = min(count[i], k);
+        for (int s0 = 0; s0 < ext; s0 += 4) {                   // four slots' loads in flight, then their sums in slot order
+            int32_t j4[4];
+            float d4[4];
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                const bool on = s0 + u < ext;
+                j4[u] = on ? nb_idx[i * k + s0 + u] : -1;
+                d4[u] = on ? nb_dist[i * k + s0 + u] : 0.f;
+            }
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                const int32_t j = j4[u];
+                const int lj = j - r0;
+                if (j >= 0 && (int64_t)j < n && lj >= 0 && lj < m && lj != li && flab[lj] == f) {
+                    s += d4[u];                                 // (slot order, float32: the oracle's sum)
+                    ++same;
+                }
+            }
+        }
+        s += (float)(size[f] - 1 - same);
+        atomicMin(&bestl[f], ((unsigned long long)__float_as_uint(s) << 32) | (unsigned long long)(uint32_t)i);
+    }
+    __syncthreads();
+    for (int c = tid; c < nf; c += kTileThreads) best[fb + c] = bestl[c];
+}
+
 }  // namespace fal
-FAL_WARM_KERNEL(fal::refine_kernel);      // (fal_ctx_plan: this unit's code object is loaded up front)
+FAL_WARM_KERNEL(fal::refine_kernel);      // (fal_ctx_plan: this unit's code object is loaded up front; the tile kernels are in it)
 
 using namespace fal;
 
-// a10 on device-resident counts: *d_count_in DBSCAN clusters in, *d_count_out refined clusters out
-int fal::refine_dev(fal_ctx* ctx, int32_t* labels, int64_t n, const float* mz, const float* rt, double tol, int is_da,
-                    double rt_tol, const int64_t* d_count_in, int64_t** d_count_out) {
-    hipStream_t st = ctx->stream;
-    // sized by n: a DBSCAN cluster of this library may hold ONE member (a core row whose only eps-neighbours are
-    // non-core borders that join a lower core), and the staged ABI accepts any cluster count <= n
+// a10's arrays in the context's scratch (SLOT_TAIL, SLOT_TAIL2, SLOT_TAIL4), for both drivers of refine_kernel:
+// counts | cursor | n_sub (n + 1 each: a DBSCAN cluster of this library may hold ONE member -- a core row whose only eps-neighbours
+// are non-core borders that join a lower core -- and the staged ABI accepts any cluster count <= n), rows | sub (n each);
+// seg | base (n + 3 each); the slab of refine_kernel's global work arrays.  The tiled driver leaves counts, cursor and base unused.
+struct RefineArrays {
+    int32_t *counts, *cursor, *n_sub, *rows, *sub;
+    int64_t *seg, *base;
+    RefineScratch S;
+};
+static int refine_arrays(fal_ctx* ctx, int64_t n, RefineArrays* A) {
     const int64_t cmax = n + 1;
-    int32_t *counts = nullptr, *rows = nullptr;
-    int64_t *seg = nullptr, *base = nullptr;
     unsigned char* slab = nullptr;
-    FAL_TRY(ctx->reserve(SLOT_TAIL, sizeof(int32_t) * (size_t)(3 * cmax + 2 * n) + 64, (void**)&counts));
-    int32_t* cursor = counts + cmax;
-    int32_t* n_sub = cursor + cmax;
-    rows = n_sub + cmax;
-    int32_t* sub = rows + n;
-    FAL_TRY(ctx->reserve(SLOT_TAIL2, sizeof(int64_t) * (size_t)(2 * (cmax + 2)), (void**)&seg));
-    base = seg + (cmax + 2);
+    FAL_TRY(ctx->reserve(SLOT_TAIL, sizeof(int32_t) * (size_t)(3 * cmax + 2 * n) + 64, (void**)&A->counts));
+    A->cursor = A->counts + cmax;
+    A->n_sub = A->cursor + cmax;
+    A->rows = A->n_sub + cmax;
+    A->sub = A->rows + n;
+    FAL_TRY(ctx->reserve(SLOT_TAIL2, sizeof(int64_t) * (size_t)(2 * (cmax + 2)), (void**)&A->seg));
+    A->base = A->seg + (cmax + 2);
     const size_t per = 4 * 11 + 8;   // 11 4-byte arrays + 1 double array
     FAL_TRY(ctx->reserve(SLOT_TAIL4, per * (size_t)n + 256, (void**)&slab));
-    RefineScratch S;
+    RefineScratch& S = A->S;
     S.zmd = reinterpret_cast<double*>(slab);
     float* f = reinterpret_cast<float*>(slab + 8 * (size_t)n);
     S.val = f;            S.smin = f + n;       S.smax = f + 2 * n;
     int32_t* q = reinterpret_cast<int32_t*>(f + 3 * n);
     S.ord = q;            S.sid = q + n;        S.zl = q + 2 * n;     S.zr = q + 3 * n;
     S.t_a = q + 4 * n;    S.t_b = q + 5 * n;    S.stack = q + 6 * n;  S.visit = q + 7 * n;
+    return FAL_OK;
+}
+
+// a10 on device-resident counts: *d_count_in DBSCAN clusters in, *d_count_out refined clusters out
+int fal::refine_dev(fal_ctx* ctx, int32_t* labels, int64_t n, const float* mz, const float* rt, double tol, int is_da,
+                    double rt_tol, const int64_t* d_count_in, int64_t** d_count_out) {
+    hipStream_t st = ctx->stream;
+    const int64_t cmax = n + 1;
+    RefineArrays A;
+    FAL_TRY(refine_arrays(ctx, n, &A));
+    int32_t *counts = A.counts, *cursor = A.cursor, *n_sub = A.n_sub, *rows = A.rows, *sub = A.sub;
+    int64_t *seg = A.seg, *base = A.base;
+    const RefineScratch& S = A.S;
     const int grid = (int)std::min<int64_t>(ceil_div(n, 256), (int64_t)ctx->num_cus * 16);
     const int cgrid = (int)std::min<int64_t>(cmax, (int64_t)ctx->num_cus * 32);
     FAL_CHECK_HIP(hipMemsetAsync(counts, 0, sizeof(int32_t) * (size_t)(3 * cmax), st));   // counts, cursor, n_sub
@@ -516,7 +901,7 @@ int fal::refine_dev(fal_ctx* ctx, int32_t* labels, int64_t n, const float* mz, c
         FAL_TRY(device_scan_i32(ctx, counts, cmax, seg, SLOT_TAIL3));
         hipLaunchKernelGGL(member_scatter_kernel, dim3(grid), dim3(256), 0, st, labels, n, seg, cursor, rows);
         hipLaunchKernelGGL(refine_kernel, dim3(cgrid), dim3(64), 0, st, rows, seg, d_count_in, mz,
-                           rt_tol >= 0.0 ? rt : nullptr, tol, is_da, rt_tol, S, sub, n_sub);
+                           rt_tol >= 0.0 ? rt : nullptr, tol, is_da, rt_tol, S, sub, n_sub, 0);
         FAL_TRY(device_scan_i32(ctx, n_sub, cmax, base, SLOT_TAIL3));
         hipLaunchKernelGGL(relabel_kernel, dim3(cgrid), dim3(64), 0, st, rows, seg, d_count_in, sub, base, labels);
     }
@@ -652,6 +1037,108 @@ int fal_cluster_graph_counted(fal_ctx* ctx, const int32_t* nb_idx, const float* 
     FAL_REQUIRE(nb_count || n == 0, FAL_EINVAL, "fal_cluster_graph_counted: NULL nb_count");
     return cluster_graph_impl(ctx, nb_idx, nb_dist, n, k, eps, -1, precursor_mz_sorted, rt_sorted, tol, tol_is_da, rt_tol,
                               row_order, labels_sorted_scratch, labels_out, medoids_out, n_clusters, n_labels, nb_count);
+}
+
+void fal_graph_tile_limits(int* tile_rows, int* max_tile_rows) {
+    if (tile_rows) *tile_rows = kTileRows;
+    if (max_tile_rows) *max_tile_rows = kTileMaxRows;
+}
+
+// fal_cluster_graph_counted per bucket tile.  A bucket beyond kTileMaxRows rows, or FALCON_GRAPH_TILED=0 (read per call: A/B
+// runs), sends the whole call down fal_cluster_graph_counted's path; fal_ctx_counter(10) tells which ran.
+int fal_cluster_graph_tiled(fal_ctx* ctx, const int32_t* nb_idx, const float* nb_dist, const int32_t* nb_count, int64_t n, int k,
+                            float eps, const int64_t* bucket_off, int64_t n_buckets, const float* precursor_mz_sorted,
+                            const float* rt_sorted, double tol, int tol_is_da, double rt_tol, const int64_t* row_order,
+                            int32_t* labels_sorted_scratch, int32_t* labels_out, int32_t* medoids_out, int64_t* n_clusters,
+                            int64_t* n_labels) {
+    fal::CallScope _call(ctx);
+    FAL_REQUIRE(ctx && n >= 0 && k >= 1 && n < (int64_t)INT32_MAX && n_clusters && n_labels, FAL_EINVAL,
+                "fal_cluster_graph_tiled: bad argument");
+    FAL_REQUIRE(nb_count || n == 0, FAL_EINVAL, "fal_cluster_graph_tiled: NULL nb_count");
+    FAL_REQUIRE(bucket_off && n_buckets >= 0, FAL_EINVAL, "fal_cluster_graph_tiled: NULL bucket table");
+    ctx->counters[10] = 0;
+    std::vector<int32_t> tile_row;
+    int64_t max_rows = 0;
+    const char* sw = getenv("FALCON_GRAPH_TILED");
+    const bool forced_off = sw && sw[0] == '0';
+    const int rc = build_tile_table(bucket_off, n_buckets, n, kTileRows, kTileMaxRows, tile_row, &max_rows);
+    FAL_REQUIRE(rc >= 0, FAL_EINVAL, "fal_cluster_graph_tiled: bucket_off must ascend from 0 to n");
+    if (rc == 1 || forced_off || n == 0)
+        return cluster_graph_impl(ctx, nb_idx, nb_dist, n, k, eps, -1, precursor_mz_sorted, rt_sorted, tol, tol_is_da, rt_tol,
+                                  row_order, labels_sorted_scratch, labels_out, medoids_out, n_clusters, n_labels, nb_count);
+    *n_clusters = *n_labels = 0;
+    FAL_REQUIRE(nb_idx && nb_dist && precursor_mz_sorted && row_order && labels_sorted_scratch && labels_out && medoids_out,
+                FAL_EINVAL, "fal_cluster_graph_tiled: NULL array");
+    ctx->counters[10] = 1;
+    hipStream_t st = ctx->stream;
+    const int nt = (int)tile_row.size() - 1;
+    int32_t* labels = labels_sorted_scratch;
+    // tile tables: tile_row[nt + 1] | cnt[3][nt] | base[3][nt + 1] | kept[nt] | fbase[nt + 1], then the int64 totals
+    int32_t* tt = nullptr;
+    const size_t words = (size_t)(nt + 1) + 3 * (size_t)nt + 3 * (size_t)(nt + 1) + (size_t)nt + (size_t)(nt + 1);
+    FAL_TRY(ctx->reserve(SLOT_TILES, sizeof(int32_t) * (words + 2) + sizeof(int64_t) * 4, (void**)&tt));
+    int32_t *d_tile_row = tt, *cnt = d_tile_row + (nt + 1), *base = cnt + 3 * (size_t)nt, *kept = base + 3 * (size_t)(nt + 1),
+            *fbase = kept + nt;
+    int64_t* totals = reinterpret_cast<int64_t*>(tt + ((words + 1) & ~(size_t)1));     // [0] DBSCAN clusters, [1] members, [2] error, [3] clusters kept
+    FAL_TRY(ctx->upload(d_tile_row, tile_row.data(), sizeof(int32_t) * (size_t)(nt + 1)));
+    // a10's arrays (refine_dev's) and a11's
+    const int64_t cmax = n + 1;
+    RefineArrays A;
+    FAL_TRY(refine_arrays(ctx, n, &A));
+    int32_t *n_sub = A.n_sub, *rows = A.rows, *sub = A.sub, *noise = nullptr;
+    int64_t *seg = A.seg, *rank = nullptr;
+    const RefineScratch& S = A.S;
+    unsigned long long* best = nullptr;
+    FAL_TRY(ctx->reserve(SLOT_FIN, sizeof(int32_t) * (size_t)(n + 2), (void**)&noise));
+    FAL_TRY(ctx->reserve(SLOT_FIN2, sizeof(unsigned long long) * (size_t)(cmax + 1), (void**)&best));
+    FAL_TRY(ctx->reserve(SLOT_FIN3, sizeof(int64_t) * (size_t)(n + 1), (void**)&rank));
+    // Dynamic LDS: one size per launch, so EVERY workgroup of the call gets what the call's largest tile needs -- 16 B per row
+    // in both kernels, and in tile_dbscan_kernel another 16 B per row of edge list (four eps-edges a row; a smaller tile of the
+    // same launch has the rest of the block for its list) as far as the CU's 160 KB go: beyond 4,864 rows the list of the largest
+    // tile shrinks, to 6,144 edges at 8,192 rows, and a tile whose edges do not fit reads its core rows a second time.
+    // Measured at 10 M spectra (profiles/NOTES.md): tiles of ~3,750 rows, 120 KB and one workgroup a CU, still halve the
+    // dbscan stage of the per-row kernels.  Beyond 64 KB a kernel has to be told: a call with a bucket of more than 1,536 rows
+    // pays two hipFuncSetAttribute calls on the host, in front of its first launch.
+    constexpr size_t kLdsMost = 16 * (size_t)kTileMaxRows + 24 * 1024;
+    const size_t lds_db = std::min<size_t>(32 * (size_t)max_rows, kLdsMost), lds_md = 16 * (size_t)max_rows;
+    size_t lds_mem = 8;
+    while (lds_mem < 4 * (size_t)max_rows) lds_mem <<= 1;
+    if (lds_db > 48 * 1024) {
+        FAL_CHECK_HIP(hipFuncSetAttribute((const void*)tile_dbscan_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsMost));
+        FAL_CHECK_HIP(hipFuncSetAttribute((const void*)tile_medoid_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 16 * kTileMaxRows));
+    }
+    ctx->stage_reset(ST_DBSCAN);
+    ctx->stage_reset(ST_TAIL);
+    {
+        StageScope ts(ctx, ST_DBSCAN);
+        hipLaunchKernelGGL(tile_dbscan_kernel, dim3(nt), dim3(kTileThreads), lds_db, st, nb_idx, nb_dist, nb_count, n, k, eps,
+                           d_tile_row, nt, (int)(lds_db / 4), labels, cnt);
+        hipLaunchKernelGGL(tile_scan_kernel, dim3(1), dim3(kTileThreads), 0, st, cnt, nt, 3, base, totals);
+    }
+    {
+        StageScope ts(ctx, ST_TAIL);
+        hipLaunchKernelGGL(tile_members_kernel, dim3(nt), dim3(kTileThreads), lds_mem, st, d_tile_row, base, nt, labels, seg, rows);
+        hipLaunchKernelGGL(refine_kernel, dim3((unsigned)std::min<int64_t>(cmax, (int64_t)ctx->num_cus * 32)), dim3(64), 0, st, rows,
+                           seg, totals, precursor_mz_sorted, rt_tol >= 0.0 ? rt_sorted : nullptr, tol, tol_is_da, rt_tol, S, sub,
+                           n_sub, 1);
+        hipLaunchKernelGGL(tile_kept_kernel, dim3(nt), dim3(256), 0, st, base, n_sub, kept);
+        hipLaunchKernelGGL(tile_scan_kernel, dim3(1), dim3(kTileThreads), 0, st, kept, nt, 1, fbase, totals + 3);
+        hipLaunchKernelGGL(tile_medoid_kernel, dim3(nt), dim3(kTileThreads), lds_md, st, nb_idx, nb_dist, nb_count, n, k, d_tile_row,
+                           base, fbase, nt, n_sub, rows, sub, labels, row_order, noise, best);
+        FAL_TRY(device_scan_i32(ctx, noise, n, rank, SLOT_TAIL3));
+        hipLaunchKernelGGL(finalize_kernel, dim3((unsigned)std::min<int64_t>(ceil_div(n, 256), (int64_t)ctx->num_cus * 16)), dim3(256),
+                           0, st, labels, n, totals + 3, row_order, rank, best, labels_out, medoids_out);
+    }
+    FAL_CHECK_HIP(hipGetLastError());
+    int64_t h[3] = {0, 0, 0};                  // tiles in error, clusters kept | noise rows
+    FAL_CHECK_HIP(hipMemcpyAsync(&h[0], totals + 2, 2 * sizeof(int64_t), hipMemcpyDeviceToHost, st));
+    FAL_CHECK_HIP(hipMemcpyAsync(&h[2], rank + n, sizeof(int64_t), hipMemcpyDeviceToHost, st));
+    FAL_CHECK_HIP(hipStreamSynchronize(st));
+    FAL_REQUIRE(h[0] == 0, FAL_EINVAL, "fal_cluster_graph_tiled: a stored neighbour id lies outside its row's bucket tile "
+                "(%lld tile(s)): nb_idx and bucket_off do not describe the same partition", (long long)h[0]);
+    *n_clusters = h[1];
+    *n_labels = h[1] + h[2];
+    return FAL_OK;
 }
 
 int fal_cluster_graph_linkage(fal_ctx* ctx, const int32_t* nb_idx, const float* nb_dist, int64_t n, int k, float threshold,

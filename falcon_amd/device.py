@@ -586,11 +586,19 @@ class Context:
 
     LINKAGE = {"single": 0, "complete": 1, "average": 2}
 
+    def graph_tile_limits(self):
+        """-> (rows that close a tile, most rows of one bucket `fal_cluster_graph_tiled` takes per tile)"""
+        t, m = C.c_int(), C.c_int()
+        self.lib.fal_graph_tile_limits(C.byref(t), C.byref(m))
+        return t.value, m.value
+
     def cluster_graph(self, nb_idx, nb_dist, eps: float, mz_sorted, rt_sorted, tol: float, mode: str, rt_tol, order,
-                      linkage: Optional[str] = None, nb_count=None):
+                      linkage: Optional[str] = None, nb_count=None, splits=None):
         """a9..a12 fused: -> labels i32[n] (dataset rows), medoids i32[n_labels], labels_sorted, n_clusters.
         `linkage` = None: DBSCAN(eps); "single" / "complete" / "average": hierarchical clustering cut at `eps` (f4).
-        `nb_count` (the search's per-row neighbour counts, rows front-packed): the graph passes read the stored slots only."""
+        `nb_count` (the search's per-row neighbour counts, rows front-packed): the graph passes read the stored slots only.
+        `splits` (host, the bucket table the search ran on; DBSCAN with `nb_count` only): `fal_cluster_graph_tiled`, the same
+        results computed per tile of whole buckets (`counter(10)` tells whether the tiles or the per-row path ran)."""
         torch = _torch()
         n, k = nb_idx.shape
         lab_sorted = self.empty((n,), torch.int32)
@@ -600,7 +608,12 @@ class Context:
         tail = (self._p(mz_sorted), self._p(rt_sorted), float(tol), int(mode == "Da"),
                 -1.0 if rt_tol is None else float(rt_tol), self._p(order), self._p(lab_sorted), self._p(labels),
                 self._p(medoids), C.byref(nc), C.byref(nl))
-        if linkage is None and nb_count is not None:
+        if linkage is None and nb_count is not None and splits is not None:
+            sp = np.ascontiguousarray(splits, dtype=np.int64)
+            check(self.lib.fal_cluster_graph_tiled(self._h, self._p(nb_idx), self._p(nb_dist), self._p(nb_count), n, k,
+                                                   float(eps), sp.ctypes.data_as(C.c_void_p), len(sp) - 1, *tail),
+                  "fal_cluster_graph_tiled")
+        elif linkage is None and nb_count is not None:
             check(self.lib.fal_cluster_graph_counted(self._h, self._p(nb_idx), self._p(nb_dist), self._p(nb_count), n, k,
                                                      float(eps), *tail), "fal_cluster_graph_counted")
         elif linkage is None:

@@ -89,7 +89,8 @@ int fal_ctx_enable_timing(fal_ctx* ctx, int on);
  *            an indexed bucket, bit 1 = rows handed to the flat prefilter hold negative / non-finite components, so
  *            that index is built / searched with the exact kernels (see fal_ivf_build_x16);
  * which = 7, 8: the part of counters 0 and 4 that belongs to flat buckets of up to 32 rows, whose kernel is not
- *            timed under stage 8 (subtract them to price stage 8's launches). */
+ *            timed under stage 8 (subtract them to price stage 8's launches);
+ * which = 10: 1 when the last fal_cluster_graph_tiled ran per bucket tile, 0 when it took the per-row path. */
 int fal_ctx_counter(fal_ctx* ctx, int which, int64_t* value);
 
 /* ---- a1  bin geometry: reference spectrum.py:172-199 `get_dim` (float32) --- [host] */
@@ -325,6 +326,22 @@ int fal_cluster_graph_counted(fal_ctx* ctx, const int32_t* nb_idx, const float* 
                               double tol, int tol_is_da, double rt_tol, const int64_t* row_order,
                               int32_t* labels_sorted_scratch, int32_t* labels_out, int32_t* medoids_out,
                               int64_t* n_clusters /*[host]*/, int64_t* n_labels /*[host]*/);
+
+/* fal_cluster_graph_counted given the precursor buckets of the rows (bucket_off: HOST, n_buckets + 1 ascending row offsets,
+ * 0 .. n -- the table the search ran on): the same results bit for bit, computed per TILE of consecutive whole buckets, one
+ * workgroup per tile with the per-row state in LDS.  Contract: every stored neighbour of a row lies in the
+ * row's bucket (the search is bucket by bucket).  A stored id inside [0, n) but outside its row's tile is never followed and
+ * fails the call with FAL_EINVAL; the context stays usable.  A bucket of more than max_tile_rows rows, or FALCON_GRAPH_TILED=0 in
+ * the environment (read per call), sends the whole call down fal_cluster_graph_counted's path.
+ * fal_ctx_counter(10): 1 when the last call ran per tile, 0 when it took that path. --- [dev] */
+int fal_cluster_graph_tiled(fal_ctx* ctx, const int32_t* nb_idx, const float* nb_dist, const int32_t* nb_count,
+                            int64_t n, int k, float eps, const int64_t* bucket_off /*[host]*/, int64_t n_buckets,
+                            const float* precursor_mz_sorted, const float* rt_sorted,
+                            double tol, int tol_is_da, double rt_tol, const int64_t* row_order,
+                            int32_t* labels_sorted_scratch, int32_t* labels_out, int32_t* medoids_out,
+                            int64_t* n_clusters /*[host]*/, int64_t* n_labels /*[host]*/);
+/* the rows that close a tile, and the most rows of one bucket the tiled path takes --- [host] */
+void fal_graph_tile_limits(int* tile_rows, int* max_tile_rows);
 
 /* ---- f4  hierarchical clustering of the neighbour graph: the clustering the reference snapshot ships,
  *          fcluster(fastcluster.linkage(pdist, linkage), distance_threshold, "distance") (cluster.py:283-290), on the
