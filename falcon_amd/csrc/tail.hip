@@ -542,7 +542,8 @@ __device__ __forceinline__ void tile_union(int32_t* parent, int32_t a, int32_t b
 }
 
 // a9 of one tile.  -> labels[row] = the cluster's rank among the TILE's clusters (by lowest core row) or -1;
-// cnt[0][t] = clusters, cnt[1][t] = labelled rows, cnt[2][t] = 1 when a stored id lies outside the tile.
+// cnt[0][t] = clusters, cnt[1][t] = labelled rows, cnt[2][t] = 1 when a stored id lies outside the tile, cnt[3][t] = 1 when
+// the tile's eps-edges did not fit its list and the core rows were read a second time.
 // LDS: 16 B per row (parent, vote, rank, row length) + the edge list (what is left of lds_words 4-byte words).
 __global__ __launch_bounds__(kTileThreads) void tile_dbscan_kernel(const int32_t* __restrict__ nb_idx, const float* __restrict__ nb_dist,
                                                                    const int32_t* __restrict__ count, int64_t n, int k, float eps,
@@ -556,7 +557,7 @@ __global__ __launch_bounds__(kTileThreads) void tile_dbscan_kernel(const int32_t
     const int r0 = tile_row[t], m = tile_row[t + 1] - r0;
     int32_t *parent = tile_lds, *vote = tile_lds + m, *rank = tile_lds + 2 * m, *ext_l = tile_lds + 3 * m;
     uint32_t* edges = reinterpret_cast<uint32_t*>(tile_lds + 4 * m);      // (source << 16 | target) of the eps-edges, tile rows
-    const int cap = lds_words - 4 * m;
+    const int cap = (int)tile_edge_capacity(4 * (int64_t)lds_words, m);
     if (tid == 0) s_err = s_nlab = s_ne = 0;
     // the rows' lengths first, coalesced: the pass over the rows then waits for ONE level of global loads per step (a row's
     // ids and distances together) instead of three in a chain -- the kernel is bound by that latency, not by bytes
@@ -678,6 +679,7 @@ __global__ __launch_bounds__(kTileThreads) void tile_dbscan_kernel(const int32_t
         cnt[t] = n_roots;
         cnt[nt + t] = s_nlab;
         cnt[2 * nt + t] = s_err;
+        cnt[3 * nt + t] = ne > cap;
     }
 }
 
@@ -1044,8 +1046,15 @@ void fal_graph_tile_limits(int* tile_rows, int* max_tile_rows) {
     if (max_tile_rows) *max_tile_rows = kTileMaxRows;
 }
 
+void fal_graph_tile_capacity(int64_t max_rows, int64_t rows, int64_t* lds_bytes, int64_t* edge_capacity) {
+    const int64_t b = tile_dbscan_lds_bytes(max_rows);
+    if (lds_bytes) *lds_bytes = b;
+    if (edge_capacity) *edge_capacity = tile_edge_capacity(b, rows);
+}
+
 // fal_cluster_graph_counted per bucket tile.  A bucket beyond kTileMaxRows rows, or FALCON_GRAPH_TILED=0 (read per call: A/B
-// runs), sends the whole call down fal_cluster_graph_counted's path; fal_ctx_counter(10) tells which ran.
+// runs), sends the whole call down fal_cluster_graph_counted's path; fal_ctx_counter(10) tells which ran,
+// fal_ctx_counter(11) how many tiles' eps-edges overflowed their LDS list (tile_dbscan_kernel's second pass).
 int fal_cluster_graph_tiled(fal_ctx* ctx, const int32_t* nb_idx, const float* nb_dist, const int32_t* nb_count, int64_t n, int k,
                             float eps, const int64_t* bucket_off, int64_t n_buckets, const float* precursor_mz_sorted,
                             const float* rt_sorted, double tol, int tol_is_da, double rt_tol, const int64_t* row_order,
@@ -1056,7 +1065,7 @@ int fal_cluster_graph_tiled(fal_ctx* ctx, const int32_t* nb_idx, const float* nb
                 "fal_cluster_graph_tiled: bad argument");
     FAL_REQUIRE(nb_count || n == 0, FAL_EINVAL, "fal_cluster_graph_tiled: NULL nb_count");
     FAL_REQUIRE(bucket_off && n_buckets >= 0, FAL_EINVAL, "fal_cluster_graph_tiled: NULL bucket table");
-    ctx->counters[10] = 0;
+    ctx->counters[10] = ctx->counters[11] = 0;
     std::vector<int32_t> tile_row;
     int64_t max_rows = 0;
     const char* sw = getenv("FALCON_GRAPH_TILED");
@@ -1073,13 +1082,13 @@ int fal_cluster_graph_tiled(fal_ctx* ctx, const int32_t* nb_idx, const float* nb
     hipStream_t st = ctx->stream;
     const int nt = (int)tile_row.size() - 1;
     int32_t* labels = labels_sorted_scratch;
-    // tile tables: tile_row[nt + 1] | cnt[3][nt] | base[3][nt + 1] | kept[nt] | fbase[nt + 1], then the int64 totals
+    // tile tables: tile_row[nt + 1] | cnt[4][nt] | base[4][nt + 1] | kept[nt] | fbase[nt + 1], then the int64 totals
     int32_t* tt = nullptr;
-    const size_t words = (size_t)(nt + 1) + 3 * (size_t)nt + 3 * (size_t)(nt + 1) + (size_t)nt + (size_t)(nt + 1);
-    FAL_TRY(ctx->reserve(SLOT_TILES, sizeof(int32_t) * (words + 2) + sizeof(int64_t) * 4, (void**)&tt));
-    int32_t *d_tile_row = tt, *cnt = d_tile_row + (nt + 1), *base = cnt + 3 * (size_t)nt, *kept = base + 3 * (size_t)(nt + 1),
+    const size_t words = (size_t)(nt + 1) + 4 * (size_t)nt + 4 * (size_t)(nt + 1) + (size_t)nt + (size_t)(nt + 1);
+    FAL_TRY(ctx->reserve(SLOT_TILES, sizeof(int32_t) * (words + 2) + sizeof(int64_t) * 5, (void**)&tt));
+    int32_t *d_tile_row = tt, *cnt = d_tile_row + (nt + 1), *base = cnt + 4 * (size_t)nt, *kept = base + 4 * (size_t)(nt + 1),
             *fbase = kept + nt;
-    int64_t* totals = reinterpret_cast<int64_t*>(tt + ((words + 1) & ~(size_t)1));     // [0] DBSCAN clusters, [1] members, [2] error, [3] clusters kept
+    int64_t* totals = reinterpret_cast<int64_t*>(tt + ((words + 1) & ~(size_t)1));     // [0] DBSCAN clusters, [1] members, [2] error, [3] overflowed lists, [4] clusters kept
     FAL_TRY(ctx->upload(d_tile_row, tile_row.data(), sizeof(int32_t) * (size_t)(nt + 1)));
     // a10's arrays (refine_dev's) and a11's
     const int64_t cmax = n + 1;
@@ -1092,19 +1101,15 @@ int fal_cluster_graph_tiled(fal_ctx* ctx, const int32_t* nb_idx, const float* nb
     FAL_TRY(ctx->reserve(SLOT_FIN, sizeof(int32_t) * (size_t)(n + 2), (void**)&noise));
     FAL_TRY(ctx->reserve(SLOT_FIN2, sizeof(unsigned long long) * (size_t)(cmax + 1), (void**)&best));
     FAL_TRY(ctx->reserve(SLOT_FIN3, sizeof(int64_t) * (size_t)(n + 1), (void**)&rank));
-    // Dynamic LDS: one size per launch, so EVERY workgroup of the call gets what the call's largest tile needs -- 16 B per row
-    // in both kernels, and in tile_dbscan_kernel another 16 B per row of edge list (four eps-edges a row; a smaller tile of the
-    // same launch has the rest of the block for its list) as far as the CU's 160 KB go: beyond 4,864 rows the list of the largest
-    // tile shrinks, to 6,144 edges at 8,192 rows, and a tile whose edges do not fit reads its core rows a second time.
+    // Dynamic LDS (tiles.h has the rule of tile_dbscan_kernel's and of its edge list): 16 B per row in tile_medoid_kernel.
     // Measured at 10 M spectra (profiles/NOTES.md): tiles of ~3,750 rows, 120 KB and one workgroup a CU, still halve the
     // dbscan stage of the per-row kernels.  Beyond 64 KB a kernel has to be told: a call with a bucket of more than 1,536 rows
     // pays two hipFuncSetAttribute calls on the host, in front of its first launch.
-    constexpr size_t kLdsMost = 16 * (size_t)kTileMaxRows + 24 * 1024;
-    const size_t lds_db = std::min<size_t>(32 * (size_t)max_rows, kLdsMost), lds_md = 16 * (size_t)max_rows;
+    const size_t lds_db = (size_t)tile_dbscan_lds_bytes(max_rows), lds_md = 16 * (size_t)max_rows;
     size_t lds_mem = 8;
     while (lds_mem < 4 * (size_t)max_rows) lds_mem <<= 1;
     if (lds_db > 48 * 1024) {
-        FAL_CHECK_HIP(hipFuncSetAttribute((const void*)tile_dbscan_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsMost));
+        FAL_CHECK_HIP(hipFuncSetAttribute((const void*)tile_dbscan_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kTileLdsMost));
         FAL_CHECK_HIP(hipFuncSetAttribute((const void*)tile_medoid_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 16 * kTileMaxRows));
     }
     ctx->stage_reset(ST_DBSCAN);
@@ -1113,7 +1118,7 @@ int fal_cluster_graph_tiled(fal_ctx* ctx, const int32_t* nb_idx, const float* nb
         StageScope ts(ctx, ST_DBSCAN);
         hipLaunchKernelGGL(tile_dbscan_kernel, dim3(nt), dim3(kTileThreads), lds_db, st, nb_idx, nb_dist, nb_count, n, k, eps,
                            d_tile_row, nt, (int)(lds_db / 4), labels, cnt);
-        hipLaunchKernelGGL(tile_scan_kernel, dim3(1), dim3(kTileThreads), 0, st, cnt, nt, 3, base, totals);
+        hipLaunchKernelGGL(tile_scan_kernel, dim3(1), dim3(kTileThreads), 0, st, cnt, nt, 4, base, totals);
     }
     {
         StageScope ts(ctx, ST_TAIL);
@@ -1122,22 +1127,23 @@ int fal_cluster_graph_tiled(fal_ctx* ctx, const int32_t* nb_idx, const float* nb
                            seg, totals, precursor_mz_sorted, rt_tol >= 0.0 ? rt_sorted : nullptr, tol, tol_is_da, rt_tol, S, sub,
                            n_sub, 1);
         hipLaunchKernelGGL(tile_kept_kernel, dim3(nt), dim3(256), 0, st, base, n_sub, kept);
-        hipLaunchKernelGGL(tile_scan_kernel, dim3(1), dim3(kTileThreads), 0, st, kept, nt, 1, fbase, totals + 3);
+        hipLaunchKernelGGL(tile_scan_kernel, dim3(1), dim3(kTileThreads), 0, st, kept, nt, 1, fbase, totals + 4);
         hipLaunchKernelGGL(tile_medoid_kernel, dim3(nt), dim3(kTileThreads), lds_md, st, nb_idx, nb_dist, nb_count, n, k, d_tile_row,
                            base, fbase, nt, n_sub, rows, sub, labels, row_order, noise, best);
         FAL_TRY(device_scan_i32(ctx, noise, n, rank, SLOT_TAIL3));
         hipLaunchKernelGGL(finalize_kernel, dim3((unsigned)std::min<int64_t>(ceil_div(n, 256), (int64_t)ctx->num_cus * 16)), dim3(256),
-                           0, st, labels, n, totals + 3, row_order, rank, best, labels_out, medoids_out);
+                           0, st, labels, n, totals + 4, row_order, rank, best, labels_out, medoids_out);
     }
     FAL_CHECK_HIP(hipGetLastError());
-    int64_t h[3] = {0, 0, 0};                  // tiles in error, clusters kept | noise rows
-    FAL_CHECK_HIP(hipMemcpyAsync(&h[0], totals + 2, 2 * sizeof(int64_t), hipMemcpyDeviceToHost, st));
-    FAL_CHECK_HIP(hipMemcpyAsync(&h[2], rank + n, sizeof(int64_t), hipMemcpyDeviceToHost, st));
+    int64_t h[4] = {0, 0, 0, 0};               // tiles in error, tiles with an overflowed list, clusters kept | noise rows
+    FAL_CHECK_HIP(hipMemcpyAsync(&h[0], totals + 2, 3 * sizeof(int64_t), hipMemcpyDeviceToHost, st));
+    FAL_CHECK_HIP(hipMemcpyAsync(&h[3], rank + n, sizeof(int64_t), hipMemcpyDeviceToHost, st));
     FAL_CHECK_HIP(hipStreamSynchronize(st));
+    ctx->counters[11] = h[1];
     FAL_REQUIRE(h[0] == 0, FAL_EINVAL, "fal_cluster_graph_tiled: a stored neighbour id lies outside its row's bucket tile "
                 "(%lld tile(s)): nb_idx and bucket_off do not describe the same partition", (long long)h[0]);
-    *n_clusters = h[1];
-    *n_labels = h[1] + h[2];
+    *n_clusters = h[2];
+    *n_labels = h[2] + h[3];
     return FAL_OK;
 }
 

@@ -24,6 +24,21 @@ namespace fal {
 constexpr int kTileRows = 1024;
 constexpr int kTileMaxRows = 8192;
 
+// Dynamic LDS of tile_dbscan_kernel.  One size per launch, so EVERY workgroup of the call gets what the call's largest tile
+// needs: 16 B per row of per-row state and another 16 B per row of edge list (four eps-edges a row), as far as the CU's 160 KB
+// go -- 16 B per row at kTileMaxRows plus 24 KB.  Beyond 4,864 rows the list of the largest tile shrinks, to 6,144 edges at
+// 8,192 rows; a smaller tile of the same launch has the rest of the block for its list.
+constexpr int64_t kTileLdsMost = 16 * (int64_t)kTileMaxRows + 24 * 1024;
+// -> bytes of dynamic LDS of a call whose largest tile has max_rows rows
+constexpr int64_t tile_dbscan_lds_bytes(int64_t max_rows) {
+    return 32 * max_rows < kTileLdsMost ? (max_rows > 0 ? 32 * max_rows : 0) : kTileLdsMost;
+}
+// -> eps-edges the list of a tile of m rows holds in a block of lds_bytes (what its 16 B per row leave, in 4-byte words); a
+//    tile with more eps-edges than that reads its core rows a second time.  Never negative.
+constexpr int64_t tile_edge_capacity(int64_t lds_bytes, int64_t m) {
+    return lds_bytes / 4 > 4 * m ? lds_bytes / 4 - 4 * m : 0;
+}
+
 // bucket_off[0 .. n_buckets]: ascending row offsets of the buckets, bucket_off[0] = 0, bucket_off[n_buckets] = n.
 // -> 0: tile_row = row offsets of the tiles (n_tiles + 1 entries, whole buckets, in order, covering [0, n); empty buckets
 //       belong to no tile), *max_rows = the largest tile

@@ -592,6 +592,13 @@ class Context:
         self.lib.fal_graph_tile_limits(C.byref(t), C.byref(m))
         return t.value, m.value
 
+    def graph_tile_capacity(self, max_rows: int, rows: int):
+        """-> (dynamic LDS bytes of the DBSCAN tile kernel in a call whose largest tile has `max_rows` rows, eps-edges the
+        list of a tile of `rows` rows holds in that call); `counter(11)` counts the tiles of a call that had more"""
+        b, c = C.c_int64(), C.c_int64()
+        self.lib.fal_graph_tile_capacity(int(max_rows), int(rows), C.byref(b), C.byref(c))
+        return b.value, c.value
+
     def cluster_graph(self, nb_idx, nb_dist, eps: float, mz_sorted, rt_sorted, tol: float, mode: str, rt_tol, order,
                       linkage: Optional[str] = None, nb_count=None, splits=None):
         """a9..a12 fused: -> labels i32[n] (dataset rows), medoids i32[n_labels], labels_sorted, n_clusters.

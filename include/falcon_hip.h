@@ -333,7 +333,9 @@ int fal_cluster_graph_counted(fal_ctx* ctx, const int32_t* nb_idx, const float* 
  * row's bucket (the search is bucket by bucket).  A stored id inside [0, n) but outside its row's tile is never followed and
  * fails the call with FAL_EINVAL; the context stays usable.  A bucket of more than max_tile_rows rows, or FALCON_GRAPH_TILED=0 in
  * the environment (read per call), sends the whole call down fal_cluster_graph_counted's path.
- * fal_ctx_counter(10): 1 when the last call ran per tile, 0 when it took that path. --- [dev] */
+ * fal_ctx_counter(10): 1 when the last call ran per tile, 0 when it took that path.
+ * fal_ctx_counter(11): the tiles of the last call whose eps-edges did not fit the tile's edge list in LDS
+ * (fal_graph_tile_capacity) and whose core rows were read a second time; 0 when the per-row path ran. --- [dev] */
 int fal_cluster_graph_tiled(fal_ctx* ctx, const int32_t* nb_idx, const float* nb_dist, const int32_t* nb_count,
                             int64_t n, int k, float eps, const int64_t* bucket_off /*[host]*/, int64_t n_buckets,
                             const float* precursor_mz_sorted, const float* rt_sorted,
@@ -342,6 +344,11 @@ int fal_cluster_graph_tiled(fal_ctx* ctx, const int32_t* nb_idx, const float* nb
                             int64_t* n_clusters /*[host]*/, int64_t* n_labels /*[host]*/);
 /* the rows that close a tile, and the most rows of one bucket the tiled path takes --- [host] */
 void fal_graph_tile_limits(int* tile_rows, int* max_tile_rows);
+/* *lds_bytes = the dynamic LDS of the DBSCAN tile kernel in a call whose largest tile has max_rows rows; *edge_capacity =
+ * the eps-edges (stored slots below the count that hold another row of the tile within eps, one per slot) a tile of `rows`
+ * rows of that call keeps in its list: 4 per row of the largest tile up to 4,864 rows, down to 6,144 at 8,192 rows, and a
+ * smaller tile of the same call has the rest of the block.  Either pointer may be NULL. --- [host] */
+void fal_graph_tile_capacity(int64_t max_rows, int64_t rows, int64_t* lds_bytes, int64_t* edge_capacity);
 
 /* ---- f4  hierarchical clustering of the neighbour graph: the clustering the reference snapshot ships,
  *          fcluster(fastcluster.linkage(pdist, linkage), distance_threshold, "distance") (cluster.py:283-290), on the

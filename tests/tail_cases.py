@@ -470,6 +470,113 @@ def graph_catches(name):
             "count": ("lt", "past_count", "highest", "lowest_cluster")}[name]
 
 
+def tile_table(sizes, tile_rows):
+    """row offsets of the bucket tiles of `fal_cluster_graph_tiled` for buckets of these sizes, none beyond the library's
+    largest tile: consecutive whole buckets; a bucket that would take the open tile over `tile_rows` closes it, unless the
+    tile is empty (test_tiles_cpu.py holds this against the library's builder)"""
+    rows, start, pos = [0], 0, 0
+    for s in sizes:
+        if pos + s - start > tile_rows and pos > start:
+            rows.append(pos)
+            start = pos
+        pos += int(s)
+    if pos > start:
+        rows.append(pos)
+    return np.array(rows, np.int64)
+
+
+def tile_eps_edges(idx, dist, nb_count, tile_rows, eps):
+    """eps-edges per tile as `tile_dbscan_kernel` counts them for its edge list: a slot below min(nb_count, k) that holds a row
+    of the row's own tile other than the row itself at float32 dist <= float32 eps; the same id twice in a row counts per slot"""
+    n, k = idx.shape
+    tile_rows = np.asarray(tile_rows, np.int64)
+    tile = np.searchsorted(tile_rows, np.arange(n), side="right") - 1
+    lo, hi = tile_rows[tile][:, None], tile_rows[tile + 1][:, None]
+    stored = np.arange(k)[None, :] < np.minimum(np.asarray(nb_count), k)[:, None]
+    j = idx.astype(np.int64)
+    edge = stored & (j >= lo) & (j < hi) & (j != np.arange(n)[:, None]) & (dist <= f32(eps))
+    return np.bincount(tile, weights=edge.sum(1), minlength=len(tile_rows) - 1).astype(np.int64)
+
+
+_NEAR = np.array([0.05, EPS32, EPS_DOWN, 0.01], f32)
+_FAR = np.array([0.5, EPS_UP, 0.11], f32)
+
+
+def _store_row(rng, idx, dist, i, lo, m, e, f):
+    """row i of a bucket [lo, lo + m): e + f distinct other rows of the bucket front-packed in random order, e of them within
+    EPS and f beyond -> the stored length"""
+    c = e + f
+    t = rng.choice(m - 1, c, replace=False) if c else np.zeros(0, np.int64)
+    idx[i, :c] = lo + t + (t >= i - lo)
+    d = rng.choice(_FAR, c)
+    d[rng.permutation(c)[:e]] = rng.choice(_NEAR, e)
+    dist[i, :c] = d
+    return c
+
+
+def density_graph(sizes, k, per_row, seed, hide=True):
+    """front-packed random rows, a row's neighbours drawn from its WHOLE bucket; bucket b holds round(per_row[b] * rows)
+    eps-edges at EPS the counts leave visible (fewer where its rows cannot store that many), unequally spread over the rows,
+    next to up to three neighbours beyond eps a row.  hide: rows % 11 == 0 have nb_count 0 in front of stored neighbours (any
+    number of them within eps) and full odd rows k + 2, as test_gpu_graph_tiled.bucket_graph has them.
+    -> idx, dist, nb_count, splits"""
+    rng = np.random.default_rng(seed)
+    per_row = np.broadcast_to(np.asarray(per_row, f64), (len(sizes),))
+    splits = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
+    n = int(splits[-1])
+    idx = np.full((n, k), -1, np.int32)
+    dist = np.full((n, k), np.inf, f32)
+    count = np.zeros(n, np.int32)
+    for b, m in enumerate(sizes):
+        lo, most = int(splits[b]), min(k, m - 1)
+        rows = np.arange(lo, lo + m)
+        hidden = (rows % 11 == 0) if hide else np.zeros(m, bool)
+        vis = np.flatnonzero(~hidden)
+        e = np.zeros(m, np.int64)
+        if len(vis) and most > 0:
+            E = min(int(round(per_row[b] * m)), len(vis) * most)
+            e[vis] = E // len(vis)
+            e[rng.choice(vis, E % len(vis), replace=False)] += 1
+            for a, c in rng.choice(vis, (m, 2)):                # one edge from row a to row c: the total stays
+                if e[a] > 0 and e[c] < most:
+                    e[a] -= 1
+                    e[c] += 1
+        e[hidden] = rng.integers(0, most + 1, int(hidden.sum()))
+        for li in range(m):
+            i = lo + li
+            c = _store_row(rng, idx, dist, i, lo, m, int(e[li]), int(min(most - e[li], rng.integers(0, 4))))
+            count[i] = 0 if hidden[li] else (k + 2 if c == k and i % 2 else c)
+    return idx, dist, count, splits
+
+
+def cut_graph(m, k, n_core, n_border, n_edges, seed):
+    """one bucket of m rows with EXACTLY n_edges eps-edges at EPS: n_core rows (rows 0 and m - 1 among them, the others
+    anywhere) store them, as evenly as n_edges divides, to rows drawn from the core rows and n_border further rows (core ->
+    core and core -> border edges); every other row is noise.  Rows % 3 == 0 with room keep one more row within eps BEHIND their
+    count; neighbours beyond eps fill some of the slots left.  -> idx, dist, nb_count"""
+    rng = np.random.default_rng(seed)
+    chosen = np.concatenate([[0, m - 1], 1 + rng.choice(m - 2, n_core + n_border - 2, replace=False)])
+    chosen[2:] = rng.permutation(chosen[2:])
+    core = chosen[:n_core]
+    idx = np.full((m, k), -1, np.int32)
+    dist = np.full((m, k), np.inf, f32)
+    count = np.zeros(m, np.int32)
+    e = np.full(n_core, n_edges // n_core)
+    e[rng.choice(n_core, n_edges % n_core, replace=False)] += 1
+    assert e.min() >= 1 and e.max() <= min(k, len(chosen) - 1)
+    for i, ei in zip(core.tolist(), e.tolist()):
+        pool = chosen[chosen != i]
+        f = int(min(k - ei, rng.integers(0, 3)))
+        near = rng.choice(pool, ei, replace=False)
+        t = np.concatenate([near, rng.choice(np.setdiff1d(np.arange(m), np.append(near, i)), f, replace=False)])
+        d = np.concatenate([rng.choice(_NEAR, ei), rng.choice(_FAR, f)])
+        o = rng.permutation(ei + f)
+        idx[i, :ei + f], dist[i, :ei + f], count[i] = t[o], d[o], ei + f
+        if i % 3 == 0 and ei + f < k:
+            idx[i, ei + f], dist[i, ei + f] = rng.choice(pool), f32(0.05)
+    return idx, dist, count
+
+
 # =========================================================================== a10 refinement
 def linkage_1d_ref(values, ppm, variant=None):
     """complete linkage of 1-D values: sort (stable), then m - 1 times merge the adjacent pair of segments with the smallest

@@ -1,11 +1,14 @@
 """The host tile-table builder of the tiled graph tail (`csrc/tiles.h`, plain C++) compiled on its own (tests/hostbuild.py):
-whole buckets, in order, covering [0, n), every tile within the limits, closed by the first bucket that would take it over."""
+whole buckets, in order, covering [0, n), every tile within the limits, closed by the first bucket that would take it over.
+And the capacity rule of the DBSCAN tile kernel's edge list (`tile_dbscan_lds_bytes`, `tile_edge_capacity`): the figures its
+comments state."""
 import ctypes as C
 
 import numpy as np
 import pytest
 
 from tests import hostbuild
+from tests import tail_cases as tc
 
 pytestmark = pytest.mark.skipif(not hostbuild.have_compiler(), reason="no host C++ compiler and no hipcc")
 
@@ -21,6 +24,12 @@ int t_tiles(const int64_t* off, int64_t nb, int64_t n, int64_t tile_rows, int64_
     for (size_t i = 0; i < v.size(); ++i) out[i] = v[i];
     return rc;
 }
+long long t_lds(long long max_rows) { return fal::tile_dbscan_lds_bytes(max_rows); }
+// out[m] = the edge capacity of a tile of m rows in a call whose largest tile has max_rows rows, m = 0 .. max_rows
+void t_caps(long long max_rows, long long* out) {
+    const int64_t b = fal::tile_dbscan_lds_bytes(max_rows);
+    for (long long m = 0; m <= max_rows; ++m) out[m] = fal::tile_edge_capacity(b, m);
+}
 }
 """
 
@@ -28,6 +37,13 @@ int t_tiles(const int64_t* off, int64_t nb, int64_t n, int64_t tile_rows, int64_
 @pytest.fixture(scope="module")
 def lib(tmp_path_factory):
     return hostbuild.compile_shim(tmp_path_factory.mktemp("tiles"), "tiles_shim", SHIM)
+
+
+def caps(lib, max_rows):
+    lib.t_lds.restype = C.c_longlong
+    out = np.zeros(max_rows + 1, np.int64)
+    lib.t_caps(C.c_longlong(max_rows), out.ctypes.data_as(C.c_void_p))
+    return int(lib.t_lds(C.c_longlong(max_rows))), out
 
 
 def tiles(lib, sizes, T, L):
@@ -66,6 +82,7 @@ def test_table_follows_the_rule(lib, sizes):
     rc, rows, mx, off = tiles(lib, sizes, T, L)
     assert rc == 0
     assert np.array_equal(rows, expected(sizes, T))
+    assert np.array_equal(rows, tc.tile_table(sizes, T))                           # (the copy the GPU tests count tiles with)
     assert rows[0] == 0 and rows[-1] == off[-1] and np.all(np.diff(rows) > 0)      # in order, covering [0, n), no empty tile
     assert np.all(np.isin(rows, off))                                              # whole buckets
     for a, b in zip(rows[:-1], rows[1:]):
@@ -93,3 +110,27 @@ def test_bucket_over_the_limit_and_bad_tables(lib):
     assert call(off, 9) == -1
     assert call(np.array([1, 4], np.int64), 4) == -1                                # does not start at 0
     assert call(np.array([0, 4], np.int64), 5) == -1                                # does not end at n
+
+
+def test_edge_capacity_figures(lib):
+    """what tiles.h and the driver say of the edge list: four eps-edges a row for the call's largest tile up to 4,864 rows,
+    shrinking from there to 6,144 edges at 8,192 rows; a smaller tile of the same call has the rest of the block (four more
+    edges for every row it is shorter); the block never exceeds the CU's 160 KB less the kernels' static words, always holds the
+    16 B per row of the largest tile, and no capacity is negative"""
+    L = lib.t_limits(1)
+    assert L == 8192
+    own, lds = np.zeros(L + 1, np.int64), np.zeros(L + 1, np.int64)
+    for mx in range(1, L + 1):
+        lds[mx], c = caps(lib, mx)
+        own[mx] = c[mx]
+        assert c.min() >= 0 and c[0] == lds[mx] // 4
+        assert np.all(np.diff(c) == -4)                                            # the rest of the block goes to a smaller tile
+        assert lds[mx] % 16 == 0 and 16 * mx <= lds[mx]
+    r = np.arange(L + 1)
+    assert np.array_equal(own[1:4865], 4 * r[1:4865])                              # four edges a row ...
+    assert own[4865] < 4 * 4865 and np.all(np.diff(own[4864:]) == -4)              # ... up to 4,864 rows, then shrinking
+    assert own[8192] == 6144 and own[4864] == own.max() == 19456
+    assert np.all(np.diff(lds[1:]) >= 0) and lds[L] == lds[4864] <= 160 * 1024 - 1024
+    assert caps(lib, 5000)[1][100] == lds[5000] // 4 - 400 >= 4000                 # a dense 100-row tile beside a 5,000-row one
+    assert caps(lib, 64)[1][64] == 256
+    assert caps(lib, 0)[0] == 0                                                    # an empty call asks for nothing
