@@ -24,6 +24,8 @@ MGF_FLAG_BYTES, MGF_FLAG_LINES, MGF_ST_HOST = 1, 2, 1
 # fal_mgf_write: the most bytes one number takes (csrc/mgfwrite.h kMgfNumMax)
 MGF_NUM_MAX = 23
 FAL_EINVAL = -1
+# fal_csv_*: the most bytes one number takes (csrc/csvwrite.h kCsvNumMax), the rows the merge sort's first pass sorts per block
+CSV_NUM_MAX, CSV_SORT_BLOCK = 19, 1024
 # fal_mzml_index / fal_mzml_parse: the same for mzML text (include/falcon_hip.h)
 MZML_FLAG_STRUCT, MZML_FLAG_MARKUP, MZML_FLAG_TAGS = 1, 2, 4
 MZML_ST_OK, MZML_ST_SKIP, MZML_ST_HOST = 0, 1, 2
@@ -127,6 +129,12 @@ _SIGNATURES = {
                              c_void_p, c_void_p, c_int64, c_void_p, c_void_p, P(c_int64)], c_int),
     "fal_mgf_write": ([c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_void_p,
                        c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int64, c_void_p, c_int64, c_void_p], c_int),
+    "fal_csv_order": ([c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_void_p, P(c_int64)], c_int),
+    "fal_csv_write_sizes": ([c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_int64,
+                             c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p, P(c_int64)], c_int),
+    "fal_csv_write": ([c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_int64,
+                       c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_void_p, c_int64, c_int64, c_void_p, c_int64,
+                       c_void_p], c_int),
     "fal_mzml_index": ([c_void_p, c_void_p, c_int64, P(c_int64)], c_int),
     "fal_mzml_parse": ([c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                         c_void_p, c_void_p], c_int),

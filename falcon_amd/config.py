@@ -94,6 +94,9 @@ class Config:
         p.add_argument("--mgf_writer", type=str, default="device", choices=["device", "host"],
                        help="--export_representatives: format the MGF text on the GPU (device), or with the host writer; the "
                             "file is the same byte for byte.")
+        p.add_argument("--csv_writer", type=str, default="device", choices=["device", "host"],
+                       help="Sort the rows of the cluster CSV and format their text on the GPU (device), or with the host "
+                            "writer; the file is the same byte for byte.")
         p.add_argument("--distributed", action="store_true",
                        help="Run as one rank of a multi-GPU job launched by `python -m torch.distributed.run --module "
                             "falcon_amd.falcon ...`: the precursor windows / buckets of every charge are dealt to the ranks, "
@@ -189,6 +192,8 @@ class Config:
             self._parser.error(f"--mzml_reader {ns['mzml_reader']}: device or host")
         if ns["mgf_writer"] not in ("device", "host"):
             self._parser.error(f"--mgf_writer {ns['mgf_writer']}: device or host")
+        if ns["csv_writer"] not in ("device", "host"):
+            self._parser.error(f"--csv_writer {ns['csv_writer']}: device or host")
         if ns["representatives"] == "consensus" and not ns["export_representatives"]:
             self._parser.error("--representatives consensus needs --export_representatives (there is no other output it changes)")
         if ns["assign_to"] is not None and isinstance(ns["assign_to"], str):

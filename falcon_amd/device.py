@@ -457,6 +457,102 @@ class Context:
             chunk = h_out[:need].numpy()
             yield chunk.copy() if copy else chunk
 
+    def csv_order(self, file_rank, ident, id_ptr):
+        """`fal_csv_order`: the rows of the cluster CSV sorted by (file_rank, natural order of the ASCII id, row) -> (order i32[n]
+        on the device, the longest digit run in an id).  file_rank i32[n]; ident: the ids' bytes, id_ptr i64[n + 1] their offsets.
+        Synchronises once.  FalconHipError (code `_lib.FAL_EINVAL`) when id_ptr does not ascend inside the blob."""
+        torch = _torch()
+        rank, ident, id_ptr = self.to_dev(file_rank, torch.int32), self._text_to_dev(ident), self.to_dev(id_ptr, torch.int64)
+        n = int(rank.shape[0])
+        if id_ptr.shape[0] != n + 1:
+            raise ValueError("csv_order: id_ptr needs one entry more than file_rank")
+        order = self.empty((max(n, 1),), torch.int32)
+        longest = C.c_int64(0)
+        check(self.lib.fal_csv_order(self._h, self._p(rank), self._p(ident) if ident.numel() else None, self._p(id_ptr), ident.numel(), n,
+                                     self._p(order), C.byref(longest)), "fal_csv_order")
+        return order[:n], int(longest.value)
+
+    def _csv_columns(self, file_id, file_names, file_name_ptr, ident, id_ptr, charge, precursor_mz, retention_time, cluster, order=None,
+                     quote_cr: Optional[bool] = None):
+        """the CSV writer's columns as device tensors of the entry points' types, checked against each other"""
+        torch = _torch()
+        if quote_cr is None:
+            from .ms_io.csv_io import host_quotes_cr
+            quote_cr = host_quotes_cr()
+        cols = dict(file_id=self.to_dev(file_id, torch.int32), fn=self._text_to_dev(file_names), fn_ptr=self.to_dev(file_name_ptr, torch.int64),
+                    id=self._text_to_dev(ident), id_ptr=self.to_dev(id_ptr, torch.int64), charge=self.to_dev(charge, torch.int32),
+                    precursor_mz=self.to_dev(precursor_mz, torch.float32), retention_time=self.to_dev(retention_time, torch.float32),
+                    cluster=self.to_dev(cluster, torch.int64), order=None if order is None else self.to_dev(order, torch.int32),
+                    quote_cr=int(bool(quote_cr)))
+        n = int(cols["file_id"].shape[0])
+        for name in ("charge", "precursor_mz", "retention_time", "cluster"):
+            if cols[name].shape[0] != n:
+                raise ValueError(f"format_csv: {name} has {cols[name].shape[0]} entries for {n} rows")
+        if cols["id_ptr"].shape[0] != n + 1 or cols["fn_ptr"].shape[0] < 1:
+            raise ValueError("format_csv: id_ptr needs one entry more than the rows, file_name_ptr at least one")
+        cols["rows"] = n if order is None else int(cols["order"].shape[0])
+        return cols
+
+    def _csv_column_args(self, c):
+        ptr = lambda t: self._p(t) if t is not None and t.numel() else None
+        return [ptr(c["order"]), c["rows"], ptr(c["file_id"]), ptr(c["fn"]), self._p(c["fn_ptr"]), c["fn_ptr"].shape[0] - 1, c["fn"].numel(),
+                ptr(c["id"]), self._p(c["id_ptr"]), c["id"].numel(), ptr(c["charge"]), ptr(c["precursor_mz"]), ptr(c["retention_time"]),
+                ptr(c["cluster"]), c["file_id"].shape[0], c["quote_cr"]]
+
+    def csv_write_sizes(self, cols):
+        """`fal_csv_write_sizes` of `_csv_columns` columns -> (sizes i64[rows], offsets i64[rows + 1] on the device, total bytes).
+        Synchronises once."""
+        torch = _torch()
+        rows = cols["rows"]
+        sizes, offsets = self.empty((max(rows, 1),), torch.int64), self.empty((rows + 1,), torch.int64)
+        total = C.c_int64(0)
+        check(self.lib.fal_csv_write_sizes(self._h, *self._csv_column_args(cols), self._p(sizes), self._p(offsets), C.byref(total)),
+              "fal_csv_write_sizes")
+        return sizes[:rows], offsets, int(total.value)
+
+    def csv_write(self, cols, offsets, first: int, last: int, out, host_out=None):
+        """`fal_csv_write`: the text of rows [first, last) into the uint8 device tensor (or view) `out`; `host_out`: a pinned uint8
+        host tensor of the same size that receives a copy.  Synchronises once.  FalconHipError (code `_lib.FAL_EINVAL`, nothing
+        written) when `out` is too small."""
+        if host_out is not None and (not host_out.is_pinned() or host_out.numel() != out.numel()):
+            raise ValueError("csv_write: host_out must be pinned and of out's size")
+        check(self.lib.fal_csv_write(self._h, *self._csv_column_args(cols), self._p(offsets), int(first), int(last),
+                                     self._p(out) if out.numel() else None, out.numel(),
+                                     self._p(host_out) if host_out is not None and out.numel() else None), "fal_csv_write")
+
+    def format_csv(self, file_id, file_names, file_name_ptr, ident, id_ptr, charge, precursor_mz, retention_time, cluster, order=None,
+                   max_bytes: Optional[int] = None, copy: bool = True, quote_cr: Optional[bool] = None):
+        """The rows of the cluster CSV, byte for byte what `falcon._write_cluster_info` writes below its header (DESIGN.md "Cluster
+        CSV out of the device"), as a generator of uint8 host arrays that together are the rows.  file_id i32[n] into the names
+        `file_names` (their encoded bytes) / `file_name_ptr` i64[files + 1]; ident / id_ptr i64[n + 1]: the spectrum ids; charge
+        i32[n] (0: None), precursor_mz / retention_time f32[n], cluster i64[n]; order i32: text row k is input row order[k] (what
+        `csv_order` gives; None: the rows as they are).  Arrays or device tensors.  Chunks are cut on row boundaries at about
+        `max_bytes` (default `mgf_io.DEFAULT_CHUNK_BYTES`); one larger row grows its chunk.  Every chunk is formatted into one
+        device buffer and copied through one pinned host buffer, with one stream synchronisation; `copy=False` yields views of
+        that pinned buffer, valid until the next chunk is asked for."""
+        torch = _torch()
+        if max_bytes is None:
+            from .ms_io.mgf_io import DEFAULT_CHUNK_BYTES as max_bytes
+        cols = self._csv_columns(file_id, file_names, file_name_ptr, ident, id_ptr, charge, precursor_mz, retention_time, cluster, order,
+                                 quote_cr)
+        n = cols["rows"]
+        if n == 0:
+            return
+        _, offsets, total = self.csv_write_sizes(cols)
+        off = offsets.cpu().numpy()
+        cuts = [0]                                   # (a loop over the chunks, not over the rows)
+        while cuts[-1] < n:
+            last = int(np.searchsorted(off, off[cuts[-1]] + max(int(max_bytes), 1), side="right")) - 1
+            cuts.append(min(max(last, cuts[-1] + 1), n))
+        cap = int(max(off[b] - off[a] for a, b in zip(cuts[:-1], cuts[1:])))
+        d_out = self.empty((max(cap, 1),), torch.uint8)
+        h_out = torch.empty((max(cap, 1),), dtype=torch.uint8, pin_memory=True)
+        for a, b in zip(cuts[:-1], cuts[1:]):
+            need = int(off[b] - off[a])
+            self.csv_write(cols, offsets, a, b, d_out[:need], h_out[:need])
+            chunk = h_out[:need].numpy()
+            yield chunk.copy() if copy else chunk
+
     def mzml_index(self, d_text):
         """`fal_mzml_index` of mzML text on the device (uint8 tensor) -> (spectra, tags inside spectra, `_lib.MZML_FLAG_*` bits,
         tags).  Synchronises once.  The tables stay in the context for the `mzml_parse` of the same tensor."""

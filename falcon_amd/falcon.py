@@ -28,7 +28,7 @@ import numpy as np
 from . import __version__
 from .cluster import cluster, spectrum
 from .config import config
-from .ms_io import mgf_io, ms_io
+from .ms_io import csv_io, mgf_io, ms_io
 
 logger = logging.getLogger("falcon")
 
@@ -89,6 +89,7 @@ def _run(args) -> int:
     logger.debug("mgf_reader = %s", config.mgf_reader)       # (no output depends on it: not an option line of the CSV header)
     logger.debug("mzml_reader = %s", config.mzml_reader)     # (the same)
     logger.debug("mgf_writer = %s", config.mgf_writer)       # (the same)
+    logger.debug("csv_writer = %s", config.csv_writer)       # (the same)
     if config.distributed:
         return _run_distributed()
 
@@ -102,6 +103,7 @@ def _run(args) -> int:
 
     ann = _ann_params()
     rows_all, current_label, representatives = [], 0, []
+    csv_blocks = [] if config.csv_writer == "device" else None       # column blocks instead of a tuple per spectrum
     library = {}
     if config.assign_to:
         library, current_label = _load_library(spectra_dir, pipe.ctx)
@@ -111,7 +113,7 @@ def _run(args) -> int:
         if n == 0:
             continue
         if charge in library:
-            part = _assign_charge(pipe, part, charge, library[charge], rows_all)
+            part = _assign_charge(pipe, part, charge, library[charge], rows_all, csv_blocks)
             if part is None:
                 continue                 # every spectrum of the charge went to an existing cluster
         ds = cluster.SpectrumDataset(part["precursor_mz"], part["retention_time"], part["mz"], part["intensity"],
@@ -120,8 +122,8 @@ def _run(args) -> int:
             ds, config.linkage, config.distance_threshold, config.min_matched_peaks, config.precursor_tol[0],
             config.precursor_tol[1], config.rt_tol, config.fragment_tol, config.batch_size, ann=ann, pipeline=pipe)
         current_label = _emit_charge(part, charge, labels, medoids, current_label, rows_all, representatives,
-                                     _consensus(pipe.ctx, part, charge, labels, medoids))
-    _write_outputs(rows_all, representatives, pipe.ctx)
+                                     _consensus(pipe.ctx, part, charge, labels, medoids), csv_blocks=csv_blocks)
+    _write_outputs(rows_all, representatives, pipe.ctx, csv_blocks=csv_blocks)
     if rm_work_dir:
         shutil.rmtree(config.work_dir)
     return 0
@@ -159,17 +161,21 @@ def _dataset(part):
     return cluster.SpectrumDataset(part["precursor_mz"], part["retention_time"], part["mz"], part["intensity"], part["indptr"])
 
 
-def _assign_charge(pipe, part, charge, lib, rows_all):
+def _assign_charge(pipe, part, charge, lib, rows_all, csv_blocks=None):
     """`--assign_to`, one charge: every spectrum whose nearest representative lies within the threshold takes that cluster's id
-    (its CSV row is written here) -> the partition of the spectra that are left (same columns, rows in order), None when
-    none is left"""
+    (its CSV row is written here: a tuple in `rows_all`, or with `csv_blocks` one column block for the device writer) -> the
+    partition of the spectra that are left (same columns, rows in order), None when none is left"""
     n = len(part["precursor_mz"])
     best_row, _, _, assigned = cluster.assign_to_library(
         _dataset(part), _dataset(lib), config.eps, config.precursor_tol[0], config.precursor_tol[1], config.rt_tol,
         config.fragment_tol, config.min_matched_peaks, pipeline=pipe)
     ids = lib["cluster"][best_row[assigned]]
     logger.info("Charge %s: assigned %d of %d spectra to %d existing clusters", charge, int(assigned.sum()), n, len(np.unique(ids)))
-    for i, cid in zip(np.flatnonzero(assigned), ids):
+    if csv_blocks is not None:
+        took = np.flatnonzero(assigned)
+        csv_blocks.append(csv_io.column_block(part["filename"][took], part["identifier"][took], charge, part["precursor_mz"][took],
+                                              part["retention_time"][took], np.asarray(ids, np.int64)))
+    for i, cid in zip(np.flatnonzero(assigned) if csv_blocks is None else (), ids):
         rows_all.append((str(part["filename"][i]), str(part["identifier"][i]), charge, np.float32(part["precursor_mz"][i]),
                          np.float32(part["retention_time"][i]), int(cid)))
     rest = np.flatnonzero(~assigned)
@@ -252,13 +258,17 @@ def _consensus(ctx, part, charge, labels, medoids):
     return indptr.cpu().numpy(), mz.cpu().numpy(), it.cpu().numpy()
 
 
-def _emit_charge(part, charge, labels, medoids, current_label, rows_all, representatives, consensus=None) -> int:
+def _emit_charge(part, charge, labels, medoids, current_label, rows_all, representatives, consensus=None, csv_blocks=None) -> int:
     """one charge's labels (by row of its partition) and medoid rows -> CSV rows and the charge's block of representatives; ->
-    the next label.  consensus (indptr, mz, intensity by cluster): the representatives' peaks; everything else stays the medoid's"""
+    the next label.  consensus (indptr, mz, intensity by cluster): the representatives' peaks; everything else stays the medoid's.
+    csv_blocks (a list): the CSV rows as one column block for the device writer instead of a tuple per spectrum in `rows_all`"""
     n = len(part["precursor_mz"])
     labels = labels + current_label                                                            # falcon.py:189-193
     current_label = int(labels.max()) + 1
-    for i in range(n):
+    if csv_blocks is not None:
+        csv_blocks.append(csv_io.column_block(part["filename"], part["identifier"], charge, part["precursor_mz"], part["retention_time"],
+                                              np.asarray(labels, np.int64)))
+    for i in range(n if csv_blocks is None else 0):
         # float32 columns keep their own (shortest round-trip) text form, as pandas' to_csv prints them
         rows_all.append((str(part["filename"][i]), str(part["identifier"][i]), charge,
                          np.float32(part["precursor_mz"][i]), np.float32(part["retention_time"][i]), int(labels[i])))
@@ -310,22 +320,59 @@ def _write_representatives(filename: str, blocks, ctx) -> None:
         ms_io.write_representatives(filename, ctx, *_block_columns(b), titles, append=True)
 
 
-def _write_outputs(rows_all, representatives, ctx=None) -> None:
+def _write_cluster_info_device(blocks, ctx) -> bool:
+    """the CSV of the column blocks through the device writer: the header as host text, the rows sorted and formatted on `ctx`
+    (`csv_io`) -> True; False, with one debug line and nothing written, where the file is the host writer's"""
+    why = "no device context" if ctx is None else None
+    cols = order = None
+    if why is None:
+        cols, why = csv_io.device_columns(blocks, _natural_key)
+    if why is None:
+        order = csv_io.sort_rows(ctx, cols)
+        if order is None:
+            why = "an identifier holds a digit run longer than int() takes"
+    if why is not None:
+        logger.debug("csv_writer: the host writer writes %s.csv: %s", config.output_filename, why)
+        return False
+    with open(f"{config.output_filename}.csv", "a", newline="") as f:
+        _write_csv_header(f)
+        f.flush()
+        csv_io.write_rows(f.buffer, ctx, cols, order)
+    return True
+
+
+def _write_outputs(rows_all, representatives, ctx=None, csv_blocks=None) -> None:
     """falcon.py:206-244: the CSV on a worker thread, the MGF of representatives on the calling one (the device writer runs on
-    `ctx`; a new thread would not inherit the device)"""
-    rows_all.sort(key=lambda r: (_natural_key(r[0]), _natural_key(r[1])))                      # falcon.py:206-208
-    n_clusters = len({r[5] for r in rows_all})
+    `ctx`; a new thread would not inherit the device).  csv_blocks: the CSV's rows as column blocks (`--csv_writer device`):
+    sorted and formatted on `ctx`, on the calling thread too, or turned into tuples where the host writer has to write them"""
+    if csv_blocks:
+        n_rows = len(rows_all) + sum(len(b["cluster"]) for b in csv_blocks)
+        n_clusters = len(np.unique(np.concatenate([np.asarray(b["cluster"], np.int64) for b in csv_blocks] +
+                                                  [np.array([r[5] for r in rows_all], np.int64)])))
+    else:
+        n_rows, n_clusters = len(rows_all), len({r[5] for r in rows_all})
     logger.info("Export cluster assignments of %d spectra to %d unique clusters to output file %s",
-                len(rows_all), n_clusters, f"{config.output_filename}.csv")
+                n_rows, n_clusters, f"{config.output_filename}.csv")
+    if csv_blocks is not None:
+        if not rows_all and _write_cluster_info_device(csv_blocks, ctx):
+            if config.export_representatives:
+                _export_representatives(representatives, ctx)
+            return
+        rows_all = list(rows_all) + list(csv_io.block_tuples(csv_blocks))
+    rows_all.sort(key=lambda r: (_natural_key(r[0]), _natural_key(r[1])))                      # falcon.py:206-208
     csv_worker = threading.Thread(target=_write_cluster_info, args=(rows_all,), daemon=True)
     csv_worker.start()
     try:
         if config.export_representatives:
-            logger.info("Export %d cluster representative spectra to output file %s",
-                        sum(len(b["rows"]) for b in representatives), f"{config.output_filename}.mgf")
-            _write_representatives(f"{config.output_filename}.mgf", representatives, ctx)
+            _export_representatives(representatives, ctx)
     finally:
         csv_worker.join()
+
+
+def _export_representatives(representatives, ctx) -> None:
+    logger.info("Export %d cluster representative spectra to output file %s",
+                sum(len(b["rows"]) for b in representatives), f"{config.output_filename}.mgf")
+    _write_representatives(f"{config.output_filename}.mgf", representatives, ctx)
 
 
 def _run_distributed() -> int:
@@ -390,9 +437,11 @@ def _run_distributed() -> int:
             runner.close()
         if rank == 0:
             rows_all, current_label, representatives = [], 0, []
-            # a context of rank 0's own for the consensus and for the device writer, as for the preparation of the partitions
+            csv_blocks = [] if config.csv_writer == "device" else None
+            # a context of rank 0's own for the consensus and for the device writers, as for the preparation of the partitions
             out_ctx = None
-            if config.export_representatives and (config.representatives == "consensus" or config.mgf_writer == "device"):
+            if csv_blocks is not None or (config.export_representatives and
+                                          (config.representatives == "consensus" or config.mgf_writer == "device")):
                 from .device import Context
                 out_ctx = Context(device)
             try:
@@ -400,8 +449,9 @@ def _run_distributed() -> int:
                     if len(labels):
                         cons = (_consensus(out_ctx, part, charge, labels, medoids)
                                 if out_ctx is not None and config.representatives == "consensus" else None)
-                        current_label = _emit_charge(part, charge, labels, medoids, current_label, rows_all, representatives, cons)
-                _write_outputs(rows_all, representatives, out_ctx)
+                        current_label = _emit_charge(part, charge, labels, medoids, current_label, rows_all, representatives, cons,
+                                                     csv_blocks=csv_blocks)
+                _write_outputs(rows_all, representatives, out_ctx, csv_blocks=csv_blocks)
             finally:
                 if out_ctx is not None:
                     out_ctx.close()
@@ -558,17 +608,23 @@ def _prepare_spectra(spectra_dir: str, min_mz: float, max_mz: float, ctx) -> Lis
     return sorted(parts, key=_natural_key)
 
 
+def _write_csv_header(f):
+    """the `#` lines and the column row -> the csv writer that wrote it"""
+    import csv
+    f.write(f"# falcon version {__version__}\n")
+    for line in _option_lines():
+        f.write(f"# {line}\n")
+    f.write("#\n")
+    w = csv.writer(f, quoting=csv.QUOTE_MINIMAL, lineterminator="\n")
+    w.writerow(csv_io.COLUMNS)
+    return w
+
+
 def _write_cluster_info(rows) -> None:
     """falcon.py:483-524: `#` header block with every option, then the CSV table (pandas `to_csv` conventions:
     minimal quoting with doubled quotes, float32 columns in their shortest round-trip form)."""
-    import csv
     with open(f"{config.output_filename}.csv", "a", newline="") as f:
-        f.write(f"# falcon version {__version__}\n")
-        for line in _option_lines():
-            f.write(f"# {line}\n")
-        f.write("#\n")
-        w = csv.writer(f, quoting=csv.QUOTE_MINIMAL, lineterminator="\n")
-        w.writerow(["filename", "spectrum_id", "precursor_charge", "precursor_mz", "retention_time", "cluster"])
+        w = _write_csv_header(f)
         for fn, sid, charge, pmz, rt, lab in rows:
             w.writerow([fn, sid, charge, str(np.float32(pmz)), str(np.float32(rt)), lab])
 

@@ -505,6 +505,38 @@ int fal_mgf_write(fal_ctx* ctx, const float* mz, const float* intensity, const i
                   const int64_t* cluster, const uint8_t* title, const int64_t* title_ptr, int64_t title_bytes,
                   const int64_t* offsets, int64_t first, int64_t last, uint8_t* out, int64_t out_bytes, uint8_t* host_out);
 
+/* ---- the cluster CSV's columns -> the order of its rows and their text (the device writer; DESIGN.md "Cluster CSV out of the
+ *          device" states the key order, the number form and the quoting; falcon_amd/falcon.py's sort by _natural_key and its
+ *          _write_cluster_info are what it mirrors: for the same rows the order and the bytes are equal).
+ * n rows, n < 2^31.  id u8[id_bytes] with id_ptr i64[n + 1]: row r's spectrum id, ASCII bytes [id_ptr[r], id_ptr[r + 1]).
+ * fal_csv_order: order_out i32[n] = the rows sorted by (file_rank[r], natural order of the id, r): text runs as byte strings (a
+ *          proper prefix first), digit runs as integers of any length, ids that differ only in leading zeros equal -- the stable
+ *          sort of the host.  *max_digit_run_out (host): the longest run of digits in an id.  A stable merge sort of the row
+ *          indices whose first pass sorts blocks of FAL_CSV_SORT_BLOCK rows.  FAL_EINVAL when id_ptr does not ascend inside the
+ *          blob; nothing outside the blob is ever read.  One stream synchronisation, in front of the sort.
+ * The text's row k is input row order[k] (order i32[rows]; NULL: row k, rows <= n): "<file name>,<id>,<charge>,<precursor_mz>,
+ *          <retention_time>,<cluster>\n" with file_id i32[n] into the names fn u8[fn_bytes] / fn_ptr i64[n_files + 1], charge i32[n]
+ *          (0: None), precursor_mz / retention_time f32[n] as str(np.float32(x)) (at most 19 bytes), cluster i64[n]; the two text
+ *          fields under csv.QUOTE_MINIMAL (a field with ',', '"' or '\n' -- and '\r' when quote_cr is set -- in quotes, its
+ *          quotes doubled).
+ * fal_csv_write_sizes -> sizes_out i64[rows], offsets_out i64[rows + 1] (their exclusive scan, the total last) and *total_out
+ *          (host).  One stream synchronisation.  FAL_EINVAL when an order entry, a file id or a byte range lies outside its array.
+ * fal_csv_write: the text of rows [first, last) into out[0, out_bytes) at offsets[k] - offsets[first].  out needs no alignment.
+ *          FAL_EINVAL, and nothing written, when out_bytes < offsets[last] - offsets[first]; no byte outside a row's own range
+ *          is ever stored, whatever the offsets hold.  host_out: NULL, or pinned host memory of out_bytes bytes that receives a
+ *          copy of out before the call's one stream synchronisation.  No host work per row. ---------------------------- [dev] */
+#define FAL_CSV_SORT_BLOCK 1024
+int fal_csv_order(fal_ctx* ctx, const int32_t* file_rank, const uint8_t* id, const int64_t* id_ptr, int64_t id_bytes, int64_t n,
+                  int32_t* order_out, int64_t* max_digit_run_out);
+int fal_csv_write_sizes(fal_ctx* ctx, const int32_t* order, int64_t rows, const int32_t* file_id, const uint8_t* fn, const int64_t* fn_ptr,
+                        int64_t n_files, int64_t fn_bytes, const uint8_t* id, const int64_t* id_ptr, int64_t id_bytes,
+                        const int32_t* charge, const float* precursor_mz, const float* retention_time, const int64_t* cluster, int64_t n,
+                        int quote_cr, int64_t* sizes_out, int64_t* offsets_out, int64_t* total_out);
+int fal_csv_write(fal_ctx* ctx, const int32_t* order, int64_t rows, const int32_t* file_id, const uint8_t* fn, const int64_t* fn_ptr,
+                  int64_t n_files, int64_t fn_bytes, const uint8_t* id, const int64_t* id_ptr, int64_t id_bytes, const int32_t* charge,
+                  const float* precursor_mz, const float* retention_time, const int64_t* cluster, int64_t n, int quote_cr,
+                  const int64_t* offsets, int64_t first, int64_t last, uint8_t* out, int64_t out_bytes, uint8_t* host_out);
+
 /* ---- mzML structure -> per-spectrum columns + the tables of fal_decode_peaks (the device reader; DESIGN.md "mzML on the
  *          device" states the grammar; falcon_amd/ms_io/mzml_io.read_chunks is the reader it mirrors and the one that decides
  *          whatever it leaves open).
