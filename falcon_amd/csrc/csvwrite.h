@@ -9,12 +9,8 @@
 // digit runs compare as integers of any length (leading zeros dropped, then the longer is larger, then bytewise).  Keys that
 // differ only in leading zeros are equal: 0.
 //
-// Numbers.  A float32 x becomes the bytes of str(np.float32(x)): numpy's Dragon4 in its "unique" mode, the shortest digits
-// inside the float32's own rounding interval (half a float32 ulp on each side, half of that below a power of two with a biased
-// exponent above 1; the ends count when the significand is even: they read back), the nearest to x among them, exact ties to
-// even.  This is Ryu's rule (Adams 2018) for float32, and the digits come from mgfwrite.h's 128-bit multiply and power-of-five
-// tables: the significand is held as m 2^31 in units of 2^(e - 31), so that the half ulp is the integer 2^30 and the binary
-// exponent stays inside the range the tables were cut for ([-180, 73] here).
+// Numbers.  A float32 x becomes the bytes of str(np.float32(x)): the shortest digits inside the float32's own rounding interval
+// (numtext.h's num_shortest_f32), in numpy's layout.
 //   layout : positional when 1e-4 <= |x| < 1e16 as doubles ("0.0001", "12.5", "9999999000000000.0"), otherwise d[.ddd]e[+-]XX;
 //            the float32 nearest 1e-4 lies below it ("1e-04"), the one nearest 1e16 above it ("1e+16").  "nan", "inf", "-inf",
 //            "0.0", "-0.0".
@@ -25,7 +21,7 @@
 // doubled.  A row is <filename>,<spectrum_id>,<charge>,<precursor_mz>,<retention_time>,<cluster>\n; charge 0 prints None.
 #pragma once
 #include <stdint.h>
-#include "mgfwrite.h"
+#include "numtext.h"
 
 namespace fal {
 
@@ -73,101 +69,15 @@ __host__ __device__ inline int64_t csv_max_digit_run(const uint8_t* a, int64_t l
     return best;
 }
 
-// the shortest digits of a finite, non-zero float32 (sign dropped) inside its own rounding interval
-__host__ __device__ __forceinline__ MgfDecimal csv_shortest(uint32_t bits) {
-    const uint32_t frac = bits & 0x7FFFFFu;
-    const int be = (int)((bits >> 23) & 0xFF);
-    const uint32_t m = be == 0 ? frac : frac | 0x800000u;        // value = m 2^e
-    const int e = be == 0 ? -149 : be - 150;
-    const int e2 = e - 31;
-    const uint64_t mv = (uint64_t)m << 31;                       // in units of 2^e2: the half ulp is 2^30
-    const uint64_t mp = mv + (uint64_t(1) << 30);
-    const uint64_t mm = mv - (uint64_t(1) << ((frac == 0 && be > 1) ? 29 : 30));
-    const bool accept = (m & 1u) == 0;                           // an even significand: a decimal on an end of the interval reads back
-    uint64_t vr, vp, vm;
-    int e10;
-    bool vr_tz = false, vp_exact = false, vm_exact = false;      // vr / vp / vm are whole numbers before any digit is removed
-    if (e2 >= 0) {
-        const int q = (int)(((uint32_t)e2 * 78913u) >> 18) - (e2 > 3);
-        e10 = q;
-        const int k = 125 + (int)(((uint32_t)q * 1217359u) >> 19);
-        const int j = -e2 + q + k;
-        vr = mgf_mul_shift(mv, kMgfPow5Inv[q], j);
-        vp = mgf_mul_shift(mp, kMgfPow5Inv[q], j);
-        vm = mgf_mul_shift(mm, kMgfPow5Inv[q], j);
-        vr_tz = mgf_multiple_of_pow5(mv, q);
-        vp_exact = mgf_multiple_of_pow5(mp, q);
-        vm_exact = mgf_multiple_of_pow5(mm, q);
-    } else {
-        const int q = (int)(((uint32_t)-e2 * 732923u) >> 20) - (-e2 > 1);
-        e10 = q + e2;
-        const int i = -e2 - q;
-        const int k = (int)(((uint32_t)i * 1217359u) >> 19) + 1 - 125;
-        const int j = q - k;
-        vr = mgf_mul_shift(mv, kMgfPow5[i], j);
-        vp = mgf_mul_shift(mp, kMgfPow5[i], j);
-        vm = mgf_mul_shift(mm, kMgfPow5[i], j);
-        if (q < 63) {
-            const uint64_t mask = (uint64_t(1) << q) - 1;
-            vr_tz = (mv & mask) == 0;
-            vp_exact = (mp & mask) == 0;
-            vm_exact = (mm & mask) == 0;
-        }
-    }
-    vp -= vp_exact && !accept;                                   // the upper end itself is not taken
-    bool vm_tz = vm_exact && accept;                             // the lower end itself may be
-    int removed = 0;
-    uint32_t last = 0;
-    uint64_t out;
-    if (vm_tz || vr_tz) {
-        while (vp / 10 > vm / 10) {
-            vm_tz &= vm % 10 == 0;
-            vr_tz &= last == 0;
-            last = (uint32_t)(vr % 10);
-            vr /= 10;
-            vp /= 10;
-            vm /= 10;
-            ++removed;
-        }
-        if (vm_tz) {
-            while (vm % 10 == 0) {
-                vr_tz &= last == 0;
-                last = (uint32_t)(vr % 10);
-                vr /= 10;
-                vp /= 10;
-                vm /= 10;
-                ++removed;
-            }
-        }
-        if (vr_tz && last == 5 && vr % 2 == 0) last = 4;         // exactly half: to even
-        out = vr + ((vr == vm && !vm_tz) || last >= 5);
-    } else {
-        bool up = false;
-        while (vp / 10 > vm / 10) {
-            up = vr % 10 >= 5;
-            vr /= 10;
-            vp /= 10;
-            vm /= 10;
-            ++removed;
-        }
-        out = vr + (vr == vm || up);
-    }
-    MgfDecimal d;
-    d.digits = out;
-    d.n = mgf_uint_len(out);
-    d.decpt = e10 + removed + d.n;
-    return d;
-}
-
 // a number made ready once: its length and its text come from the same digits
 struct CsvNum {
-    MgfDecimal d;
+    NumDecimal d;
     int kind;                    // 0: digits, 1: zero, 2: inf, 3: nan
     bool neg, positional;
 };
 
 __host__ __device__ __forceinline__ CsvNum csv_num(float x) {
-    const uint32_t bits = mgf_float_bits(x);
+    const uint32_t bits = num_float_bits(x);
     CsvNum v;
     v.d.digits = 0;
     v.d.n = v.d.decpt = 0;
@@ -180,7 +90,7 @@ __host__ __device__ __forceinline__ CsvNum csv_num(float x) {
         v.kind = 1;
     } else {
         v.kind = 0;
-        v.d = csv_shortest(bits);
+        v.d = num_shortest_f32(bits);
         const double a = (double)__builtin_bit_cast(float, bits & 0x7FFFFFFFu);
         v.positional = a >= 1e-4 && a < 1e16;
     }
@@ -188,16 +98,16 @@ __host__ __device__ __forceinline__ CsvNum csv_num(float x) {
 }
 
 __host__ __device__ __forceinline__ int csv_num_len(const CsvNum& v) {
-    return (int)v.neg + (v.kind ? 3 : mgf_decimal_len(v.d, v.positional));
+    return (int)v.neg + (v.kind ? 3 : num_decimal_len(v.d, v.positional));
 }
 
 // (room for kCsvNumMax bytes) -> the length
 __host__ __device__ __forceinline__ int csv_write_num(uint8_t* dst, const CsvNum& v) {
     int at = 0;
     if (v.neg) dst[at++] = '-';
-    if (v.kind == 0) return at + mgf_write_decimal(dst + at, v.d, v.positional);
+    if (v.kind == 0) return at + num_write_decimal(dst + at, v.d, v.positional);
     const char* w = v.kind == 1 ? "0.0" : v.kind == 2 ? "inf" : "nan";
-    return at + mgf_put(dst + at, w, 3);
+    return at + num_put(dst + at, w, 3);
 }
 
 __host__ __device__ __forceinline__ int csv_num_len(float x) { return csv_num_len(csv_num(x)); }
@@ -231,16 +141,6 @@ __host__ __device__ inline int64_t csv_write_field(uint8_t* dst, const uint8_t* 
     return at;
 }
 
-__host__ __device__ __forceinline__ int csv_int_len(int64_t v) { return (v < 0) + mgf_uint_len(mgf_abs64(v)); }
-
-__host__ __device__ __forceinline__ int csv_write_int(uint8_t* dst, int64_t v) {
-    const uint64_t a = mgf_abs64(v);
-    const int n = mgf_uint_len(a);
-    if (v < 0) dst[0] = '-';
-    mgf_write_uint(dst + (v < 0), a, n);
-    return (v < 0) + n;
-}
-
 // one row with its numbers made ready and its text fields measured (fn_len / id_len: csv_field_len of the two)
 struct CsvRow {
     const uint8_t* fn;
@@ -268,8 +168,8 @@ __host__ __device__ inline CsvRow csv_row(const uint8_t* fn, int64_t fn_n, const
 }
 
 __host__ __device__ inline int64_t csv_row_len(const CsvRow& r) {
-    return r.fn_len + r.id_len + (r.charge == 0 ? 4 : csv_int_len(r.charge)) + csv_num_len(r.pm) + csv_num_len(r.rt) +
-           csv_int_len(r.cluster) + 6;
+    return r.fn_len + r.id_len + (r.charge == 0 ? 4 : num_int_len(r.charge)) + csv_num_len(r.pm) + csv_num_len(r.rt) +
+           num_int_len(r.cluster) + 6;
 }
 
 // the row at dst (room for csv_row_len bytes) -> its length
@@ -278,13 +178,13 @@ __host__ __device__ inline int64_t csv_write_row(uint8_t* dst, const CsvRow& r) 
     dst[at++] = ',';
     at += csv_write_field(dst + at, r.id, r.id_n, r.id_len);
     dst[at++] = ',';
-    at += r.charge == 0 ? mgf_put(dst + at, "None", 4) : csv_write_int(dst + at, r.charge);
+    at += r.charge == 0 ? num_put(dst + at, "None", 4) : num_write_int(dst + at, r.charge);
     dst[at++] = ',';
     at += csv_write_num(dst + at, r.pm);
     dst[at++] = ',';
     at += csv_write_num(dst + at, r.rt);
     dst[at++] = ',';
-    at += csv_write_int(dst + at, r.cluster);
+    at += num_write_int(dst + at, r.cluster);
     dst[at++] = '\n';
     return at;
 }

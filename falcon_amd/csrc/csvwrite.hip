@@ -11,19 +11,16 @@
 //
 // fal_csv_write (one synchronisation, at its end): a lane per row, a wave per tile of 64 consecutive rows.  A round measures the
 // rows again (the digits are made once per round and kept for the text), places them in the wave's LDS tile at a wave prefix sum
-// of their lengths -- as many leading rows as the tile takes -- and the lanes format their rows there.  The tile stands for the
-// 16-byte aligned stretch of the output around the round's first byte, so it is flushed with one 16-byte store per lane and unit;
-// only the bytes in front of the first aligned unit and behind the last one -- at most 15 each, units shared with the neighbouring
-// tiles -- go out as single bytes.  A row that no tile takes (longer than kCsvTile - 15 bytes) is written by its lane alone,
-// straight into its own range.  Every row's length is checked against offsets[k + 1] - offsets[k] and every round's range against
-// [0, offsets[last] - offsets[first]] <= out_bytes before anything of it is stored.
+// of their lengths -- as many leading rows as the tile takes -- and the lanes format their rows there.  The tile is textwrite.h's
+// Tile around the round's first byte, flushed whole at the round's end.  A row that no tile takes (longer than kCsvTile - 15
+// bytes) is written by its lane alone, straight into its own range.  Every row's length is checked against
+// offsets[k + 1] - offsets[k] and every round's range against [0, offsets[last] - offsets[first]] <= out_bytes before anything of
+// it is stored.
 #include <algorithm>
 #include <rocprim/device/device_merge_sort.hpp>
 #include "common.h"
 #include "csvwrite.h"
-#include "ivf.h"
-#include "textscan.h"
-#include "util.h"
+#include "textwrite.h"
 
 namespace fal {
 namespace {
@@ -34,7 +31,6 @@ static_assert(kCsvTile % 16 == 0 && kCsvTile >= 64 * (kCsvFixedMax + 16), "a til
 static_assert(kCsvSortBlock == FAL_CSV_SORT_BLOCK, "the header states the sort's block size");
 // block sort of 256 threads x 4 rows; merge path from 16,384 rows on (below: the odd-even merge)
 using CsvSortConfig = rocprim::merge_sort_config<256, 256, kCsvSortBlock / 256, 128, 128, 4, (1 << 14)>;
-enum { CW_BAD_INPUT = 1, CW_TOO_SMALL = 2, CW_OVERFLOW = 4 };      // meta[META_FLAGS] bits
 enum { META_DIGITS = 2 };                                            // meta word: the longest digit run
 
 struct CsvColumns {
@@ -95,7 +91,7 @@ __global__ __launch_bounds__(256) void csv_check_ids_kernel(const uint8_t* __res
         if (a < 0 || b < a || b > id_bytes) bad = true;
         else longest = std::max<unsigned long long>(longest, (unsigned long long)csv_max_digit_run(id + a, b - a));
     }
-    if (bad) atomicOr(&meta[META_FLAGS], (unsigned long long)CW_BAD_INPUT);
+    if (bad) atomicOr(&meta[META_FLAGS], (unsigned long long)TW_BAD_INPUT);
     if (longest) atomicMax(&meta[META_DIGITS], longest);
 }
 
@@ -126,7 +122,7 @@ __global__ __launch_bounds__(256) void csv_write_sizes_kernel(CsvColumns c, int6
         sizes[k] = bad ? 0 : csv_row_len(r);
         any_bad |= bad;
     }
-    if (any_bad) atomicOr(&meta[META_FLAGS], (unsigned long long)CW_BAD_INPUT);
+    if (any_bad) atomicOr(&meta[META_FLAGS], (unsigned long long)TW_BAD_INPUT);
 }
 
 // ---- write: a lane per row, a wave per tile of 64 rows -----------------------------------------------------------------------------
@@ -137,7 +133,7 @@ __global__ __launch_bounds__(256) void csv_write_kernel(CsvColumns c, const int6
     uint8_t* tile = tiles[threadIdx.x >> 6];
     const int64_t base = offsets[first], need = offsets[last] - base;
     if (need < 0 || need > out_bytes) {                                          // uniform over the grid: nothing is written
-        if (blockIdx.x == 0 && threadIdx.x == 0) atomicOr(&meta[META_FLAGS], (unsigned long long)CW_TOO_SMALL);
+        if (blockIdx.x == 0 && threadIdx.x == 0) atomicOr(&meta[META_FLAGS], (unsigned long long)TW_TOO_SMALL);
         return;
     }
     const int64_t waves = (int64_t)gridDim.x * (blockDim.x >> 6), n_tiles = (last - first + 63) / 64;
@@ -157,7 +153,7 @@ __global__ __launch_bounds__(256) void csv_write_kernel(CsvColumns c, const int6
             }
             const int64_t g0 = offsets[r] - base;
             if (__ballot(bad) != 0ull || g0 < 0 || g0 > need) {                 // columns or offsets that are not the sizing pass's
-                if (lane == 0) atomicOr(&meta[META_FLAGS], (unsigned long long)CW_BAD_INPUT);
+                if (lane == 0) atomicOr(&meta[META_FLAGS], (unsigned long long)TW_BAD_INPUT);
                 break;
             }
             const int mis = (int)(reinterpret_cast<uintptr_t>(out + g0) & 15);
@@ -168,29 +164,21 @@ __global__ __launch_bounds__(256) void csv_write_kernel(CsvColumns c, const int6
             if (cnt == 0) {                                                      // row r alone is longer than a tile
                 const int64_t len0 = __shfl((long long)len, 0, 64);
                 if (g0 + len0 > need) {
-                    if (lane == 0) atomicOr(&meta[META_FLAGS], (unsigned long long)CW_BAD_INPUT);
+                    if (lane == 0) atomicOr(&meta[META_FLAGS], (unsigned long long)TW_BAD_INPUT);
                     break;
                 }
-                if (lane == 0 && csv_write_row(out + g0, row) != len0) atomicOr(&meta[META_FLAGS], (unsigned long long)CW_OVERFLOW);
+                if (lane == 0 && csv_write_row(out + g0, row) != len0) atomicOr(&meta[META_FLAGS], (unsigned long long)TW_OVERFLOW);
                 r += 1;
                 continue;
             }
             const int total = __shfl(incl, cnt - 1, 64);
             if (g0 + total > need) {
-                if (lane == 0) atomicOr(&meta[META_FLAGS], (unsigned long long)CW_BAD_INPUT);
+                if (lane == 0) atomicOr(&meta[META_FLAGS], (unsigned long long)TW_BAD_INPUT);
                 break;
             }
-            if (lane < cnt && csv_write_row(tile + mis + incl - clen, row) != len) atomicOr(&meta[META_FLAGS], (unsigned long long)CW_OVERFLOW);
-            wave_lds_sync();
-            // tile[i] is the byte at gbase + i, gbase 16-byte aligned; [mis, hi) is this round's text
-            uint8_t* gbase = out + g0 - mis;
-            const int hi = mis + total;
-            const int u0 = (mis + 15) >> 4, u1 = hi >> 4;                        // the complete 16-byte units [u0, u1)
-            const int head_end = std::min(u0 << 4, hi);
-            if (mis + lane < head_end) gbase[mis + lane] = tile[mis + lane];     // in front of the first aligned unit: < 16 bytes
-            for (int u = u0 + lane; u < u1; u += 64) *reinterpret_cast<uint4*>(gbase + 16 * u) = *reinterpret_cast<const uint4*>(tile + 16 * u);
-            const int rest = std::max(u1 << 4, head_end);                        // behind the last complete unit: < 16 bytes
-            if (rest + lane < hi) gbase[rest + lane] = tile[rest + lane];
+            if (lane < cnt && csv_write_row(tile + mis + incl - clen, row) != len) atomicOr(&meta[META_FLAGS], (unsigned long long)TW_OVERFLOW);
+            Tile text{tile, out + g0 - mis, out + g0 + total, mis, mis + total, false};       // [mis, mis + total): this round's text
+            tile_flush(text, true, lane);
             wave_lds_sync();                                                     // (the next round writes the tile again)
             r += cnt;
         }
@@ -205,16 +193,6 @@ int check_columns(const char* who, fal_ctx* ctx, const int32_t* file_id, const i
     FAL_REQUIRE(ctx && n >= 0 && n < (int64_t(1) << 31) && rows >= 0 && n_files >= 0 && fn_bytes >= 0 && id_bytes >= 0, FAL_EINVAL,
                 "%s: bad argument", who);
     FAL_REQUIRE(rows == 0 || (n > 0 && file_id && fn_ptr && id_ptr && charge && pm && rt && cluster), FAL_EINVAL, "%s: NULL column", who);
-    return FAL_OK;
-}
-
-int read_flags(fal_ctx* ctx, const unsigned long long* meta, const int64_t* extra, unsigned long long** host) {
-    unsigned long long* h = nullptr;
-    FAL_TRY(ctx->pinned_reserve(sizeof(unsigned long long) * (META_WORDS + 1), (void**)&h));
-    FAL_CHECK_HIP(hipMemcpyAsync(h, meta, sizeof(unsigned long long) * META_WORDS, hipMemcpyDeviceToHost, ctx->stream));
-    if (extra) FAL_CHECK_HIP(hipMemcpyAsync(h + META_WORDS, extra, sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream));
-    FAL_CHECK_HIP(hipStreamSynchronize(ctx->stream));
-    *host = h;
     return FAL_OK;
 }
 
@@ -241,9 +219,9 @@ extern "C" int fal_csv_order(fal_ctx* ctx, const int32_t* file_rank, const uint8
     FAL_CHECK_HIP(hipMemsetAsync(meta, 0, 64, ctx->stream));
     hipLaunchKernelGGL(csv_check_ids_kernel, dim3(capped_grid(ctx, n, 256)), dim3(256), 0, ctx->stream, id, id_ptr, id_bytes, n, iota, meta);
     FAL_CHECK_HIP(hipGetLastError());
-    unsigned long long* h = nullptr;
-    FAL_TRY(read_flags(ctx, meta, nullptr, &h));
-    FAL_REQUIRE(!(h[META_FLAGS] & CW_BAD_INPUT), FAL_EINVAL, "fal_csv_order: id_ptr not ascending inside the id blob");
+    const unsigned long long* h = nullptr;
+    FAL_TRY(read_meta(ctx, meta, &h));
+    FAL_REQUIRE(!(h[META_FLAGS] & TW_BAD_INPUT), FAL_EINVAL, "fal_csv_order: id_ptr not ascending inside the id blob");
     *max_digit_run_out = (int64_t)h[META_DIGITS];
     FAL_CHECK_HIP(rocprim::merge_sort<CsvSortConfig>(scratch + sort_at, sort_bytes, iota, order_out, (size_t)n, less, ctx->stream));
     return FAL_OK;
@@ -265,19 +243,12 @@ extern "C" int fal_csv_write_sizes(fal_ctx* ctx, const int32_t* order, int64_t r
         return FAL_OK;
     }
     unsigned long long* meta = nullptr;
-    FAL_TRY(ctx->reserve(SLOT_CSVW, 64, (void**)&meta));
-    FAL_CHECK_HIP(hipMemsetAsync(meta, 0, 64, ctx->stream));
+    FAL_TRY(writer_meta(ctx, SLOT_CSVW, &meta));
     const CsvColumns c{order, file_id, fn, fn_ptr, n_files, fn_bytes, id, id_ptr, id_bytes, charge, precursor_mz, retention_time, cluster, n,
                        quote_cr != 0};
     hipLaunchKernelGGL(csv_write_sizes_kernel, dim3(capped_grid(ctx, rows, 256)), dim3(256), 0, ctx->stream, c, rows, sizes_out, meta);
-    FAL_CHECK_HIP(hipGetLastError());
-    FAL_TRY(device_scan_i64(ctx, sizes_out, rows, offsets_out, SLOT_SORT));
-    unsigned long long* h = nullptr;
-    FAL_TRY(read_flags(ctx, meta, offsets_out + rows, &h));
-    FAL_REQUIRE(!(h[META_FLAGS] & CW_BAD_INPUT), FAL_EINVAL,
-                "fal_csv_write_sizes: an order entry or a file id outside its range, or fn_ptr / id_ptr not ascending inside their blobs");
-    *total_out = (int64_t)h[META_WORDS];
-    return FAL_OK;
+    return finish_sizes(ctx, meta, sizes_out, rows, offsets_out, total_out,
+                        "fal_csv_write_sizes: an order entry or a file id outside its range, or fn_ptr / id_ptr not ascending inside their blobs");
 }
 
 extern "C" int fal_csv_write(fal_ctx* ctx, const int32_t* order, int64_t rows, const int32_t* file_id, const uint8_t* fn, const int64_t* fn_ptr,
@@ -292,20 +263,10 @@ extern "C" int fal_csv_write(fal_ctx* ctx, const int32_t* order, int64_t rows, c
                     (fn || fn_bytes == 0) && (id || id_bytes == 0),
                 FAL_EINVAL, "fal_csv_write: bad argument");
     unsigned long long* meta = nullptr;
-    FAL_TRY(ctx->reserve(SLOT_CSVW, 64, (void**)&meta));
-    FAL_CHECK_HIP(hipMemsetAsync(meta, 0, 64, ctx->stream));
+    FAL_TRY(writer_meta(ctx, SLOT_CSVW, &meta));
     const CsvColumns c{order, file_id, fn, fn_ptr, n_files, fn_bytes, id, id_ptr, id_bytes, charge, precursor_mz, retention_time, cluster, n,
                        quote_cr != 0};
     hipLaunchKernelGGL(csv_write_kernel, dim3(capped_grid(ctx, ceil_div(std::max<int64_t>(last - first, 1), (int64_t)64), 4)), dim3(256), 0,
                        ctx->stream, c, offsets, first, last, out, out_bytes, meta);
-    FAL_CHECK_HIP(hipGetLastError());
-    if (host_out && out_bytes > 0) FAL_CHECK_HIP(hipMemcpyAsync(host_out, out, (size_t)out_bytes, hipMemcpyDeviceToHost, ctx->stream));
-    unsigned long long* h = nullptr;
-    FAL_TRY(read_flags(ctx, meta, nullptr, &h));
-    FAL_REQUIRE(!(h[META_FLAGS] & CW_TOO_SMALL), FAL_EINVAL, "fal_csv_write: %lld bytes are too few for rows [%lld, %lld)",
-                (long long)out_bytes, (long long)first, (long long)last);
-    FAL_REQUIRE(!(h[META_FLAGS] & CW_BAD_INPUT), FAL_EINVAL,
-                "fal_csv_write: offsets that are no scan of the rows' sizes, or columns that are not those of fal_csv_write_sizes");
-    FAL_REQUIRE(!(h[META_FLAGS] & CW_OVERFLOW), FAL_EINTERNAL, "fal_csv_write: a row's text is not the size fal_csv_write_sizes gave");
-    return FAL_OK;
+    return finish_write(ctx, meta, "fal_csv_write", "rows", "a row", first, last, out, out_bytes, host_out);
 }

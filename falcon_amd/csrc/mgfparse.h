@@ -16,13 +16,7 @@
 // the host reader.  Whitespace is space, tab, CR, LF: the device grammar admits no other byte str.strip() strips.
 #pragma once
 #include <stdint.h>
-#ifndef __HIPCC__            // plain host compiler (the CPU tests' shim): the qualifiers mean nothing there
-#ifndef __host__
-#define __host__
-#define __device__
-#define __forceinline__ inline
-#endif
-#endif
+#include "numtext.h"          // the 128-bit multiply; the qualifiers for a plain host compiler (the CPU tests' shim)
 
 namespace fal {
 
@@ -113,14 +107,6 @@ __host__ __device__ __forceinline__ uint64_t mgf_pow5(int k) {          // k <= 
     uint64_t v = 1;
     for (int i = 0; i < k; ++i) v *= 5;
     return v;
-}
-
-__host__ __device__ __forceinline__ void mgf_mul128(uint64_t a, uint64_t b, uint64_t* hi, uint64_t* lo) {
-    const uint64_t a0 = (uint32_t)a, a1 = a >> 32, b0 = (uint32_t)b, b1 = b >> 32;
-    const uint64_t p00 = a0 * b0, p01 = a0 * b1, p10 = a1 * b0, p11 = a1 * b1;
-    const uint64_t mid = (p00 >> 32) + (uint32_t)p01 + (uint32_t)p10;
-    *lo = (mid << 32) | (uint32_t)p00;
-    *hi = p11 + (p01 >> 32) + (p10 >> 32) + (mid >> 32);
 }
 
 __host__ __device__ __forceinline__ double mgf_from_bits(uint64_t u) { return __builtin_bit_cast(double, u); }
@@ -215,7 +201,7 @@ __host__ __device__ __forceinline__ bool mgf_parse_double(const uint8_t* p, int 
     }
     if (q >= 0) {
         uint64_t hi, lo;
-        mgf_mul128(w, p5, &hi, &lo);
+        num_mul128(w, p5, &hi, &lo);
         *out = mgf_round128(hi, lo, false, q, neg);
         return true;
     }

@@ -1,13 +1,8 @@
-// MGF text out of the device: the pure per-number and per-entry functions of the writer.  Shared by mgfwrite.hip's kernels and the
-// host build of the CPU tests (tests/hostbuild_mgfwrite.py); they mirror falcon_amd/ms_io/mgf_io.write_spectra, which stays the
-// writer of record: for the same entries the bytes are the same.
+// MGF text out of the device: the entry layout of the writer, on numtext.h's digits and number text.  Shared by mgfwrite.hip's
+// kernels and the host build of the CPU tests (tests/hostbuild_mgfwrite.py); they mirror falcon_amd/ms_io/mgf_io.write_spectra,
+// which stays the writer of record: for the same entries the bytes are the same.
 //
-// Numbers.  A float32 x becomes the bytes of Python's repr(float(x)): the shortest decimal that reads back as the widened double
-// (nearest to it among the shortest, ties to even), in repr's layout.  The digits are Ryu's (Adams 2018) for the double, cut down
-// to what float32 inputs need: the significand is 24 bits shifted up to 53, the binary exponent of the integer significand lies
-// in [-201, 75], so the two tables of 128-bit powers of five shrink to 22 + 64 entries (tools/gen_mgfwrite_pow5.py prints them
-// from exact integers).  The interval is the double's: half a double ulp on each side, both ends included (the low significand
-// bits are zero: even), and half of that below a power of two.  There is no "not decided" case: every bit pattern has its text.
+// Numbers.  A float32 x becomes the bytes of Python's repr(float(x)): num_shortest_widened's digits in repr's layout.
 //   layout : decpt = position of the decimal point in front of the digits' first; -4 < decpt <= 16 positional ("0.000ddd", "dd.dd",
 //            "dd00.0"), otherwise d[.ddd]e[+-]XX with at least two exponent digits; "-0.0", "nan" (any NaN), "inf", "-inf".
 //   length : at most 17 digits; sign + "0.000" + 17 digits = sign + 17 digits + '.' + "e-XX" = 23 bytes = kMgfNumMax.
@@ -17,7 +12,7 @@
 // fields behind the title (mgf_field_*) and a peak line (mgf_peak_*); mgf_entry_len / mgf_write_entry put them together serially.
 #pragma once
 #include <stdint.h>
-#include "mgfparse.h"
+#include "numtext.h"
 
 namespace fal {
 
@@ -27,296 +22,25 @@ constexpr int kMgfHeadLen = 17;                      // "BEGIN IONS\nTITLE="
 constexpr int kMgfTailLen = 10;                      // "END IONS\n\n"
 constexpr int kMgfFields = 4;                        // "\nPEPMASS=..\n", "CHARGE=..\n" or nothing, "RTINSECONDS=..\n", "CLUSTER=..\n"
 constexpr int kMgfFieldMax = 12 + kMgfNumMax + 1;    // the longest of them (RTINSECONDS)
-constexpr int kMgfPow5InvCount = 22, kMgfPow5Count = 64;
-
-// ---- GENERATED by tools/gen_mgfwrite_pow5.py: {low, high} words -----------------------------------------------------------------
-static constexpr uint64_t kMgfPow5Inv[22][2] = {
-    {0x0000000000000001ull, 0x2000000000000000ull},
-    {0x999999999999999aull, 0x1999999999999999ull},
-    {0x47ae147ae147ae15ull, 0x147ae147ae147ae1ull},
-    {0x6c8b4395810624deull, 0x10624dd2f1a9fbe7ull},
-    {0x7a786c226809d496ull, 0x1a36e2eb1c432ca5ull},
-    {0x61f9f01b866e43abull, 0x14f8b588e368f084ull},
-    {0xb4c7f34938583622ull, 0x10c6f7a0b5ed8d36ull},
-    {0x87a6520ec08d236aull, 0x1ad7f29abcaf4857ull},
-    {0x9fb841a566d74f88ull, 0x15798ee2308c39dfull},
-    {0xe62d01511f12a607ull, 0x112e0be826d694b2ull},
-    {0xd6ae6881cb5109a4ull, 0x1b7cdfd9d7bdbab7ull},
-    {0xdef1ed34a2a73aeaull, 0x15fd7fe17964955full},
-    {0x7f27f0f6e885c8bbull, 0x119799812dea1119ull},
-    {0x650cb4be40d60df8ull, 0x1c25c268497681c2ull},
-    {0xea70909833de7193ull, 0x16849b86a12b9b01ull},
-    {0x21f3a6e0297ec143ull, 0x1203af9ee756159bull},
-    {0x6985d7cd0f313537ull, 0x1cd2b297d889bc2bull},
-    {0x2137dfd73f5a90f9ull, 0x170ef54646d49689ull},
-    {0xe75fe645cc4873faull, 0x12725dd1d243aba0ull},
-    {0xa5663d3c7a0d865dull, 0x1d83c94fb6d2ac34ull},
-    {0x511e976394d79eb1ull, 0x179ca10c9242235dull},
-    {0xda7edf82dd794bc1ull, 0x12e3b40a0e9b4f7dull},
-};
-static constexpr uint64_t kMgfPow5[64][2] = {
-    {0x0000000000000000ull, 0x1000000000000000ull},
-    {0x0000000000000000ull, 0x1400000000000000ull},
-    {0x0000000000000000ull, 0x1900000000000000ull},
-    {0x0000000000000000ull, 0x1f40000000000000ull},
-    {0x0000000000000000ull, 0x1388000000000000ull},
-    {0x0000000000000000ull, 0x186a000000000000ull},
-    {0x0000000000000000ull, 0x1e84800000000000ull},
-    {0x0000000000000000ull, 0x1312d00000000000ull},
-    {0x0000000000000000ull, 0x17d7840000000000ull},
-    {0x0000000000000000ull, 0x1dcd650000000000ull},
-    {0x0000000000000000ull, 0x12a05f2000000000ull},
-    {0x0000000000000000ull, 0x174876e800000000ull},
-    {0x0000000000000000ull, 0x1d1a94a200000000ull},
-    {0x0000000000000000ull, 0x12309ce540000000ull},
-    {0x0000000000000000ull, 0x16bcc41e90000000ull},
-    {0x0000000000000000ull, 0x1c6bf52634000000ull},
-    {0x0000000000000000ull, 0x11c37937e0800000ull},
-    {0x0000000000000000ull, 0x16345785d8a00000ull},
-    {0x0000000000000000ull, 0x1bc16d674ec80000ull},
-    {0x0000000000000000ull, 0x1158e460913d0000ull},
-    {0x0000000000000000ull, 0x15af1d78b58c4000ull},
-    {0x0000000000000000ull, 0x1b1ae4d6e2ef5000ull},
-    {0x0000000000000000ull, 0x10f0cf064dd59200ull},
-    {0x0000000000000000ull, 0x152d02c7e14af680ull},
-    {0x0000000000000000ull, 0x1a784379d99db420ull},
-    {0x0000000000000000ull, 0x108b2a2c28029094ull},
-    {0x0000000000000000ull, 0x14adf4b7320334b9ull},
-    {0x4000000000000000ull, 0x19d971e4fe8401e7ull},
-    {0x8800000000000000ull, 0x1027e72f1f128130ull},
-    {0xaa00000000000000ull, 0x1431e0fae6d7217cull},
-    {0xd480000000000000ull, 0x193e5939a08ce9dbull},
-    {0xc9a0000000000000ull, 0x1f8def8808b02452ull},
-    {0xbe04000000000000ull, 0x13b8b5b5056e16b3ull},
-    {0xad85000000000000ull, 0x18a6e32246c99c60ull},
-    {0xd8e6400000000000ull, 0x1ed09bead87c0378ull},
-    {0x878fe80000000000ull, 0x13426172c74d822bull},
-    {0x6973e20000000000ull, 0x1812f9cf7920e2b6ull},
-    {0x03d0da8000000000ull, 0x1e17b84357691b64ull},
-    {0x8262889000000000ull, 0x12ced32a16a1b11eull},
-    {0x22fb2ab400000000ull, 0x178287f49c4a1d66ull},
-    {0xabb9f56100000000ull, 0x1d6329f1c35ca4bfull},
-    {0xcb54395ca0000000ull, 0x125dfa371a19e6f7ull},
-    {0xbe2947b3c8000000ull, 0x16f578c4e0a060b5ull},
-    {0x2db399a0ba000000ull, 0x1cb2d6f618c878e3ull},
-    {0xfc90400474400000ull, 0x11efc659cf7d4b8dull},
-    {0x7bb4500591500000ull, 0x166bb7f0435c9e71ull},
-    {0xdaa16406f5a40000ull, 0x1c06a5ec5433c60dull},
-    {0xa8a4de8459868000ull, 0x118427b3b4a05bc8ull},
-    {0xd2ce16256fe82000ull, 0x15e531a0a1c872baull},
-    {0x87819baecbe22800ull, 0x1b5e7e08ca3a8f69ull},
-    {0xf4b1014d3f6d5900ull, 0x111b0ec57e6499a1ull},
-    {0x71dd41a08f48af40ull, 0x1561d276ddfdc00aull},
-    {0x0e549208b31adb10ull, 0x1aba4714957d300dull},
-    {0x28f4db456ff0c8eaull, 0x10b46c6cdd6e3e08ull},
-    {0x33321216cbecfb24ull, 0x14e1878814c9cd8aull},
-    {0xbffe969c7ee839edull, 0x1a19e96a19fc40ecull},
-    {0xf7ff1e21cf512434ull, 0x105031e2503da893ull},
-    {0xf5fee5aa43256d41ull, 0x14643e5ae44d12b8ull},
-    {0x337e9f14d3eec892ull, 0x197d4df19d605767ull},
-    {0x005e46da08ea7ab6ull, 0x1fdca16e04b86d41ull},
-    {0xa03aec4845928cb2ull, 0x13e9e4e4c2f34448ull},
-    {0xc849a75a56f72fdeull, 0x18e45e1df3b0155aull},
-    {0x7a5c1130ecb4fbd6ull, 0x1f1d75a5709c1ab1ull},
-    {0xec798abe93f11d65ull, 0x13726987666190aeull},
-};
-// ---- end of the generated block ------------------------------------------------------------------------------------------------
-
-struct MgfDecimal {          // 0.d1 d2 .. dn x 10^decpt, d1 != 0
-    uint64_t digits;
-    int n, decpt;
-};
-
-__host__ __device__ __forceinline__ uint32_t mgf_float_bits(float x) { return __builtin_bit_cast(uint32_t, x); }
-
-__host__ __device__ __forceinline__ int mgf_uint_len(uint64_t v) {
-    int n = 1;
-    while (v >= 10) {
-        v /= 10;
-        ++n;
-    }
-    return n;
-}
-
-// decimal digits of v, most significant first, at dst[0 .. n)
-__host__ __device__ __forceinline__ void mgf_write_uint(uint8_t* dst, uint64_t v, int n) {
-    for (int i = n - 1; i >= 0; --i) {
-        dst[i] = (uint8_t)('0' + (uint32_t)(v % 10));
-        v /= 10;
-    }
-}
-
-// (m (mul[1] 2^64 + mul[0])) >> j, 64 < j < 128; m below 2^55
-__host__ __device__ __forceinline__ uint64_t mgf_mul_shift(uint64_t m, const uint64_t* mul, int j) {
-    uint64_t hi1, lo1, hi0, lo0;
-    mgf_mul128(m, mul[1], &hi1, &lo1);
-    mgf_mul128(m, mul[0], &hi0, &lo0);
-    const uint64_t sum = hi0 + lo1;
-    if (sum < hi0) ++hi1;
-    const int d = j - 64;
-    return (hi1 << (64 - d)) | (sum >> d);
-}
-
-__host__ __device__ __forceinline__ bool mgf_multiple_of_pow5(uint64_t v, int p) {
-    int c = 0;
-    while (v % 5 == 0 && c < p) {          // v != 0
-        v /= 5;
-        ++c;
-    }
-    return c >= p;
-}
-
-// the shortest digits of a finite, non-zero float32 (sign dropped) read as a double
-__host__ __device__ __forceinline__ MgfDecimal mgf_shortest(uint32_t bits) {
-    uint32_t frac = bits & 0x7FFFFFu;
-    int be = (int)((bits >> 23) & 0xFF);
-    int e;                                                       // value = mant 2^e, mant in [2^23, 2^24)
-    uint32_t mant;
-    if (be == 0) {                                               // float32 denormal: a normal double
-        const int lz = __builtin_clz(frac) - 8;
-        mant = frac << lz;
-        e = -149 - lz;
-    } else {
-        mant = frac | 0x800000u;
-        e = be - 150;
-    }
-    const uint64_t m2 = (uint64_t)mant << 29;                    // the double's 53-bit significand
-    const int e2 = e - 29 - 2;
-    const uint64_t mv = 4 * m2;
-    const uint32_t mm_shift = mant != 0x800000u;                 // a power of two: the gap below is half as wide
-    uint64_t vr, vp, vm;
-    int e10;
-    bool vm_tz = false, vr_tz = false;                           // "trailing zeros": the removed digits of vm / vr were all 0
-    if (e2 >= 0) {
-        const int q = (int)(((uint32_t)e2 * 78913u) >> 18) - (e2 > 3);           // floor(log10(2^e2)), less one
-        e10 = q;
-        const int k = 125 + (int)(((uint32_t)q * 1217359u) >> 19);               // 125 + bitlength(5^q) - 1
-        const int j = -e2 + q + k;
-        vr = mgf_mul_shift(mv, kMgfPow5Inv[q], j);
-        vp = mgf_mul_shift(mv + 2, kMgfPow5Inv[q], j);
-        vm = mgf_mul_shift(mv - 1 - mm_shift, kMgfPow5Inv[q], j);
-        if (mv % 5 == 0) vr_tz = mgf_multiple_of_pow5(mv, q);                    // (q <= 21 always: 5^q below 2^55 can divide)
-        else vm_tz = mgf_multiple_of_pow5(mv - 1 - mm_shift, q);
-    } else {
-        const int q = (int)(((uint32_t)-e2 * 732923u) >> 20) - (-e2 > 1);        // floor(log10(5^-e2)), less one
-        e10 = q + e2;
-        const int i = -e2 - q;
-        const int k = (int)(((uint32_t)i * 1217359u) >> 19) + 1 - 125;           // bitlength(5^i) - 125
-        const int j = q - k;
-        vr = mgf_mul_shift(mv, kMgfPow5[i], j);
-        vp = mgf_mul_shift(mv + 2, kMgfPow5[i], j);
-        vm = mgf_mul_shift(mv - 1 - mm_shift, kMgfPow5[i], j);
-        if (q <= 1) {
-            vr_tz = true;                                                        // mv = 4 m2 is a multiple of 2^q
-            vm_tz = mm_shift == 1;                                               // mv - 2 is even, mv - 1 is not
-        } else if (q < 63) {
-            vr_tz = (mv & ((uint64_t(1) << q) - 1)) == 0;
-        }
-    }
-    int removed = 0;
-    uint32_t last = 0;
-    uint64_t out;
-    if (vm_tz || vr_tz) {
-        while (vp / 10 > vm / 10) {
-            vm_tz &= vm % 10 == 0;
-            vr_tz &= last == 0;
-            last = (uint32_t)(vr % 10);
-            vr /= 10;
-            vp /= 10;
-            vm /= 10;
-            ++removed;
-        }
-        if (vm_tz) {
-            while (vm % 10 == 0) {
-                vr_tz &= last == 0;
-                last = (uint32_t)(vr % 10);
-                vr /= 10;
-                vp /= 10;
-                vm /= 10;
-                ++removed;
-            }
-        }
-        if (vr_tz && last == 5 && vr % 2 == 0) last = 4;                         // exactly half: to even
-        out = vr + ((vr == vm && !vm_tz) || last >= 5);
-    } else {
-        bool up = false;
-        while (vp / 10 > vm / 10) {
-            up = vr % 10 >= 5;
-            vr /= 10;
-            vp /= 10;
-            vm /= 10;
-            ++removed;
-        }
-        out = vr + (vr == vm || up);
-    }
-    MgfDecimal d;
-    d.digits = out;
-    d.n = mgf_uint_len(out);
-    d.decpt = e10 + removed + d.n;
-    return d;
-}
+// numtext.h's tables under the names this writer's CPU tests (tests/hostbuild_mgfwrite.py) read them by
+constexpr int kMgfPow5InvCount = kNumPow5InvCount, kMgfPow5Count = kNumPow5Count;
+constexpr const uint64_t (&kMgfPow5Inv)[22][2] = kNumPow5Inv, (&kMgfPow5)[64][2] = kNumPow5;
 
 __host__ __device__ __forceinline__ bool mgf_positional(int decpt) { return decpt > -4 && decpt <= 16; }
 
-// bytes of the digits in repr's layout, positional or with an exponent (the sign is not counted)
-__host__ __device__ __forceinline__ int mgf_decimal_len(const MgfDecimal& d, bool positional) {
-    if (positional) return d.decpt <= 0 ? 2 - d.decpt + d.n : d.decpt < d.n ? d.n + 1 : d.decpt + 2;
-    const int ex = d.decpt - 1, ax = ex < 0 ? -ex : ex;
-    return d.n + (d.n > 1) + 2 + (ax < 10 ? 2 : mgf_uint_len((uint64_t)ax));
-}
-
-// the digits at dst in that layout -> their length
-__host__ __device__ __forceinline__ int mgf_write_decimal(uint8_t* dst, const MgfDecimal& d, bool positional) {
-    uint64_t v = d.digits;
-    if (positional) {
-        if (d.decpt <= 0) {                                      // 0.000ddd
-            dst[0] = '0';
-            dst[1] = '.';
-            for (int i = 0; i < -d.decpt; ++i) dst[2 + i] = '0';
-            mgf_write_uint(dst + 2 - d.decpt, v, d.n);
-            return 2 - d.decpt + d.n;
-        }
-        if (d.decpt < d.n) {                                     // dd.ddd
-            for (int i = d.n - 1; i >= 0; --i) {
-                dst[i + (i >= d.decpt)] = (uint8_t)('0' + (uint32_t)(v % 10));
-                v /= 10;
-            }
-            dst[d.decpt] = '.';
-            return d.n + 1;
-        }
-        mgf_write_uint(dst, v, d.n);                             // dd00.0
-        for (int i = d.n; i < d.decpt; ++i) dst[i] = '0';
-        dst[d.decpt] = '.';
-        dst[d.decpt + 1] = '0';
-        return d.decpt + 2;
-    }
-    for (int i = d.n - 1; i >= 0; --i) {                         // d[.ddd]e+XX
-        dst[i + (i >= 1)] = (uint8_t)('0' + (uint32_t)(v % 10));
-        v /= 10;
-    }
-    if (d.n > 1) dst[1] = '.';
-    int at = d.n + (d.n > 1);
-    const int ex = d.decpt - 1, ax = ex < 0 ? -ex : ex;
-    dst[at] = 'e';
-    dst[at + 1] = ex < 0 ? '-' : '+';
-    const int xn = ax < 10 ? 2 : mgf_uint_len((uint64_t)ax);
-    mgf_write_uint(dst + at + 2, (uint64_t)ax, xn);
-    return at + 2 + xn;
-}
-
 // bytes of repr(float(x))
 __host__ __device__ __forceinline__ int mgf_num_len(float x) {
-    const uint32_t bits = mgf_float_bits(x);
+    const uint32_t bits = num_float_bits(x);
     const int neg = (int)(bits >> 31);
     if ((bits & 0x7F800000u) == 0x7F800000u) return (bits & 0x7FFFFFu) ? 3 : 3 + neg;
     if ((bits & 0x7FFFFFFFu) == 0) return 3 + neg;
-    const MgfDecimal d = mgf_shortest(bits);
-    return neg + mgf_decimal_len(d, mgf_positional(d.decpt));
+    const NumDecimal d = num_shortest_widened(bits);
+    return neg + num_decimal_len(d, mgf_positional(d.decpt));
 }
 
 // repr(float(x)) at dst (room for kMgfNumMax bytes) -> its length
 __host__ __device__ __forceinline__ int mgf_write_num(uint8_t* dst, float x) {
-    const uint32_t bits = mgf_float_bits(x);
+    const uint32_t bits = num_float_bits(x);
     int at = 0;
     if ((bits & 0x7F800000u) == 0x7F800000u && (bits & 0x7FFFFFu)) {
         dst[0] = 'n';
@@ -337,25 +61,18 @@ __host__ __device__ __forceinline__ int mgf_write_num(uint8_t* dst, float x) {
         dst[at + 2] = '0';
         return at + 3;
     }
-    const MgfDecimal d = mgf_shortest(bits);
-    return at + mgf_write_decimal(dst + at, d, mgf_positional(d.decpt));
+    const NumDecimal d = num_shortest_widened(bits);
+    return at + num_write_decimal(dst + at, d, mgf_positional(d.decpt));
 }
-
-__host__ __device__ __forceinline__ int mgf_put(uint8_t* dst, const char* word, int n) {
-    for (int i = 0; i < n; ++i) dst[i] = (uint8_t)word[i];
-    return n;
-}
-
-__host__ __device__ __forceinline__ uint64_t mgf_abs64(int64_t v) { return v < 0 ? ~(uint64_t)v + 1 : (uint64_t)v; }
 
 // the four fields behind the title's bytes; `which` 0: "\nPEPMASS=<pm>\n" (it closes the title line), 1: "CHARGE=<|z|><+ or ->\n"
 // when charge != 0, 2: "RTINSECONDS=<rt>\n", 3: "CLUSTER=<id>\n"
 __host__ __device__ __forceinline__ int mgf_field_len(int which, float pm, int32_t charge, float rt, int64_t cluster) {
     switch (which) {
         case 0: return 9 + mgf_num_len(pm) + 1;
-        case 1: return charge == 0 ? 0 : 7 + mgf_uint_len(mgf_abs64(charge)) + 2;
+        case 1: return charge == 0 ? 0 : 7 + num_int_len((int64_t)num_abs64(charge)) + 2;
         case 2: return 12 + mgf_num_len(rt) + 1;
-        default: return 8 + (cluster < 0) + mgf_uint_len(mgf_abs64(cluster)) + 1;
+        default: return 8 + num_int_len(cluster) + 1;
     }
 }
 
@@ -363,26 +80,19 @@ __host__ __device__ __forceinline__ int mgf_field_len(int which, float pm, int32
 __host__ __device__ __forceinline__ int mgf_write_field(uint8_t* dst, int which, float pm, int32_t charge, float rt, int64_t cluster) {
     int at;
     if (which == 0) {
-        at = mgf_put(dst, "\nPEPMASS=", 9);
+        at = num_put(dst, "\nPEPMASS=", 9);
         at += mgf_write_num(dst + at, pm);
     } else if (which == 1) {
         if (charge == 0) return 0;
-        at = mgf_put(dst, "CHARGE=", 7);
-        const uint64_t a = mgf_abs64(charge);
-        const int n = mgf_uint_len(a);
-        mgf_write_uint(dst + at, a, n);
-        at += n;
+        at = num_put(dst, "CHARGE=", 7);
+        at += num_write_int(dst + at, (int64_t)num_abs64(charge));
         dst[at++] = charge < 0 ? '-' : '+';
     } else if (which == 2) {
-        at = mgf_put(dst, "RTINSECONDS=", 12);
+        at = num_put(dst, "RTINSECONDS=", 12);
         at += mgf_write_num(dst + at, rt);
     } else {
-        at = mgf_put(dst, "CLUSTER=", 8);
-        if (cluster < 0) dst[at++] = '-';
-        const uint64_t a = mgf_abs64(cluster);
-        const int n = mgf_uint_len(a);
-        mgf_write_uint(dst + at, a, n);
-        at += n;
+        at = num_put(dst, "CLUSTER=", 8);
+        at += num_write_int(dst + at, cluster);
     }
     dst[at++] = '\n';
     return at;
@@ -399,8 +109,8 @@ __host__ __device__ __forceinline__ int mgf_write_peak(uint8_t* dst, float mz, f
     return at;
 }
 
-__host__ __device__ __forceinline__ int mgf_write_head(uint8_t* dst) { return mgf_put(dst, "BEGIN IONS\nTITLE=", kMgfHeadLen); }
-__host__ __device__ __forceinline__ int mgf_write_tail(uint8_t* dst) { return mgf_put(dst, "END IONS\n\n", kMgfTailLen); }
+__host__ __device__ __forceinline__ int mgf_write_head(uint8_t* dst) { return num_put(dst, "BEGIN IONS\nTITLE=", kMgfHeadLen); }
+__host__ __device__ __forceinline__ int mgf_write_tail(uint8_t* dst) { return num_put(dst, "END IONS\n\n", kMgfTailLen); }
 
 // one entry, serially: what the kernels compute a lane per field and per peak
 __host__ __device__ inline int64_t mgf_entry_len(int64_t title_len, float pm, int32_t charge, float rt, int64_t cluster, const float* mz,

@@ -5,19 +5,15 @@
 // fal_mgf_write_sizes (one synchronisation, at its end): one wave per entry adds up its text -- the lanes take the peak lines 64
 // at a time, lanes 0-3 the four fields behind the title -- then the library's scan (device_scan_i64) turns the sizes into offsets.
 //
-// fal_mgf_write (one synchronisation, at its end): one wave per entry.  The wave owns a kWriteTile-byte LDS tile that stands for
-// the 16-byte aligned stretch of the output around its write position.  A round appends up to 64 pieces (a peak line per lane;
-// the head; a stretch of the title; the four fields; the tail) at offsets from a wave prefix sum of their lengths -- the digits
-// are computed again rather than kept from the sizing pass -- and then flushes every complete 16-byte unit with one 16-byte store
-// per lane; what is left (under 16 bytes) moves to the front of the tile.  Only the bytes in front of the entry's first aligned
-// unit and behind its last one -- at most 15 each, units it shares with its neighbours -- go out as single bytes.  Every store is
+// fal_mgf_write (one synchronisation, at its end): one wave per entry.  The wave owns a kWriteTile-byte LDS tile (textwrite.h's
+// Tile).  A round appends up to 64 pieces (a peak line per lane; the head; a stretch of the title; the four fields; the tail) at
+// offsets from a wave prefix sum of their lengths -- the digits are computed again rather than kept from the sizing pass -- and
+// then flushes the tile's complete 16-byte units; what is left (under 16 bytes) moves to the front of the tile.  Every store is
 // bounded by the entry's own range [offset[k], offset[k + 1]) - offset[first], checked against out_bytes before anything is written.
 #include <algorithm>
 #include "common.h"
-#include "ivf.h"
 #include "mgfwrite.h"
-#include "textscan.h"
-#include "util.h"
+#include "textwrite.h"
 
 namespace fal {
 namespace {
@@ -26,7 +22,6 @@ constexpr int kWriteTile = 3136;                 // >= 31 bytes carried over + 6
 constexpr int kTitleChunk = 2048;                // title bytes appended per round
 static_assert(31 + 64 * kMgfPeakMax <= kWriteTile && 31 + kTitleChunk <= kWriteTile && 31 + kMgfHeadLen <= kWriteTile &&
                   kWriteTile % 16 == 0, "the tile takes one round's text behind what the last flush left");
-enum { WR_BAD_INPUT = 1, WR_TOO_SMALL = 2, WR_OVERFLOW = 4 };      // meta[META_FLAGS] bits
 
 struct MgfEntries {
     const float* mz;
@@ -87,63 +82,26 @@ __global__ __launch_bounds__(256) void mgf_write_sizes_kernel(MgfEntries e, int6
         len = wave_sum_i64(len);
         if (lane == 0) {
             sizes[k] = kMgfHeadLen + (t1 - t0) + len + kMgfTailLen;
-            if (bad) atomicOr(&meta[META_FLAGS], (unsigned long long)WR_BAD_INPUT);
+            if (bad) atomicOr(&meta[META_FLAGS], (unsigned long long)TW_BAD_INPUT);
         }
     }
 }
 
 // ---- write: one wave per entry ----------------------------------------------------------------------------------------------------
-// the wave's tile: tile[i] is the byte at gbase + i (gbase 16-byte aligned); [lo, hi) is text not stored yet; `end`: the entry's end
-struct Tile {
-    uint8_t* tile;
-    uint8_t* gbase;
-    uint8_t* end;
-    int lo, hi;
-    bool overflow;
-};
-
-__device__ __forceinline__ void tile_flush(Tile& t, bool final, int lane) {
-    wave_lds_sync();
-    const int64_t room = t.end - t.gbase;                                        // bytes of the tile inside the entry's range
-    if (t.hi > room) {                                                           // (more text than the sizes said: never stored)
-        t.hi = (int)std::max<int64_t>(room, t.lo);
-        t.overflow = true;
-    }
-    const int u0 = (t.lo + 15) >> 4, u1 = t.hi >> 4;                             // the complete 16-byte units [u0, u1)
-    if (!final && u1 <= u0) return;
-    const int head_end = std::min(u0 << 4, t.hi);
-    if (t.lo + lane < head_end) t.gbase[t.lo + lane] = t.tile[t.lo + lane];      // in front of the first aligned unit: < 16 bytes
-    for (int u = u0 + lane; u < u1; u += 64) *reinterpret_cast<uint4*>(t.gbase + 16 * u) = *reinterpret_cast<const uint4*>(t.tile + 16 * u);
-    const int rest = std::max(u1 << 4, head_end);                                // behind the last complete unit: < 16 bytes
-    if (final) {
-        if (rest + lane < t.hi) t.gbase[rest + lane] = t.tile[rest + lane];
-        t.lo = t.hi;
-        return;
-    }
-    const int rem = t.hi - rest;
-    const uint8_t v = lane < rem ? t.tile[rest + lane] : (uint8_t)0;
-    wave_lds_sync();
-    if (lane < rem) t.tile[lane] = v;
-    t.gbase += rest;
-    t.lo = 0;
-    t.hi = rem;
-    wave_lds_sync();
-}
-
 __global__ __launch_bounds__(256) void mgf_write_kernel(MgfEntries e, const int64_t* __restrict__ offsets, int64_t first, int64_t last,
                                                         uint8_t* __restrict__ out, int64_t out_bytes, unsigned long long* __restrict__ meta) {
     __shared__ __attribute__((aligned(16))) uint8_t tiles[4][kWriteTile];
     const int lane = threadIdx.x & 63;
     const int64_t base = offsets[first], need = offsets[last] - base;
     if (need < 0 || need > out_bytes) {                                          // uniform over the grid: nothing is written
-        if (blockIdx.x == 0 && threadIdx.x == 0) atomicOr(&meta[META_FLAGS], (unsigned long long)WR_TOO_SMALL);
+        if (blockIdx.x == 0 && threadIdx.x == 0) atomicOr(&meta[META_FLAGS], (unsigned long long)TW_TOO_SMALL);
         return;
     }
     const int64_t waves = (int64_t)gridDim.x * (blockDim.x >> 6);
     for (int64_t k = first + blockIdx.x * (int64_t)(blockDim.x >> 6) + (threadIdx.x >> 6); k < last; k += waves) {
         const int64_t g0 = offsets[k] - base, g1 = offsets[k + 1] - base;
         if (g0 < 0 || g1 < g0 || g1 > need) {                                    // offsets that are no scan of sizes
-            if (lane == 0) atomicOr(&meta[META_FLAGS], (unsigned long long)WR_BAD_INPUT);
+            if (lane == 0) atomicOr(&meta[META_FLAGS], (unsigned long long)TW_BAD_INPUT);
             continue;
         }
         int64_t p0, p1, t0, t1;
@@ -191,7 +149,7 @@ __global__ __launch_bounds__(256) void mgf_write_kernel(MgfEntries e, const int6
         t.hi += kMgfTailLen;
         tile_flush(t, true, lane);
         const bool shortfall = t.gbase + t.hi != t.end;                          // (less text than the sizes said)
-        if (lane == 0 && (t.overflow || shortfall)) atomicOr(&meta[META_FLAGS], (unsigned long long)WR_OVERFLOW);
+        if (lane == 0 && (t.overflow || shortfall)) atomicOr(&meta[META_FLAGS], (unsigned long long)TW_OVERFLOW);
         wave_lds_sync();
     }
 }
@@ -204,16 +162,6 @@ int check_entries(const char* who, fal_ctx* ctx, const float* mz, const float* i
     FAL_REQUIRE(ctx && n >= 0 && n_rows >= 0 && nnz >= 0 && title_bytes >= 0, FAL_EINVAL, "%s: bad argument", who);
     FAL_REQUIRE(n == 0 || (indptr && rows && pm && rt && charge && cluster && title_ptr), FAL_EINVAL, "%s: NULL column", who);
     FAL_REQUIRE(nnz == 0 || (mz && intensity), FAL_EINVAL, "%s: NULL peaks", who);
-    return FAL_OK;
-}
-
-int read_flags(fal_ctx* ctx, const unsigned long long* meta, const int64_t* extra, unsigned long long** host) {
-    unsigned long long* h = nullptr;
-    FAL_TRY(ctx->pinned_reserve(sizeof(unsigned long long) * (META_WORDS + 1), (void**)&h));
-    FAL_CHECK_HIP(hipMemcpyAsync(h, meta, sizeof(unsigned long long) * META_WORDS, hipMemcpyDeviceToHost, ctx->stream));
-    if (extra) FAL_CHECK_HIP(hipMemcpyAsync(h + META_WORDS, extra, sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream));
-    FAL_CHECK_HIP(hipStreamSynchronize(ctx->stream));
-    *host = h;
     return FAL_OK;
 }
 
@@ -236,18 +184,11 @@ extern "C" int fal_mgf_write_sizes(fal_ctx* ctx, const float* mz, const float* i
         return FAL_OK;
     }
     unsigned long long* meta = nullptr;
-    FAL_TRY(ctx->reserve(SLOT_MGFW, 64, (void**)&meta));
-    FAL_CHECK_HIP(hipMemsetAsync(meta, 0, 64, ctx->stream));
+    FAL_TRY(writer_meta(ctx, SLOT_MGFW, &meta));
     const MgfEntries e{mz, intensity, indptr, n_rows, nnz, rows, precursor_mz, retention_time, charge, cluster, nullptr, title_ptr, title_bytes};
     hipLaunchKernelGGL(mgf_write_sizes_kernel, dim3(capped_grid(ctx, n, 4)), dim3(256), 0, ctx->stream, e, n, sizes_out, meta);
-    FAL_CHECK_HIP(hipGetLastError());
-    FAL_TRY(device_scan_i64(ctx, sizes_out, n, offsets_out, SLOT_SORT));
-    unsigned long long* h = nullptr;
-    FAL_TRY(read_flags(ctx, meta, offsets_out + n, &h));
-    FAL_REQUIRE(!(h[META_FLAGS] & WR_BAD_INPUT), FAL_EINVAL,
-                "fal_mgf_write_sizes: a row outside the CSR, or indptr / title_ptr not ascending inside their arrays");
-    *total_out = (int64_t)h[META_WORDS];
-    return FAL_OK;
+    return finish_sizes(ctx, meta, sizes_out, n, offsets_out, total_out,
+                        "fal_mgf_write_sizes: a row outside the CSR, or indptr / title_ptr not ascending inside their arrays");
 }
 
 extern "C" int fal_mgf_write(fal_ctx* ctx, const float* mz, const float* intensity, const int64_t* indptr, int64_t n_rows, int64_t nnz,
@@ -261,19 +202,9 @@ extern "C" int fal_mgf_write(fal_ctx* ctx, const float* mz, const float* intensi
                     (title || title_bytes == 0),
                 FAL_EINVAL, "fal_mgf_write: bad argument");
     unsigned long long* meta = nullptr;
-    FAL_TRY(ctx->reserve(SLOT_MGFW, 64, (void**)&meta));
-    FAL_CHECK_HIP(hipMemsetAsync(meta, 0, 64, ctx->stream));
+    FAL_TRY(writer_meta(ctx, SLOT_MGFW, &meta));
     const MgfEntries e{mz, intensity, indptr, n_rows, nnz, rows, precursor_mz, retention_time, charge, cluster, title, title_ptr, title_bytes};
     hipLaunchKernelGGL(mgf_write_kernel, dim3(capped_grid(ctx, std::max<int64_t>(last - first, 1), 4)), dim3(256), 0, ctx->stream, e, offsets,
                        first, last, out, out_bytes, meta);
-    FAL_CHECK_HIP(hipGetLastError());
-    if (host_out && out_bytes > 0) FAL_CHECK_HIP(hipMemcpyAsync(host_out, out, (size_t)out_bytes, hipMemcpyDeviceToHost, ctx->stream));
-    unsigned long long* h = nullptr;
-    FAL_TRY(read_flags(ctx, meta, nullptr, &h));
-    FAL_REQUIRE(!(h[META_FLAGS] & WR_TOO_SMALL), FAL_EINVAL, "fal_mgf_write: %lld bytes are too few for entries [%lld, %lld)",
-                (long long)out_bytes, (long long)first, (long long)last);
-    FAL_REQUIRE(!(h[META_FLAGS] & WR_BAD_INPUT), FAL_EINVAL,
-                "fal_mgf_write: offsets that are no scan of the entries' sizes, or columns that are not those of fal_mgf_write_sizes");
-    FAL_REQUIRE(!(h[META_FLAGS] & WR_OVERFLOW), FAL_EINTERNAL, "fal_mgf_write: an entry's text is not the size fal_mgf_write_sizes gave");
-    return FAL_OK;
+    return finish_write(ctx, meta, "fal_mgf_write", "entries", "an entry", first, last, out, out_bytes, host_out);
 }

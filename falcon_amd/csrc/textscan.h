@@ -1,10 +1,12 @@
 // What the text readers on the device (mgfparse.hip, mzmlscan.hip) share.  Device side: 16-byte loads that stop at the end of
 // the text, a block-wide prefix sum, the copy of a byte range into an LDS tile, and the two passes that build a text's mark
 // table (the positions of one byte value: the line starts of MGF, the '<' of mzML).  Host side (at the bottom): the index
-// handle fal_ctx::TextIndex that carries the tables from fal_*_index to fal_*_parse.
+// handle fal_ctx::TextIndex that carries the tables from fal_*_index to fal_*_parse.  The meta words and their read-back are
+// util.h's, shared with the text writers (textwrite.h).
 #pragma once
 #include <algorithm>
 #include "common.h"
+#include "util.h"
 
 namespace fal {
 
@@ -49,10 +51,9 @@ __device__ __forceinline__ void stage_bytes(const uint8_t* __restrict__ text, in
 
 // ---- the mark table ----------------------------------------------------------------------------------------------------------------
 // Two walks over the text, 16 bytes per lane and kTileBytes per block of 256, with a device scan of the tile counts between
-// them (tile_base[0 .. n_tiles], the last entry the total).  Of the meta words both passes need two: meta[META_COUNT] = the
-// table's entries, whatever its capacity, and meta[META_FLAGS], where Flag is set when they exceed it.
+// them (tile_base[0 .. n_tiles], the last entry the total).  Of the meta words (util.h) both passes need two: meta[META_COUNT] =
+// the table's entries, whatever its capacity, and meta[META_FLAGS], where Flag is set when they exceed it.
 constexpr int kTileBytes = 4096;
-enum { META_COUNT = 0, META_FLAGS = 1, META_WORDS = 4 };
 
 // how many of the lane's 16 bytes v = load16(text, n, pos) are Mark
 template <char Mark>
@@ -118,16 +119,6 @@ inline int text_index_begin(const char* who, fal_ctx* ctx, fal_ctx::TextIndex fa
     return FAL_OK;
 }
 
-// the META_WORDS meta words on the host, through the pinned buffer; synchronises
-inline int read_meta(fal_ctx* ctx, const unsigned long long* meta, const unsigned long long** host) {
-    unsigned long long* h = nullptr;
-    FAL_TRY(ctx->pinned_reserve(sizeof(unsigned long long) * META_WORDS, (void**)&h));
-    FAL_CHECK_HIP(hipMemcpyAsync(h, meta, sizeof(unsigned long long) * META_WORDS, hipMemcpyDeviceToHost, ctx->stream));
-    FAL_CHECK_HIP(hipStreamSynchronize(ctx->stream));
-    *host = h;
-    return FAL_OK;
-}
-
 inline void store_index(fal_ctx::TextIndex& ix, const void* text, int64_t n_bytes, int64_t spectra, int64_t extra, int64_t cap_table,
                         int64_t cap_spectra, const void* b0, const void* b1, const void* b2, const void* b3) {
     ix = fal_ctx::TextIndex{text, n_bytes, spectra, extra, cap_table, cap_spectra, {b0, b1, b2, b3}};
@@ -141,11 +132,6 @@ inline bool matches(const fal_ctx* ctx, const fal_ctx::TextIndex& ix, int first_
         for (int i = 0; i < 4; ++i) mine = mine && ix.blocks[i] == ctx->scratch[first_slot + i].ptr;
     }
     return mine;
-}
-
-// blocks of a grid-stride kernel over `items`, `per_block` to a block: at least one, at most 16 a compute unit
-inline unsigned capped_grid(const fal_ctx* ctx, int64_t items, int per_block) {
-    return (unsigned)std::max<int64_t>(1, std::min<int64_t>(ceil_div(items, per_block), (int64_t)ctx->num_cus * 16));
 }
 
 }  // namespace fal

@@ -1,9 +1,30 @@
-// Small shared launch helpers (implemented in sortutil.hip).
+// Small shared launch helpers (implemented in sortutil.hip, the inline ones here).
 #pragma once
+#include <algorithm>
 #include "common.h"
 #include "peakmatch.h"
 
 namespace fal {
+// blocks of a grid-stride kernel over `items`, `per_block` to a block: at least one, at most 16 a compute unit
+inline unsigned capped_grid(const fal_ctx* ctx, int64_t items, int per_block) {
+    return (unsigned)std::max<int64_t>(1, std::min<int64_t>(ceil_div(items, per_block), (int64_t)ctx->num_cus * 16));
+}
+
+// The meta block of the text readers and writers: META_WORDS device words a call clears, its kernels set and its one
+// synchronisation reads back.  meta[META_FLAGS]: the call's flag bits; meta[META_COUNT]: the mark table's entries (textscan.h).
+enum { META_COUNT = 0, META_FLAGS = 1, META_WORDS = 4 };
+
+// the meta words on the host, through the pinned buffer; `extra`: one more device word, read into host[META_WORDS].  Synchronises
+inline int read_meta(fal_ctx* ctx, const unsigned long long* meta, const unsigned long long** host, const int64_t* extra = nullptr) {
+    unsigned long long* h = nullptr;
+    FAL_TRY(ctx->pinned_reserve(sizeof(unsigned long long) * (META_WORDS + 1), (void**)&h));
+    FAL_CHECK_HIP(hipMemcpyAsync(h, meta, sizeof(unsigned long long) * META_WORDS, hipMemcpyDeviceToHost, ctx->stream));
+    if (extra) FAL_CHECK_HIP(hipMemcpyAsync(h + META_WORDS, extra, sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream));
+    FAL_CHECK_HIP(hipStreamSynchronize(ctx->stream));
+    *host = h;
+    return FAL_OK;
+}
+
 // out[0..n) = exclusive prefix of in (int32 flags/counts), out[n] = total (all on device).  Sums are int64 throughout.
 // Three forms (sortutil.hip device_scan_t), by nb = ceil(n / 1024) blocks:
 //   nb <= 1,025 (n <= 1,049,600)   block sums + fused apply: every block adds up the sums in front of it in ONE round of

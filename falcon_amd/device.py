@@ -20,6 +20,17 @@ def _torch():
     return torch
 
 
+def chunk_cuts(offsets, max_bytes) -> list:
+    """The cuts [0, ..., n] of the text writers' chunks over n units with the ascending byte offsets `offsets` (n + 1): a chunk
+    takes the units that stay within `max_bytes` (at least 1) of its first, and at least one: a larger unit grows its own."""
+    n = len(offsets) - 1
+    cuts = [0]
+    while cuts[-1] < n:
+        last = int(np.searchsorted(offsets, offsets[cuts[-1]] + max(int(max_bytes), 1), side="right")) - 1
+        cuts.append(min(max(last, cuts[-1] + 1), n))
+    return cuts
+
+
 class Context:
     """Owns a `fal_ctx` bound to `cuda:<device>` and torch's current stream on it."""
 
@@ -382,6 +393,38 @@ class Context:
         return dict(flags=0, lines=lines, indptr=indptr, mz=mz, intensity=it, precursor_mz=pmz, charge=charge,
                     has_charge=has_charge.astype(bool), retention_time=rt, title=title, span=span, status=status)
 
+    def _write_sizes(self, entry: str, args, n: int):
+        """a text writer's sizing call `entry` over the packed columns `args`, n units -> (sizes i64[n], offsets i64[n + 1] on the
+        device, total bytes)"""
+        torch = _torch()
+        sizes, offsets = self.empty((max(n, 1),), torch.int64), self.empty((n + 1,), torch.int64)
+        total = C.c_int64(0)
+        check(getattr(self.lib, entry)(self._h, *args, self._p(sizes), self._p(offsets), C.byref(total)), entry)
+        return sizes[:n], offsets, int(total.value)
+
+    def _write_range(self, entry: str, args, offsets, first: int, last: int, out, host_out):
+        """a text writer's write call `entry` over the packed columns `args`: units [first, last) into `out`, copied to `host_out`"""
+        if host_out is not None and (not host_out.is_pinned() or host_out.numel() != out.numel()):
+            raise ValueError(f"{entry[4:]}: host_out must be pinned and of out's size")
+        check(getattr(self.lib, entry)(self._h, *args, self._p(offsets), int(first), int(last), self._p(out) if out.numel() else None,
+                                       out.numel(), self._p(host_out) if host_out is not None and out.numel() else None), entry)
+
+    def _write_chunks(self, n: int, offsets, max_bytes, copy: bool, write):
+        """units [0, n) cut at `chunk_cuts`, every chunk through `write(first, last, d_view, h_view)` -> its host array"""
+        torch = _torch()
+        if max_bytes is None:
+            from .ms_io.mgf_io import DEFAULT_CHUNK_BYTES as max_bytes
+        off = offsets.cpu().numpy()
+        cuts = chunk_cuts(off[:n + 1], max_bytes)
+        cap = int(max(off[b] - off[a] for a, b in zip(cuts[:-1], cuts[1:])))
+        d_out = self.empty((max(cap, 1),), torch.uint8)
+        h_out = torch.empty((max(cap, 1),), dtype=torch.uint8, pin_memory=True)
+        for a, b in zip(cuts[:-1], cuts[1:]):
+            need = int(off[b] - off[a])
+            write(a, b, d_out[:need], h_out[:need])
+            chunk = h_out[:need].numpy()
+            yield chunk.copy() if copy else chunk
+
     def _mgf_entries(self, mz, intensity, indptr, rows, precursor_mz, retention_time, charge, cluster, title, title_ptr):
         """the writer's columns as device tensors of the entry points' types, checked against each other"""
         torch = _torch()
@@ -407,23 +450,13 @@ class Context:
     def mgf_write_sizes(self, cols):
         """`fal_mgf_write_sizes` of `_mgf_entries` columns -> (sizes i64[n], offsets i64[n + 1] on the device, total bytes).
         Synchronises once."""
-        torch = _torch()
-        n = int(cols["rows"].shape[0])
-        sizes, offsets = self.empty((max(n, 1),), torch.int64), self.empty((n + 1,), torch.int64)
-        total = C.c_int64(0)
-        check(self.lib.fal_mgf_write_sizes(self._h, *self._mgf_entry_args(cols, False), self._p(sizes), self._p(offsets),
-                                           C.byref(total)), "fal_mgf_write_sizes")
-        return sizes[:n], offsets, int(total.value)
+        return self._write_sizes("fal_mgf_write_sizes", self._mgf_entry_args(cols, False), int(cols["rows"].shape[0]))
 
     def mgf_write(self, cols, offsets, first: int, last: int, out, host_out=None):
         """`fal_mgf_write`: the text of entries [first, last) into the uint8 device tensor (or view) `out`; `host_out`: a pinned
         uint8 host tensor of the same size that receives a copy.  Synchronises once.  FalconHipError (code `_lib.FAL_EINVAL`,
         nothing written) when `out` is too small."""
-        if host_out is not None and (not host_out.is_pinned() or host_out.numel() != out.numel()):
-            raise ValueError("mgf_write: host_out must be pinned and of out's size")
-        check(self.lib.fal_mgf_write(self._h, *self._mgf_entry_args(cols, True), self._p(offsets), int(first), int(last),
-                                     self._p(out) if out.numel() else None, out.numel(),
-                                     self._p(host_out) if host_out is not None and out.numel() else None), "fal_mgf_write")
+        self._write_range("fal_mgf_write", self._mgf_entry_args(cols, True), offsets, first, last, out, host_out)
 
     def format_mgf(self, mz, intensity, indptr, rows, precursor_mz, retention_time, charge, cluster, title, title_ptr,
                    max_bytes: Optional[int] = None, copy: bool = True):
@@ -435,27 +468,12 @@ class Context:
         `mgf_io.DEFAULT_CHUNK_BYTES`); one larger entry grows its chunk.  Every chunk is formatted into one device buffer and
         copied through one pinned host buffer, with one stream synchronisation; `copy=False` yields views of that pinned
         buffer, valid until the next chunk is asked for."""
-        torch = _torch()
-        if max_bytes is None:
-            from .ms_io.mgf_io import DEFAULT_CHUNK_BYTES as max_bytes
         cols = self._mgf_entries(mz, intensity, indptr, rows, precursor_mz, retention_time, charge, cluster, title, title_ptr)
         n = int(cols["rows"].shape[0])
         if n == 0:
             return
-        _, offsets, total = self.mgf_write_sizes(cols)
-        off = offsets.cpu().numpy()
-        cuts = [0]                                   # (a loop over the chunks, not over the entries)
-        while cuts[-1] < n:
-            last = int(np.searchsorted(off, off[cuts[-1]] + max(int(max_bytes), 1), side="right")) - 1
-            cuts.append(min(max(last, cuts[-1] + 1), n))
-        cap = int(max(off[b] - off[a] for a, b in zip(cuts[:-1], cuts[1:])))
-        d_out = self.empty((max(cap, 1),), torch.uint8)
-        h_out = torch.empty((max(cap, 1),), dtype=torch.uint8, pin_memory=True)
-        for a, b in zip(cuts[:-1], cuts[1:]):
-            need = int(off[b] - off[a])
-            self.mgf_write(cols, offsets, a, b, d_out[:need], h_out[:need])
-            chunk = h_out[:need].numpy()
-            yield chunk.copy() if copy else chunk
+        sizes, offsets, _ = self.mgf_write_sizes(cols)            # (sizes: alive until the last chunk, as the buffers are)
+        yield from self._write_chunks(n, offsets, max_bytes, copy, lambda a, b, d, h: self.mgf_write(cols, offsets, a, b, d, h))
 
     def csv_order(self, file_rank, ident, id_ptr):
         """`fal_csv_order`: the rows of the cluster CSV sorted by (file_rank, natural order of the ASCII id, row) -> (order i32[n]
@@ -502,23 +520,13 @@ class Context:
     def csv_write_sizes(self, cols):
         """`fal_csv_write_sizes` of `_csv_columns` columns -> (sizes i64[rows], offsets i64[rows + 1] on the device, total bytes).
         Synchronises once."""
-        torch = _torch()
-        rows = cols["rows"]
-        sizes, offsets = self.empty((max(rows, 1),), torch.int64), self.empty((rows + 1,), torch.int64)
-        total = C.c_int64(0)
-        check(self.lib.fal_csv_write_sizes(self._h, *self._csv_column_args(cols), self._p(sizes), self._p(offsets), C.byref(total)),
-              "fal_csv_write_sizes")
-        return sizes[:rows], offsets, int(total.value)
+        return self._write_sizes("fal_csv_write_sizes", self._csv_column_args(cols), cols["rows"])
 
     def csv_write(self, cols, offsets, first: int, last: int, out, host_out=None):
         """`fal_csv_write`: the text of rows [first, last) into the uint8 device tensor (or view) `out`; `host_out`: a pinned uint8
         host tensor of the same size that receives a copy.  Synchronises once.  FalconHipError (code `_lib.FAL_EINVAL`, nothing
         written) when `out` is too small."""
-        if host_out is not None and (not host_out.is_pinned() or host_out.numel() != out.numel()):
-            raise ValueError("csv_write: host_out must be pinned and of out's size")
-        check(self.lib.fal_csv_write(self._h, *self._csv_column_args(cols), self._p(offsets), int(first), int(last),
-                                     self._p(out) if out.numel() else None, out.numel(),
-                                     self._p(host_out) if host_out is not None and out.numel() else None), "fal_csv_write")
+        self._write_range("fal_csv_write", self._csv_column_args(cols), offsets, first, last, out, host_out)
 
     def format_csv(self, file_id, file_names, file_name_ptr, ident, id_ptr, charge, precursor_mz, retention_time, cluster, order=None,
                    max_bytes: Optional[int] = None, copy: bool = True, quote_cr: Optional[bool] = None):
@@ -530,28 +538,12 @@ class Context:
         `max_bytes` (default `mgf_io.DEFAULT_CHUNK_BYTES`); one larger row grows its chunk.  Every chunk is formatted into one
         device buffer and copied through one pinned host buffer, with one stream synchronisation; `copy=False` yields views of
         that pinned buffer, valid until the next chunk is asked for."""
-        torch = _torch()
-        if max_bytes is None:
-            from .ms_io.mgf_io import DEFAULT_CHUNK_BYTES as max_bytes
         cols = self._csv_columns(file_id, file_names, file_name_ptr, ident, id_ptr, charge, precursor_mz, retention_time, cluster, order,
                                  quote_cr)
-        n = cols["rows"]
-        if n == 0:
+        if cols["rows"] == 0:
             return
-        _, offsets, total = self.csv_write_sizes(cols)
-        off = offsets.cpu().numpy()
-        cuts = [0]                                   # (a loop over the chunks, not over the rows)
-        while cuts[-1] < n:
-            last = int(np.searchsorted(off, off[cuts[-1]] + max(int(max_bytes), 1), side="right")) - 1
-            cuts.append(min(max(last, cuts[-1] + 1), n))
-        cap = int(max(off[b] - off[a] for a, b in zip(cuts[:-1], cuts[1:])))
-        d_out = self.empty((max(cap, 1),), torch.uint8)
-        h_out = torch.empty((max(cap, 1),), dtype=torch.uint8, pin_memory=True)
-        for a, b in zip(cuts[:-1], cuts[1:]):
-            need = int(off[b] - off[a])
-            self.csv_write(cols, offsets, a, b, d_out[:need], h_out[:need])
-            chunk = h_out[:need].numpy()
-            yield chunk.copy() if copy else chunk
+        sizes, offsets, _ = self.csv_write_sizes(cols)            # (sizes: alive until the last chunk, as the buffers are)
+        yield from self._write_chunks(cols["rows"], offsets, max_bytes, copy, lambda a, b, d, h: self.csv_write(cols, offsets, a, b, d, h))
 
     def mzml_index(self, d_text):
         """`fal_mzml_index` of mzML text on the device (uint8 tensor) -> (spectra, tags inside spectra, `_lib.MZML_FLAG_*` bits,

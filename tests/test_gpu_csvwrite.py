@@ -140,6 +140,15 @@ def check_bounds(ctx, tmp_dir):
             with pytest.raises(FalconHipError, match=f"code {FAL_EINVAL}:"):
                 ctx.csv_write(cols, offsets, first, last, buf[front:front + len(want) - 1])
             assert (buf.cpu().numpy() == SENTINEL).all()
+    # every alignment of `out`: rows [5, 5 + 70) are two tiles of 64 rows, with rows longer than a tile among them
+    want = b"".join(texts[5:75])
+    assert max(len(t) for t in texts[5:75]) == max(len(t) for t in texts) > 8192
+    for front in range(16):
+        buf = torch.full((front + len(want) + 37,), SENTINEL, dtype=torch.uint8, device=ctx.tdev)
+        ctx.csv_write(cols, offsets, 5, 75, buf[front:front + len(want)])
+        got = buf.cpu().numpy()
+        assert got[front:front + len(want)].tobytes() == want, front
+        assert (got[:front] == SENTINEL).all() and (got[front + len(want):] == SENTINEL).all(), front
     # offsets that are not the columns': FAL_EINVAL, and every store stays inside the buffer
     wrong = offsets.clone()
     wrong[3:] += 1

@@ -100,6 +100,13 @@ def check_bounds(ctx):
             with pytest.raises(FalconHipError, match=f"code {FAL_EINVAL}:"):
                 ctx.mgf_write(cols, offsets, first, last, buf[front:front + len(want) - 1])
             assert (buf.cpu().numpy() == SENTINEL).all()
+    want = b"".join(texts[5:23])                                   # every alignment of `out`
+    for front in range(16):
+        buf = torch.full((front + len(want) + 37,), SENTINEL, dtype=torch.uint8, device=ctx.tdev)
+        ctx.mgf_write(cols, offsets, 5, 23, buf[front:front + len(want)])
+        got = buf.cpu().numpy()
+        assert got[front:front + len(want)].tobytes() == want, front
+        assert (got[:front] == SENTINEL).all() and (got[front + len(want):] == SENTINEL).all(), front
 
 
 def check_round_trip(ctx):

@@ -1,8 +1,8 @@
-"""Prints the power-of-five tables of `falcon_amd/csrc/mgfwrite.h` (the block between its GENERATED markers), from exact integer
+"""Prints the power-of-five tables of `falcon_amd/csrc/numtext.h` (the block between its GENERATED markers), from exact integer
 arithmetic.  The shortest-digits conversion of a float32 widened to double needs, with e2 the binary exponent of the double's
 integer significand less 2 (-203 .. 73):
-  kMgfPow5Inv[q], q = 0 .. 21 : floor(2^(bitlength(5^q) - 1 + 125) / 5^q) + 1     (e2 >= 0: the value is divided by 10^q)
-  kMgfPow5[i],    i = 0 .. 63 : the top 125 bits of 5^i (shifted left below that)  (e2 <  0: the value is multiplied by 5^i)
+  kNumPow5Inv[q], q = 0 .. 21 : floor(2^(bitlength(5^q) - 1 + 125) / 5^q) + 1     (e2 >= 0: the value is divided by 10^q)
+  kNumPow5[i],    i = 0 .. 63 : the top 125 bits of 5^i (shifted left below that)  (e2 <  0: the value is multiplied by 5^i)
 each as {low 64 bits, high 64 bits}.  tests/test_mgfwrite_cpu.py checks the header's entries against the same expressions.
 
     python tools/gen_mgfwrite_pow5.py
@@ -32,7 +32,7 @@ def _rows(name, values):
 
 
 def main() -> None:
-    lines = _rows("kMgfPow5Inv", [pow5_inv(q) for q in range(N_INV)]) + _rows("kMgfPow5", [pow5(i) for i in range(N_POW)])
+    lines = _rows("kNumPow5Inv", [pow5_inv(q) for q in range(N_INV)]) + _rows("kNumPow5", [pow5(i) for i in range(N_POW)])
     print("\n".join(lines))
 
 
