@@ -143,6 +143,10 @@ _SIGNATURES = {
     "fal_assign_nearest": ([c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p,
                             c_void_p, c_void_p, c_int64, c_double, c_int, c_double, c_double, c_int, c_void_p, c_void_p,
                             c_void_p], c_int),
+    "fal_member_scores": ([c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int64,
+                           c_void_p, c_double, c_void_p, c_void_p], c_int),
+    "fal_cluster_summary": ([c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                             c_void_p, c_void_p, c_void_p, c_void_p, c_void_p], c_int),
 }
 
 

@@ -847,6 +847,62 @@ def consensus_spectra(dataset, labels, medoids, fragment_tol: float, min_fractio
     return indptr.cpu().numpy(), mz.cpu().numpy(), intensity.cpu().numpy(), status.cpu().numpy()
 
 
+def _member_scores_dev(ctx, dataset, labels, medoids, fragment_tol, consensus):
+    """the device tensors of `member_scores` for a SpectrumDataset"""
+    if consensus is None:
+        rep_indptr, rep_mz, rep_intensity, rep_row = dataset.indptr, dataset.mz, dataset.intensity, medoids
+    else:
+        rep_indptr, rep_mz, rep_intensity = consensus
+        rep_row = np.arange(len(medoids), dtype=np.int32)
+        if len(rep_indptr) != len(medoids) + 1:
+            raise ValueError(f"consensus holds {len(rep_indptr) - 1} spectra for {len(medoids)} clusters")
+    return ctx.member_scores(dataset.mz, dataset.intensity, dataset.indptr, labels, rep_mz, rep_intensity, rep_indptr, rep_row,
+                             fragment_tol)
+
+
+def _as_dataset(dataset):
+    if isinstance(dataset, SpectrumDataset):
+        return dataset
+    return SpectrumDataset.from_table(
+        dataset.to_table(columns=["precursor_mz", "precursor_charge", "retention_time", "mz", "intensity"])
+        if hasattr(dataset, "to_table") else dataset)
+
+
+def member_scores(dataset, labels, medoids, fragment_tol: float, consensus=None, pipeline: Optional[ClusterPipeline] = None):
+    """Every spectrum of `dataset` scored against the representative of its cluster, for the clusters `generate_clusters`
+    returned (`fal_member_scores`; DESIGN.md "Member scores and cluster summary"): the matched-peak cosine of the snapshot's
+    `cosine_fast(member, representative, fragment_tol)`, clipped to [0, 1].  The representative is the medoid's spectrum, or
+    with `consensus` (the (indptr, mz, intensity) triple `consensus_spectra` returns) the cluster's consensus peaks.
+    `min_matched_peaks` is not applied: both numbers are reported.
+
+    Returns (similarity float32[n], matched int32[n]) by dataset row."""
+    global _default_pipeline
+    dataset = _as_dataset(dataset)
+    pipe = pipeline or _default_pipeline
+    if pipe is None:
+        pipe = _default_pipeline = ClusterPipeline()
+    sim, matched = _member_scores_dev(pipe.ctx, dataset, labels, medoids, fragment_tol, consensus)
+    return sim.cpu().numpy(), matched.cpu().numpy()
+
+
+def cluster_summary(dataset, labels, medoids, fragment_tol: float, consensus=None, pipeline: Optional[ClusterPipeline] = None):
+    """`member_scores` and, per cluster, what they say about it (`fal_cluster_summary`).
+
+    Returns a dict of host arrays: per cluster `size` int32, `sim_min` float32, `worst_row` int32 (the member with `sim_min`,
+    the lowest row among equals), `sim_mean` float64, `pmz_min`, `pmz_max`, `rt_min`, `rt_max` float32 (the retention times 0
+    for a dataset without them); per spectrum `similarity` float32 and `matched` int32."""
+    global _default_pipeline
+    dataset = _as_dataset(dataset)
+    pipe = pipeline or _default_pipeline
+    if pipe is None:
+        pipe = _default_pipeline = ClusterPipeline()
+    sim, matched = _member_scores_dev(pipe.ctx, dataset, labels, medoids, fragment_tol, consensus)
+    cols = pipe.ctx.cluster_summary(labels, len(medoids), sim, dataset.precursor_mz, dataset.retention_time)
+    out = {k: v.cpu().numpy() for k, v in cols.items()}
+    out["similarity"], out["matched"] = sim.cpu().numpy(), matched.cpu().numpy()
+    return out
+
+
 def write_representatives(filename: str, dataset: SpectrumDataset, medoids, cluster_ids, identifiers, charge: int = 0,
                           consensus=None, pipeline: Optional[ClusterPipeline] = None) -> str:
     """Write the representatives of `dataset`'s clusters to the MGF file `filename`, formatted on the device

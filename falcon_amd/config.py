@@ -41,6 +41,12 @@ class Config:
         p.add_argument("--consensus_min_fraction", type=float, default=0.25,
                        help="Consensus representatives: a merged peak is kept when at least this fraction of the cluster's "
                             "members' worth of peaks falls into it (0 < q <= 1, default: 0.25).")
+        p.add_argument("--cluster_summary", action="store_true",
+                       help="Also write <output>.clusters.csv (per cluster: size, representative, smallest and mean similarity "
+                            "of its members to the representative, the worst member, precursor m/z and retention-time spread) "
+                            "and <output>.scores.csv (per spectrum: its similarity to its cluster's representative and the "
+                            "matched peaks).  The representative is the medoid, or with --export_representatives "
+                            "--representatives consensus the consensus spectrum.")
         p.add_argument("--assign_to", nargs="+", default=None, metavar="FILE",
                        help="Representative MGF files of earlier runs (--export_representatives output, one CLUSTER= id per "
                             "entry): a new spectrum whose nearest representative inside the precursor (and RT) tolerance lies "
@@ -200,6 +206,11 @@ class Config:
             ns["assign_to"] = [ns["assign_to"]]
         if ns["assign_to"] and ns["distributed"]:
             self._parser.error("--assign_to does not combine with --distributed (the assignment to representatives is not sharded)")
+        if ns["cluster_summary"] and ns["assign_to"]:
+            self._parser.error("--cluster_summary does not combine with --assign_to (the cluster-mates of an assigned spectrum "
+                               "are not in the run)")
+        if ns["cluster_summary"] and ns["distributed"]:
+            self._parser.error("--cluster_summary does not combine with --distributed (the summary is not sharded)")
         if not 1 <= ns["low_dim"] <= 800:
             raise ValueError("low_dim must be an integer in [1, 800] (README.md:114-117; the widest rows the kernels hold)")
         if ns["n_neighbors_ann"] < ns["n_neighbors"]:

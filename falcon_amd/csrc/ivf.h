@@ -20,11 +20,12 @@ enum { SLOT_JOBS = 0, SLOT_SIMS = 1, SLOT_PROBES = 2, SLOT_PROBE_SIM = 3, SLOT_Q
        SLOT_MZML = 44, SLOT_MZML2 = 45, SLOT_MZML3 = 46, SLOT_MZML4 = 47, SLOT_MZML5 = 48,   // mzmlscan.hip (44-47 live from fal_mzml_index to fal_mzml_parse)
        SLOT_MGFW = 49,     // mgfwrite.hip
        SLOT_TILES = 50,    // tail.hip: the tile tables of fal_cluster_graph_tiled
-       SLOT_CSVW = 51 };   // csvwrite.hip
+       SLOT_CSVW = 51,     // csvwrite.hip
+       SLOT_MSCORE = 52, SLOT_MSCORE2 = 53 };   // memberscore.hip
 static_assert(SLOT_MGF2 == SLOT_MGF + 1 && SLOT_MGF3 == SLOT_MGF + 2 && SLOT_MGF4 == SLOT_MGF + 3 && SLOT_MZML2 == SLOT_MZML + 1 &&
                   SLOT_MZML3 == SLOT_MZML + 2 && SLOT_MZML4 == SLOT_MZML + 3,
               "fal::matches (textscan.h) addresses the four slots of an index as first + i");
-static_assert(SLOT_CSVW + 1 == kNumSlots, "a context holds one scratch block per named slot (common.h kNumSlots)");
+static_assert(SLOT_MSCORE2 + 1 == kNumSlots, "a context holds one scratch block per named slot (common.h kNumSlots)");
 // out[0..n] = exclusive prefix sums of in[0..n) (out has n + 1 entries)
 int launch_exclusive_scan(fal_ctx* ctx, const int64_t* in, int64_t n, int64_t* out);
 }

@@ -840,6 +840,54 @@ class Context:
                                           ptr(best_row), ptr(best_dist), ptr(n_cand)), "fal_assign_nearest")
         return best_row, best_dist, n_cand
 
+    # ------------------------------------------------------------------ member scores and cluster summary
+    def member_scores(self, mz, intensity, indptr, labels, rep_mz, rep_intensity, rep_indptr, rep_row, fragment_tol: float):
+        """`fal_member_scores`: every spectrum of a clustered partition scored against its cluster's representative (DESIGN.md
+        "Member scores and cluster summary").  mz / intensity f32, indptr i64[n+1]: the partition's peaks; labels i32[n] in
+        [0, n_clusters); the representatives are rows of the CSR rep_mz / rep_intensity / rep_indptr, cluster c's is row
+        rep_row[c] (i32[n_clusters]): the partition's own CSR with the medoids, or the consensus CSR with arange.  Host or
+        device arrays.  -> similarity f32[n], matched i32[n].  Device tensors; synchronises once."""
+        torch = _torch()
+        labels = self.to_dev(labels, torch.int32)
+        rep_row = self.to_dev(rep_row, torch.int32)
+        n, nc = int(labels.numel()), int(rep_row.numel())
+        mz, intensity, indptr, _ = self._peaks(mz, intensity, indptr, np.zeros(0, np.int64))
+        rep_mz, rep_intensity, rep_indptr, _ = self._peaks(rep_mz, rep_intensity, rep_indptr, np.zeros(0, np.int64))
+        if indptr.numel() != n + 1:
+            raise ValueError(f"member_scores: indptr has {indptr.numel()} entries for {n} labels")
+        n_rep = int(rep_indptr.numel()) - 1
+        if n_rep < 0:
+            raise ValueError("member_scores: the representatives' indptr is empty")
+        similarity = self.empty((n,), torch.float32)
+        matched = self.empty((n,), torch.int32)
+        ptr = lambda t: self._p(t if t is not None and t.numel() else None)
+        check(self.lib.fal_member_scores(self._h, ptr(mz), ptr(intensity), ptr(indptr), n, ptr(labels), nc, ptr(rep_mz),
+                                         ptr(rep_intensity), ptr(rep_indptr), n_rep, ptr(rep_row), float(fragment_tol),
+                                         ptr(similarity), ptr(matched)), "fal_member_scores")
+        return similarity, matched
+
+    SUMMARY_COLUMNS = ("size", "sim_min", "worst_row", "sim_mean", "pmz_min", "pmz_max", "rt_min", "rt_max")
+
+    def cluster_summary(self, labels, n_clusters: int, similarity, precursor_mz, retention_time=None):
+        """`fal_cluster_summary`: the per-cluster columns over a partition's member scores.  labels i32[n], similarity and
+        precursor_mz f32[n], retention_time f32[n] or None (rt_min / rt_max are 0 then).  Host or device arrays.
+        -> dict of device tensors [n_clusters]: size i32, sim_min f32, worst_row i32, sim_mean f64, pmz_min, pmz_max, rt_min,
+        rt_max f32.  Does not synchronise."""
+        torch = _torch()
+        labels = self.to_dev(labels, torch.int32)
+        similarity = self.to_dev(similarity, torch.float32)
+        pmz = self.to_dev(precursor_mz, torch.float32)
+        rt = None if retention_time is None else self.to_dev(retention_time, torch.float32)
+        n, nc = int(labels.numel()), int(n_clusters)
+        if similarity.numel() != n or pmz.numel() != n or (rt is not None and rt.numel() != n):
+            raise ValueError(f"cluster_summary: the columns do not all have {n} rows")
+        types = dict(size=torch.int32, worst_row=torch.int32, sim_mean=torch.float64)
+        out = {c: self.empty((nc,), types.get(c, torch.float32)) for c in self.SUMMARY_COLUMNS}
+        ptr = lambda t: self._p(t if t is not None and t.numel() else None)
+        check(self.lib.fal_cluster_summary(self._h, ptr(labels), n, nc, ptr(similarity), ptr(pmz), ptr(rt),
+                                           *(ptr(out[c]) for c in self.SUMMARY_COLUMNS)), "fal_cluster_summary")
+        return out
+
 
 class IvfIndex:
     """Opaque `fal_ivf` handle (keeps the vectors alive: the index borrows them)."""

@@ -28,7 +28,7 @@ import numpy as np
 from . import __version__
 from .cluster import cluster, spectrum
 from .config import config
-from .ms_io import csv_io, mgf_io, ms_io
+from .ms_io import csv_io, mgf_io, ms_io, summary_io
 
 logger = logging.getLogger("falcon")
 
@@ -56,13 +56,17 @@ def main(args: Union[str, List[str], None] = None) -> int:
         root.removeHandler(handler)
 
 
-def _option_lines() -> List[str]:
+def _option_lines(header: bool = False) -> List[str]:
+    """the option lines of the log; header=True: those of the output files' `#` header -- the same without `cluster_summary`,
+    which adds files and changes none (the cluster CSV is byte for byte the same with the flag)"""
     c = config
     # (the consensus options are listed only when chosen: the default header stays what it was)
     extra = ([f"representatives = {c.representatives}", f"consensus_min_fraction = {c.consensus_min_fraction:.3f}"]
              if c.representatives == "consensus" else [])
     if c.assign_to:          # (likewise: without the option every output is what it was)
         extra.append(f"assign_to = {' '.join(c.assign_to)}")
+    if c.cluster_summary and not header:
+        extra.append(f"cluster_summary = {c.cluster_summary}")
     return [
         f"work_dir = {c.work_dir}", f"overwrite = {c.overwrite}",
         f"export_representatives = {c.export_representatives}",
@@ -105,6 +109,7 @@ def _run(args) -> int:
     rows_all, current_label, representatives = [], 0, []
     csv_blocks = [] if config.csv_writer == "device" else None       # column blocks instead of a tuple per spectrum
     library = {}
+    summaries = [] if config.cluster_summary else None
     if config.assign_to:
         library, current_label = _load_library(spectra_dir, pipe.ctx)
     for charge in charges:                                                                     # falcon.py:153
@@ -121,9 +126,16 @@ def _run(args) -> int:
         labels, medoids = cluster.generate_clusters(
             ds, config.linkage, config.distance_threshold, config.min_matched_peaks, config.precursor_tol[0],
             config.precursor_tol[1], config.rt_tol, config.fragment_tol, config.batch_size, ann=ann, pipeline=pipe)
-        current_label = _emit_charge(part, charge, labels, medoids, current_label, rows_all, representatives,
-                                     _consensus(pipe.ctx, part, charge, labels, medoids), csv_blocks=csv_blocks)
+        consensus = _consensus(pipe.ctx, part, charge, labels, medoids)
+        if summaries is not None:
+            summaries.append(_summary_block(pipe, ds, part, charge, labels, medoids, consensus, current_label))
+        current_label = _emit_charge(part, charge, labels, medoids, current_label, rows_all, representatives, consensus,
+                                     csv_blocks=csv_blocks)
     _write_outputs(rows_all, representatives, pipe.ctx, csv_blocks=csv_blocks)
+    if summaries is not None:
+        logger.info("Export the cluster summary to output files %s.clusters.csv and %s.scores.csv", config.output_filename,
+                    config.output_filename)
+        summary_io.write(config.output_filename, _header_lines(), summaries)
     if rm_work_dir:
         shutil.rmtree(config.work_dir)
     return 0
@@ -201,7 +213,10 @@ def _setup_work_dir():
 
     # falcon.py:86-122: refuse to clobber existing outputs unless --overwrite
     exit_exists = False
-    for ext, what in ((".csv", "cluster assignments"), (".mgf", "cluster representatives")):
+    outputs = [(".csv", "cluster assignments"), (".mgf", "cluster representatives")]
+    if config.cluster_summary:
+        outputs += [(".clusters.csv", "cluster summary"), (".scores.csv", "member scores")]
+    for ext, what in outputs:
         fn = f"{config.output_filename}{ext}"
         if os.path.isfile(fn):
             if config.overwrite:
@@ -256,6 +271,18 @@ def _consensus(ctx, part, charge, labels, medoids):
     logger.info("Consensus representatives of charge %s: %d clusters, %d fell back to their medoid (no merged peak reached "
                 "the quorum)", charge, len(status), int(((status & CONS_FALLBACK) != 0).sum()))
     return indptr.cpu().numpy(), mz.cpu().numpy(), it.cpu().numpy()
+
+
+def _summary_block(pipe, ds, part, charge, labels, medoids, consensus, current_label):
+    """`--cluster_summary`, one charge: the members scored against their representatives (the medoids, or the consensus peaks
+    the exported MGF holds) and the per-cluster columns -> the charge's block of `summary_io`"""
+    cols = cluster.cluster_summary(ds, labels, medoids, config.fragment_tol, consensus=consensus, pipeline=pipe)
+    cols.update(charge=charge, cluster=np.arange(len(medoids), dtype=np.int64) + current_label,
+                labels=np.asarray(labels, np.int64) + current_label, filename=part["filename"], identifier=part["identifier"],
+                medoids=np.asarray(medoids, np.int64))
+    logger.info("Cluster summary of charge %s: %d clusters, mean member similarity %.4f", charge, len(medoids),
+                float(np.mean(cols["similarity"], dtype=np.float64)))
+    return cols
 
 
 def _emit_charge(part, charge, labels, medoids, current_label, rows_all, representatives, consensus=None, csv_blocks=None) -> int:
@@ -608,11 +635,15 @@ def _prepare_spectra(spectra_dir: str, min_mz: float, max_mz: float, ctx) -> Lis
     return sorted(parts, key=_natural_key)
 
 
+def _header_lines() -> List[str]:
+    """the `#` lines in front of the cluster CSV and of the cluster summary's files"""
+    return [f"falcon version {__version__}"] + _option_lines(header=True)
+
+
 def _write_csv_header(f):
     """the `#` lines and the column row -> the csv writer that wrote it"""
     import csv
-    f.write(f"# falcon version {__version__}\n")
-    for line in _option_lines():
+    for line in _header_lines():
         f.write(f"# {line}\n")
     f.write("#\n")
     w = csv.writer(f, quoting=csv.QUOTE_MINIMAL, lineterminator="\n")

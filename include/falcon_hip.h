@@ -90,6 +90,7 @@ int fal_ctx_enable_timing(fal_ctx* ctx, int on);
  *            that index is built / searched with the exact kernels (see fal_ivf_build_x16);
  * which = 7, 8: the part of counters 0 and 4 that belongs to flat buckets of up to 32 rows, whose kernel is not
  *            timed under stage 8 (subtract them to price stage 8's launches);
+ * which = 9: the pairs the Hungarian solver finished in the LAST fal_assign_nearest or fal_member_scores on this context;
  * which = 10: 1 when the last fal_cluster_graph_tiled ran per bucket tile, 0 when it took the per-row path. */
 int fal_ctx_counter(fal_ctx* ctx, int which, int64_t* value);
 
@@ -611,6 +612,34 @@ int fal_assign_nearest(fal_ctx* ctx, const float* q_mz, const float* q_intensity
                        const int64_t* l_indptr, const float* l_precursor_mz, const float* l_rt, int64_t nl, double tol,
                        int tol_is_da, double rt_tol, double fragment_tol, int min_matches, int32_t* best_row, float* best_dist,
                        int32_t* n_cand);
+
+/* ---- member scores: every spectrum of a clustered partition scored against the representative of its cluster (DESIGN.md
+ *          "Member scores and cluster summary").  mz / intensity f32, indptr i64[n+1]: the partition's peaks by dataset row;
+ *          labels i32[n]: cluster c is label value c in [0, n_clusters) (as fal_consensus_spectra takes them; a row with another
+ *          value scores 0 with 0 matches).  The representatives are rows of a second peaks CSR (rep_mz / rep_intensity f32,
+ *          rep_indptr i64[n_rep+1]): cluster c's is row rep_row[c] (i32[n_clusters]) -- the partition's own CSR with rep_row =
+ *          the medoids, or what fal_consensus_spectra returned with rep_row = 0, 1, ...; a rep_row outside [0, n_rep) is a
+ *          representative without peaks.
+ * -> similarity f32[n]: float32(cosine(member's peaks, representative's peaks)) with fal_rescore_neighbors' arithmetic, the
+ *    member first, clipped to [0, 1]; matched i32[n]: the matched peaks.  min_matched_peaks is not applied; a medoid is scored
+ *    against itself like any other pair; a side without peaks gives 0 and 0.
+ *    A pair whose peaks chain into a component of more than 32 peaks a side fails the call with FAL_EUNSUPPORTED.  n = 0 is a
+ *    no-op.  One stream synchronisation (error word and solver-pair count; fal_ctx_counter 9 = the pairs the Hungarian solver
+ *    finished, as after fal_assign_nearest). ------------------------------------------------------------------------ [dev] */
+int fal_member_scores(fal_ctx* ctx, const float* mz, const float* intensity, const int64_t* indptr, int64_t n,
+                      const int32_t* labels, int64_t n_clusters, const float* rep_mz, const float* rep_intensity,
+                      const int64_t* rep_indptr, int64_t n_rep, const int32_t* rep_row, double fragment_tol, float* similarity,
+                      int32_t* matched);
+
+/* ---- cluster summary: the per-cluster columns over a partition's member scores.  labels i32[n] as above; similarity,
+ *          precursor_mz f32[n]; retention_time f32[n] or NULL (rt_min / rt_max are 0 then).
+ * -> per cluster c in [0, n_clusters): size i32; sim_min f32 and worst_row i32 (the member with sim_min, the lowest row among
+ *    equals); sim_mean f64 = (float64 sum of the float32 similarities) / size, summed in the one order DESIGN.md states: the
+ *    members in row order, member p added to chain p mod 64, the 64 chain sums added in chain order; pmz_min / pmz_max /
+ *    rt_min / rt_max f32.  A cluster without members: zeros, worst_row -1.  No synchronisation. ------------------------- [dev] */
+int fal_cluster_summary(fal_ctx* ctx, const int32_t* labels, int64_t n, int64_t n_clusters, const float* similarity,
+                        const float* precursor_mz, const float* retention_time, int32_t* size, float* sim_min,
+                        int32_t* worst_row, double* sim_mean, float* pmz_min, float* pmz_max, float* rt_min, float* rt_max);
 
 /* ---- sort by precursor m/z (reference cluster.py:73-85 `.sort_values`): stable.
  *          order_out i64[n] (dataset row of sorted position), mz_sorted_out f32[n]. [dev] */
