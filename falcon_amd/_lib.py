@@ -24,6 +24,8 @@ MGF_FLAG_BYTES, MGF_FLAG_LINES, MGF_ST_HOST = 1, 2, 1
 # fal_mgf_write: the most bytes one number takes (csrc/mgfwrite.h kMgfNumMax)
 MGF_NUM_MAX = 23
 FAL_EINVAL = -1
+# fal_network_edges: the most peaks of one side of a scored pair (include/falcon_hip.h FAL_NET_MAX_PEAKS)
+NET_MAX_PEAKS = 4096
 # fal_csv_*: the most bytes one number takes (csrc/csvwrite.h kCsvNumMax), the rows the merge sort's first pass sorts per block
 CSV_NUM_MAX, CSV_SORT_BLOCK = 19, 1024
 # fal_mzml_index / fal_mzml_parse: the same for mzML text (include/falcon_hip.h)
@@ -147,6 +149,8 @@ _SIGNATURES = {
                            c_void_p, c_double, c_void_p, c_void_p], c_int),
     "fal_cluster_summary": ([c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                              c_void_p, c_void_p, c_void_p, c_void_p, c_void_p], c_int),
+    "fal_network_edges": ([c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_double, c_double, c_double,
+                           c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, P(c_int64)], c_int),
 }
 
 

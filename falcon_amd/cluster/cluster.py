@@ -903,6 +903,41 @@ def cluster_summary(dataset, labels, medoids, fragment_tol: float, consensus=Non
     return out
 
 
+def representative_network(dataset, medoids, fragment_tol: float, max_shift: float = 200.0, min_cosine: float = 0.7,
+                           min_matched_peaks: int = 6, top_k: int = 10, consensus=None,
+                           pipeline: Optional[ClusterPipeline] = None):
+    """Molecular network of the clusters `generate_clusters` returned for `dataset` (`fal_network_edges`; DESIGN.md
+    "Representative network"): cluster c is a node with the peaks of its medoid's spectrum -- or, with `consensus` (the (indptr,
+    mz, intensity) triple `consensus_spectra` returns), its consensus peaks -- and the medoid's precursor m/z.  Two clusters whose
+    precursors differ by at most `max_shift` m/z are linked when their greedy modified cosine (peaks matching at the same m/z or
+    shifted by the precursor difference; the GNPS / matchms matching, not the optimal assignment) is at least `min_cosine` with at
+    least `min_matched_peaks` matched peaks, and, with `top_k` > 0, the link is among the `top_k` best of both clusters.
+
+    Returns a dict of host arrays in (a, b) order: `a`, `b` int32 (cluster indices, a < b), `similarity` float32, `matched`
+    int32, `delta_mz` float32 = float32(precursor_mz[medoid b] - precursor_mz[medoid a])."""
+    global _default_pipeline
+    dataset = _as_dataset(dataset)
+    pipe = pipeline or _default_pipeline
+    if pipe is None:
+        pipe = _default_pipeline = ClusterPipeline()
+    ctx = pipe.ctx
+    import torch
+    m = ctx.to_dev(medoids, torch.int64)
+    pmz = ctx.to_dev(dataset.precursor_mz, torch.float32)[m]
+    if consensus is None:
+        indptr, mz, intensity, rows = dataset.indptr, dataset.mz, dataset.intensity, m.to(torch.int32)
+    else:
+        indptr, mz, intensity = consensus
+        rows = np.arange(len(m), dtype=np.int32)
+        if len(indptr) != len(m) + 1:
+            raise ValueError(f"consensus holds {len(indptr) - 1} spectra for {len(m)} clusters")
+    a, b, sim, matched = ctx.network_edges(mz, intensity, indptr, rows, pmz, fragment_tol, max_shift, min_cosine,
+                                           min_matched_peaks, top_k)
+    delta = pmz[b.long()] - pmz[a.long()]
+    return dict(a=a.cpu().numpy(), b=b.cpu().numpy(), similarity=sim.cpu().numpy(), matched=matched.cpu().numpy(),
+                delta_mz=delta.cpu().numpy())
+
+
 def write_representatives(filename: str, dataset: SpectrumDataset, medoids, cluster_ids, identifiers, charge: int = 0,
                           consensus=None, pipeline: Optional[ClusterPipeline] = None) -> str:
     """Write the representatives of `dataset`'s clusters to the MGF file `filename`, formatted on the device

@@ -47,6 +47,21 @@ class Config:
                             "and <output>.scores.csv (per spectrum: its similarity to its cluster's representative and the "
                             "matched peaks).  The representative is the medoid, or with --export_representatives "
                             "--representatives consensus the consensus spectrum.")
+        p.add_argument("--network", action="store_true",
+                       help="Also write <output>.network.csv: the molecular network of the cluster representatives.  Two clusters "
+                            "of one precursor charge are linked when the greedy modified cosine of their representatives (peaks "
+                            "matching at the same m/z or shifted by the precursor difference) passes the --network_* thresholds.  "
+                            "The representative is the medoid, or with --export_representatives --representatives consensus the "
+                            "consensus spectrum.")
+        p.add_argument("--network_min_cosine", type=float, default=0.7,
+                       help="--network: smallest modified cosine of a link (0 <= c <= 1, default: 0.7).")
+        p.add_argument("--network_min_matched_peaks", type=int, default=6,
+                       help="--network: smallest number of matched peaks of a link (default: 6).")
+        p.add_argument("--network_top_k", type=int, default=10,
+                       help="--network: a link is kept when it is among the top_k most similar links of both of its clusters "
+                            "(default: 10; 0 = keep every link).")
+        p.add_argument("--network_max_shift", type=float, default=200.0,
+                       help="--network: largest precursor m/z difference of two linked clusters (default: 200.0).")
         p.add_argument("--assign_to", nargs="+", default=None, metavar="FILE",
                        help="Representative MGF files of earlier runs (--export_representatives output, one CLUSTER= id per "
                             "entry): a new spectrum whose nearest representative inside the precursor (and RT) tolerance lies "
@@ -211,6 +226,19 @@ class Config:
                                "are not in the run)")
         if ns["cluster_summary"] and ns["distributed"]:
             self._parser.error("--cluster_summary does not combine with --distributed (the summary is not sharded)")
+        if not 0.0 <= ns["network_min_cosine"] <= 1.0:
+            self._parser.error(f"--network_min_cosine {ns['network_min_cosine']} is outside [0, 1]")
+        if ns["network_min_matched_peaks"] < 0:
+            self._parser.error(f"--network_min_matched_peaks {ns['network_min_matched_peaks']} is negative")
+        if ns["network_top_k"] < 0:
+            self._parser.error(f"--network_top_k {ns['network_top_k']} is negative")
+        if not ns["network_max_shift"] >= 0.0:
+            self._parser.error(f"--network_max_shift {ns['network_max_shift']} is negative")
+        if ns["network"] and ns["assign_to"]:
+            self._parser.error("--network does not combine with --assign_to (the representatives of the existing clusters are "
+                               "not in the run)")
+        if ns["network"] and ns["distributed"]:
+            self._parser.error("--network does not combine with --distributed (the network is not sharded)")
         if not 1 <= ns["low_dim"] <= 800:
             raise ValueError("low_dim must be an integer in [1, 800] (README.md:114-117; the widest rows the kernels hold)")
         if ns["n_neighbors_ann"] < ns["n_neighbors"]:

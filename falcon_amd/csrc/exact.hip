@@ -328,6 +328,16 @@ static int exact_csr_dev(fal_ctx* ctx, const ExEdges& ed, int64_t n, int64_t** p
     return FAL_OK;
 }
 
+// util.h: the library's one instantiation of the 64-bit pair sort (exact mode's edges; network.hip's edges and rank entries)
+int sort_pairs_u64_f64(fal_ctx* ctx, uint64_t* kin, uint64_t* kout, double* vin, double* vout, int64_t n, int scratch_slot) {
+    size_t bytes = 0;
+    FAL_CHECK_HIP(rocprim::radix_sort_pairs(nullptr, bytes, kin, kout, vin, vout, (size_t)n, 0, 64, ctx->stream));
+    void* tmp = nullptr;
+    FAL_TRY(ctx->reserve(scratch_slot, bytes + 16, &tmp));
+    FAL_CHECK_HIP(rocprim::radix_sort_pairs(tmp, bytes, kin, kout, vin, vout, (size_t)n, 0, 64, ctx->stream));
+    return FAL_OK;
+}
+
 static ExactPeaks make_peaks(const float* mz, const float* intensity, const int64_t* indptr, const int64_t* row_order,
                              double fragment_tol, int min_matches) {
     ExactPeaks pk;
@@ -385,13 +395,7 @@ int fal_exact_edges(fal_ctx* ctx, const float* mz, const float* intensity, const
     uint64_t* kout = reinterpret_cast<uint64_t*>(sb);
     double* vout = reinterpret_cast<double*>(kout + m);
     int32_t* deg = reinterpret_cast<int32_t*>(vout + m);
-    if (m > 0) {
-        size_t bytes = 0;
-        FAL_CHECK_HIP(rocprim::radix_sort_pairs(nullptr, bytes, ed.keys, kout, ed.vals, vout, (size_t)m, 0, 64, st));
-        void* tmp = nullptr;
-        FAL_TRY(ctx->reserve(SLOT_EXACT6, bytes + 16, &tmp));
-        FAL_CHECK_HIP(rocprim::radix_sort_pairs(tmp, bytes, ed.keys, kout, ed.vals, vout, (size_t)m, 0, 64, st));
-    }
+    if (m > 0) FAL_TRY(sort_pairs_u64_f64(ctx, ed.keys, kout, ed.vals, vout, m, SLOT_EXACT6));
     const int egrid = (int)std::min<int64_t>(ceil_div(std::max<int64_t>(m, 1), 256), (int64_t)ctx->num_cus * 32);
     FAL_CHECK_HIP(hipMemsetAsync(deg, 0, sizeof(int32_t) * (size_t)n, st));
     if (m > 0) {

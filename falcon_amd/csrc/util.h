@@ -38,6 +38,9 @@ int device_scan_i64(fal_ctx* ctx, const int64_t* in, int64_t n, int64_t* out, in
 // stable LSD radix sort of (uint32 key, int32 value) pairs on bits [0, end_bit)
 int sort_pairs_u32_i32(fal_ctx* ctx, const uint32_t* kin, uint32_t* kout, const int32_t* vin, int32_t* vout,
                        int64_t n, int end_bit, int scratch_slot);
+// stable LSD radix sort of (uint64 key, 8-byte value) pairs on all 64 key bits (exact.hip).  The values are only moved: any
+// 8-byte payload may travel as the bit pattern of a double
+int sort_pairs_u64_f64(fal_ctx* ctx, uint64_t* kin, uint64_t* kout, double* vin, double* vout, int64_t n, int scratch_slot);
 // a9 / a10 / a11+a12 with every count left on the device (graph.hip, tail.hip)
 // (*extent_out: per row, one past its last stored neighbour -- valid until SLOT_DB is reserved again)
 int dbscan_dev(fal_ctx* ctx, const int32_t* nb_idx, const float* nb_dist, int64_t n, int k, float eps, int32_t* labels,

@@ -888,6 +888,42 @@ class Context:
                                            *(ptr(out[c]) for c in self.SUMMARY_COLUMNS)), "fal_cluster_summary")
         return out
 
+    # ------------------------------------------------------------------ representative network
+    def network_edges(self, mz, intensity, indptr, rows, precursor_mz, fragment_tol: float, max_shift: float = 200.0,
+                      min_cosine: float = 0.7, min_matched: int = 6, top_k: int = 10, max_edges: Optional[int] = None):
+        """`fal_network_edges`: the pairs of nodes whose greedy modified cosine is high (DESIGN.md "Representative network").
+        mz / intensity f32, indptr i64: a peak CSR; node v is its row rows[v] (i32[n]) with precursor m/z precursor_mz[v]
+        (f32[n]).  Host or device arrays.  `max_edges`: the room of the first call (default 16 edges a node); a result that
+        does not fit is fetched by a second call with the room the first one reported.
+        -> u i32[m] < v i32[m] (node indices), similarity f32[m], matched i32[m] in (u, v) order.  Device tensors; the call
+        synchronises up to five times."""
+        torch = _torch()
+        rows = self.to_dev(rows, torch.int32)
+        pmz = self.to_dev(precursor_mz, torch.float32)
+        n = int(rows.numel())
+        if pmz.numel() != n:
+            raise ValueError(f"network_edges: {pmz.numel()} precursors for {n} nodes")
+        mz, intensity, indptr, _ = self._peaks(mz, intensity, indptr, np.zeros(0, np.int64))
+        n_csr = int(indptr.numel()) - 1
+        if n_csr < 0:
+            raise ValueError("network_edges: indptr is empty")
+        room =int(16 * n if max_edges is None else max_edges)
+        m = C.c_int64()
+        ptr = lambda t: self._p(t if t is not None and t.numel() else None)
+        for _ in range(2):
+            u, v = self.empty((room,), torch.int32), self.empty((room,), torch.int32)
+            sim, matched = self.empty((room,), torch.float32), self.empty((room,), torch.int32)
+            rc = self.lib.fal_network_edges(self._h, ptr(mz), ptr(intensity), ptr(indptr), n_csr, ptr(rows), ptr(pmz), n,
+                                            float(fragment_tol), float(max_shift), float(min_cosine), int(min_matched), int(top_k),
+                                            ptr(u), ptr(v), ptr(sim), ptr(matched), room, C.byref(m))
+            if rc == _lib.FAL_EINVAL and m.value > room:
+                room = int(m.value)              # the edges did not fit: once more with room for them
+                continue
+            break
+        check(rc, "fal_network_edges")
+        k = int(m.value)
+        return u[:k], v[:k], sim[:k], matched[:k]
+
 
 class IvfIndex:
     """Opaque `fal_ivf` handle (keeps the vectors alive: the index borrows them)."""

@@ -28,7 +28,7 @@ import numpy as np
 from . import __version__
 from .cluster import cluster, spectrum
 from .config import config
-from .ms_io import csv_io, mgf_io, ms_io, summary_io
+from .ms_io import csv_io, mgf_io, ms_io, network_io, summary_io
 
 logger = logging.getLogger("falcon")
 
@@ -57,8 +57,8 @@ def main(args: Union[str, List[str], None] = None) -> int:
 
 
 def _option_lines(header: bool = False) -> List[str]:
-    """the option lines of the log; header=True: those of the output files' `#` header -- the same without `cluster_summary`,
-    which adds files and changes none (the cluster CSV is byte for byte the same with the flag)"""
+    """the option lines of the log; header=True: those of the output files' `#` header -- the same without `cluster_summary`
+    and the `network` lines, which add files and change none (the cluster CSV is byte for byte the same with the flags)"""
     c = config
     # (the consensus options are listed only when chosen: the default header stays what it was)
     extra = ([f"representatives = {c.representatives}", f"consensus_min_fraction = {c.consensus_min_fraction:.3f}"]
@@ -67,6 +67,8 @@ def _option_lines(header: bool = False) -> List[str]:
         extra.append(f"assign_to = {' '.join(c.assign_to)}")
     if c.cluster_summary and not header:
         extra.append(f"cluster_summary = {c.cluster_summary}")
+    if c.network and not header:
+        extra += _network_lines()
     return [
         f"work_dir = {c.work_dir}", f"overwrite = {c.overwrite}",
         f"export_representatives = {c.export_representatives}",
@@ -83,6 +85,14 @@ def _option_lines(header: bool = False) -> List[str]:
         f"rescore = {c.rescore}", f"clustering = {c.clustering}", f"dtype = {c.dtype}",
         f"exact = {c.exact}",
     ] + extra
+
+
+def _network_lines() -> List[str]:
+    """the option lines of `--network`: in the log and in the `#` header of <output>.network.csv alone"""
+    c = config
+    return [f"network = {c.network}", f"network_min_cosine = {c.network_min_cosine:.3f}",
+            f"network_min_matched_peaks = {c.network_min_matched_peaks}", f"network_top_k = {c.network_top_k}",
+            f"network_max_shift = {c.network_max_shift:.3f}"]
 
 
 def _run(args) -> int:
@@ -110,6 +120,7 @@ def _run(args) -> int:
     csv_blocks = [] if config.csv_writer == "device" else None       # column blocks instead of a tuple per spectrum
     library = {}
     summaries = [] if config.cluster_summary else None
+    networks = [] if config.network else None
     if config.assign_to:
         library, current_label = _load_library(spectra_dir, pipe.ctx)
     for charge in charges:                                                                     # falcon.py:153
@@ -129,6 +140,8 @@ def _run(args) -> int:
         consensus = _consensus(pipe.ctx, part, charge, labels, medoids)
         if summaries is not None:
             summaries.append(_summary_block(pipe, ds, part, charge, labels, medoids, consensus, current_label))
+        if networks is not None:
+            networks.append(_network_block(pipe, ds, charge, medoids, consensus, current_label))
         current_label = _emit_charge(part, charge, labels, medoids, current_label, rows_all, representatives, consensus,
                                      csv_blocks=csv_blocks)
     _write_outputs(rows_all, representatives, pipe.ctx, csv_blocks=csv_blocks)
@@ -136,6 +149,9 @@ def _run(args) -> int:
         logger.info("Export the cluster summary to output files %s.clusters.csv and %s.scores.csv", config.output_filename,
                     config.output_filename)
         summary_io.write(config.output_filename, _header_lines(), summaries)
+    if networks is not None:
+        logger.info("Export the representative network to output file %s.network.csv", config.output_filename)
+        network_io.write(config.output_filename, _header_lines() + _network_lines(), networks)
     if rm_work_dir:
         shutil.rmtree(config.work_dir)
     return 0
@@ -216,6 +232,8 @@ def _setup_work_dir():
     outputs = [(".csv", "cluster assignments"), (".mgf", "cluster representatives")]
     if config.cluster_summary:
         outputs += [(".clusters.csv", "cluster summary"), (".scores.csv", "member scores")]
+    if config.network:
+        outputs += [(".network.csv", "representative network")]
     for ext, what in outputs:
         fn = f"{config.output_filename}{ext}"
         if os.path.isfile(fn):
@@ -282,6 +300,16 @@ def _summary_block(pipe, ds, part, charge, labels, medoids, consensus, current_l
                 medoids=np.asarray(medoids, np.int64))
     logger.info("Cluster summary of charge %s: %d clusters, mean member similarity %.4f", charge, len(medoids),
                 float(np.mean(cols["similarity"], dtype=np.float64)))
+    return cols
+
+
+def _network_block(pipe, ds, charge, medoids, consensus, current_label):
+    """`--network`, one charge: the links between its clusters' representatives (the medoids, or the consensus peaks the exported
+    MGF holds) -> the charge's block of `network_io`"""
+    cols = cluster.representative_network(ds, medoids, config.fragment_tol, config.network_max_shift, config.network_min_cosine,
+                                          config.network_min_matched_peaks, config.network_top_k, consensus=consensus, pipeline=pipe)
+    cols.update(charge=charge, first=current_label)
+    logger.info("Representative network of charge %s: %d clusters, %d links", charge, len(medoids), len(cols["a"]))
     return cols
 
 

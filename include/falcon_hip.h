@@ -91,7 +91,9 @@ int fal_ctx_enable_timing(fal_ctx* ctx, int on);
  * which = 7, 8: the part of counters 0 and 4 that belongs to flat buckets of up to 32 rows, whose kernel is not
  *            timed under stage 8 (subtract them to price stage 8's launches);
  * which = 9: the pairs the Hungarian solver finished in the LAST fal_assign_nearest or fal_member_scores on this context;
- * which = 10: 1 when the last fal_cluster_graph_tiled ran per bucket tile, 0 when it took the per-row path. */
+ * which = 10: 1 when the last fal_cluster_graph_tiled ran per bucket tile, 0 when it took the per-row path;
+ * which = 11: the tiles of that call whose eps-edges took the edge list's second pass;
+ * which = 12: the pairs the greedy kernel finished in the LAST fal_network_edges on this context. */
 int fal_ctx_counter(fal_ctx* ctx, int which, int64_t* value);
 
 /* ---- a1  bin geometry: reference spectrum.py:172-199 `get_dim` (float32) --- [host] */
@@ -640,6 +642,32 @@ int fal_member_scores(fal_ctx* ctx, const float* mz, const float* intensity, con
 int fal_cluster_summary(fal_ctx* ctx, const int32_t* labels, int64_t n, int64_t n_clusters, const float* similarity,
                         const float* precursor_mz, const float* retention_time, int32_t* size, float* sim_min,
                         int32_t* worst_row, double* sim_mean, float* pmz_min, float* pmz_max, float* rt_min, float* rt_max);
+
+/* ---- representative network: the pairs of `n` nodes whose greedy modified cosine is high (DESIGN.md "Representative
+ *          network").  Node v is row rows[v] (i32[n]) of the peaks CSR mz / intensity f32, indptr i64[n_csr_rows + 1] (m/z
+ *          ascending inside a row) with precursor m/z precursor_mz[v] (f32[n]); one precursor charge; n < 2^31.
+ *          A pair (a, b), a in front of b in (precursor m/z, node index) order, is in scope when
+ *          fabs((double)(float)(pmz[b] - pmz[a])) <= max_shift; only pairs in scope are scored.  shift = (float)(pmz[a] - pmz[b]).
+ *          Peaks i of a and j of b are a candidate when (double)fabsf(amz[i] - bmz[j]) <= fragment_tol or
+ *          (double)fabsf((amz[i] - shift) - bmz[j]) <= fragment_tol (float32 subtractions in this order) and the float32 product
+ *          w = ait[i] * bit[j] is > 0.  Candidates are taken by (w descending, i ascending, j ascending) and accepted when
+ *          neither peak was accepted before: the greedy modified cosine of GNPS and matchms, NOT the optimal assignment.
+ *          score = the float64 sum of the accepted w in ascending i; sim = (float)fmax(0, fmin(score, 1)); matched = the number
+ *          accepted.  The pair is an edge when matched >= max(min_matched, 1) and sim >= (float)min_cosine.  top_k > 0: a
+ *          node's edges are ranked by (sim descending, other node ascending), an edge stays when its rank is below top_k at both
+ *          of its nodes; top_k = 0: no such filter.
+ * -> the edges (edge_u i32 < edge_v i32 node indices, edge_sim f32, edge_matched i32; room for max_edges each) in (u, v) order
+ *    and *n_edges (host).  The result depends on the arguments alone.  More edges than max_edges: FAL_EINVAL with *n_edges set
+ *    (call again with room for them); nothing is written then.  A pair in scope with a side of more than FAL_NET_MAX_PEAKS
+ *    peaks fails the call with FAL_EUNSUPPORTED (the same node outside every scope fails nothing); a row outside the CSR, or
+ *    of more than 2^24 peaks: FAL_EINVAL.  n = 0 is a no-op.  At most five stream synchronisations: the tile count; the list
+ *    and edge counts (again, up to twice, when a list or the edge buffer was too short); with top_k > 0 the kept edges.
+ *    fal_ctx_counter 12 = the pairs the greedy kernel finished. --------------------------------------------------------- [dev] */
+#define FAL_NET_MAX_PEAKS 4096
+int fal_network_edges(fal_ctx* ctx, const float* mz, const float* intensity, const int64_t* indptr, int64_t n_csr_rows,
+                      const int32_t* rows, const float* precursor_mz, int64_t n, double fragment_tol, double max_shift,
+                      double min_cosine, int min_matched, int top_k, int32_t* edge_u, int32_t* edge_v, float* edge_sim,
+                      int32_t* edge_matched, int64_t max_edges, int64_t* n_edges);
 
 /* ---- sort by precursor m/z (reference cluster.py:73-85 `.sort_values`): stable.
  *          order_out i64[n] (dataset row of sorted position), mz_sorted_out f32[n]. [dev] */
