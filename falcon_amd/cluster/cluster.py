@@ -905,7 +905,7 @@ def cluster_summary(dataset, labels, medoids, fragment_tol: float, consensus=Non
 
 def representative_network(dataset, medoids, fragment_tol: float, max_shift: float = 200.0, min_cosine: float = 0.7,
                            min_matched_peaks: int = 6, top_k: int = 10, consensus=None,
-                           pipeline: Optional[ClusterPipeline] = None):
+                           pipeline: Optional[ClusterPipeline] = None, on_device: bool = False):
     """Molecular network of the clusters `generate_clusters` returned for `dataset` (`fal_network_edges`; DESIGN.md
     "Representative network"): cluster c is a node with the peaks of its medoid's spectrum -- or, with `consensus` (the (indptr,
     mz, intensity) triple `consensus_spectra` returns), its consensus peaks -- and the medoid's precursor m/z.  Two clusters whose
@@ -914,7 +914,8 @@ def representative_network(dataset, medoids, fragment_tol: float, max_shift: flo
     least `min_matched_peaks` matched peaks, and, with `top_k` > 0, the link is among the `top_k` best of both clusters.
 
     Returns a dict of host arrays in (a, b) order: `a`, `b` int32 (cluster indices, a < b), `similarity` float32, `matched`
-    int32, `delta_mz` float32 = float32(precursor_mz[medoid b] - precursor_mz[medoid a])."""
+    int32, `delta_mz` float32 = float32(precursor_mz[medoid b] - precursor_mz[medoid a]).  `on_device`: the same columns as device
+    tensors (what `network_families` takes without another copy)."""
     global _default_pipeline
     dataset = _as_dataset(dataset)
     pipe = pipeline or _default_pipeline
@@ -933,9 +934,37 @@ def representative_network(dataset, medoids, fragment_tol: float, max_shift: flo
             raise ValueError(f"consensus holds {len(indptr) - 1} spectra for {len(m)} clusters")
     a, b, sim, matched = ctx.network_edges(mz, intensity, indptr, rows, pmz, fragment_tol, max_shift, min_cosine,
                                            min_matched_peaks, top_k)
-    delta = pmz[b.long()] - pmz[a.long()]
-    return dict(a=a.cpu().numpy(), b=b.cpu().numpy(), similarity=sim.cpu().numpy(), matched=matched.cpu().numpy(),
-                delta_mz=delta.cpu().numpy())
+    cols = dict(a=a, b=b, similarity=sim, matched=matched, delta_mz=pmz[b.long()] - pmz[a.long()])
+    return cols if on_device else {k: v.cpu().numpy() for k, v in cols.items()}
+
+
+def network_families(network, n_clusters: int, max_size: int = 100, delta: float = 0.02,
+                     pipeline: Optional[ClusterPipeline] = None):
+    """Molecular families of the network `representative_network` returned for `n_clusters` clusters (`fal_network_families`;
+    DESIGN.md "Molecular families"): the connected components of its links.  While a component has more than `max_size`
+    clusters (0: no cap), a round cuts those of its links whose similarity is within `delta` of its weakest link's.
+
+    Returns the same dict restricted to the surviving links, in their order, as host arrays, plus `family` int32 (per surviving
+    link, the family of its two clusters), `node_family` int32 (per cluster; families are numbered by their smallest cluster,
+    -1: the cluster has no surviving link), `node_size` int32 (per cluster, the clusters of its family; 1 without one),
+    `n_families`, `n_rounds` and `n_cut` (the links cut)."""
+    global _default_pipeline
+    pipe = pipeline or _default_pipeline
+    if pipe is None:
+        pipe = _default_pipeline = ClusterPipeline()
+    ctx = pipe.ctx
+    import torch
+    types = dict(a=torch.int32, b=torch.int32, similarity=torch.float32, matched=torch.int32, delta_mz=torch.float32)
+    cols = {k: ctx.to_dev(network[k], t) for k, t in types.items()}
+    family, size, edge_round, n_families, n_rounds = ctx.network_families(cols["a"], cols["b"], cols["similarity"], n_clusters,
+                                                                          max_size, delta)
+    n_cut = ctx.counter(13)
+    keep = edge_round == 0
+    out = {k: v[keep].cpu().numpy() for k, v in cols.items()}
+    out["family"] = family[cols["a"][keep].long()].cpu().numpy()
+    out.update(node_family=family.cpu().numpy(), node_size=size.cpu().numpy(), n_families=n_families, n_rounds=n_rounds,
+               n_cut=n_cut)
+    return out
 
 
 def write_representatives(filename: str, dataset: SpectrumDataset, medoids, cluster_ids, identifiers, charge: int = 0,

@@ -62,6 +62,16 @@ class Config:
                             "(default: 10; 0 = keep every link).")
         p.add_argument("--network_max_shift", type=float, default=200.0,
                        help="--network: largest precursor m/z difference of two linked clusters (default: 200.0).")
+        p.add_argument("--network_families", action="store_true",
+                       help="--network: also group the clusters into molecular families, the connected components of the "
+                            "network, and write <output>.families.csv (per cluster: its family and the family's size).  A family "
+                            "above --network_max_family_size is broken up by cutting its weakest links round by round; "
+                            "<output>.network.csv then holds the surviving links only, with a family column.")
+        p.add_argument("--network_max_family_size", type=int, default=100,
+                       help="--network_families: the most clusters of one family (default: 100; 0 = no cap).")
+        p.add_argument("--network_family_delta", type=float, default=0.02,
+                       help="--network_families: a round cuts the links of an oversized family whose cosine is within this "
+                            "much of the family's weakest link (default: 0.02).")
         p.add_argument("--assign_to", nargs="+", default=None, metavar="FILE",
                        help="Representative MGF files of earlier runs (--export_representatives output, one CLUSTER= id per "
                             "entry): a new spectrum whose nearest representative inside the precursor (and RT) tolerance lies "
@@ -239,6 +249,12 @@ class Config:
                                "not in the run)")
         if ns["network"] and ns["distributed"]:
             self._parser.error("--network does not combine with --distributed (the network is not sharded)")
+        if ns["network_families"] and not ns["network"]:
+            self._parser.error("--network_families needs --network (the families are the components of its links)")
+        if ns["network_max_family_size"] < 0:
+            self._parser.error(f"--network_max_family_size {ns['network_max_family_size']} is negative")
+        if not ns["network_family_delta"] >= 0.0:
+            self._parser.error(f"--network_family_delta {ns['network_family_delta']} is negative")
         if not 1 <= ns["low_dim"] <= 800:
             raise ValueError("low_dim must be an integer in [1, 800] (README.md:114-117; the widest rows the kernels hold)")
         if ns["n_neighbors_ann"] < ns["n_neighbors"]:

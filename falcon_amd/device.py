@@ -924,6 +924,27 @@ class Context:
         k = int(m.value)
         return u[:k], v[:k], sim[:k], matched[:k]
 
+    def network_families(self, u, v, sim, n: int, max_size: int = 100, delta: float = 0.02):
+        """`fal_network_families`: the connected components of `n` nodes under the edges (u, v i32[m], sim f32[m]; host or
+        device arrays, `network_edges`' output as it comes), cut until none has more than `max_size` nodes (0: no cap; DESIGN.md
+        "Molecular families").
+        -> family i32[n] (-1: no surviving edge), size i32[n], edge_round i32[m] (0: the edge survives) as device tensors,
+        n_families, n_rounds.  The call synchronises n_rounds + 2 times."""
+        torch = _torch()
+        u, v, sim = self.to_dev(u, torch.int32), self.to_dev(v, torch.int32), self.to_dev(sim, torch.float32)
+        m, n = int(u.numel()), int(n)
+        if v.numel() != m or sim.numel() != m:
+            raise ValueError(f"network_families: the edge columns do not all have {m} rows")
+        if n < 0:
+            raise ValueError(f"network_families: {n} nodes")
+        family, size = self.empty((n,), torch.int32), self.empty((n,), torch.int32)
+        edge_round = self.empty((m,), torch.int32)
+        nf, nr = C.c_int64(), C.c_int64()
+        ptr = lambda t: self._p(t if t.numel() else None)
+        check(self.lib.fal_network_families(self._h, ptr(u), ptr(v), ptr(sim), m, n, int(max_size), float(delta), ptr(family),
+                                            ptr(size), ptr(edge_round), C.byref(nf), C.byref(nr)), "fal_network_families")
+        return family, size, edge_round, int(nf.value), int(nr.value)
+
 
 class IvfIndex:
     """Opaque `fal_ivf` handle (keeps the vectors alive: the index borrows them)."""

@@ -68,7 +68,7 @@ def _option_lines(header: bool = False) -> List[str]:
     if c.cluster_summary and not header:
         extra.append(f"cluster_summary = {c.cluster_summary}")
     if c.network and not header:
-        extra += _network_lines()
+        extra += _network_lines() + _family_lines()
     return [
         f"work_dir = {c.work_dir}", f"overwrite = {c.overwrite}",
         f"export_representatives = {c.export_representatives}",
@@ -93,6 +93,16 @@ def _network_lines() -> List[str]:
     return [f"network = {c.network}", f"network_min_cosine = {c.network_min_cosine:.3f}",
             f"network_min_matched_peaks = {c.network_min_matched_peaks}", f"network_top_k = {c.network_top_k}",
             f"network_max_shift = {c.network_max_shift:.3f}"]
+
+
+def _family_lines() -> List[str]:
+    """the option lines of `--network_families`, none without the flag: behind `_network_lines()` in the log and in the `#`
+    headers of <output>.network.csv and <output>.families.csv"""
+    c = config
+    if not c.network_families:
+        return []
+    return [f"network_families = {c.network_families}", f"network_max_family_size = {c.network_max_family_size}",
+            f"network_family_delta = {c.network_family_delta:.3f}"]
 
 
 def _run(args) -> int:
@@ -149,7 +159,11 @@ def _run(args) -> int:
         logger.info("Export the cluster summary to output files %s.clusters.csv and %s.scores.csv", config.output_filename,
                     config.output_filename)
         summary_io.write(config.output_filename, _header_lines(), summaries)
-    if networks is not None:
+    if networks is not None and config.network_families:
+        logger.info("Export the representative network and its families to output files %s.network.csv and %s.families.csv",
+                    config.output_filename, config.output_filename)
+        network_io.write_with_families(config.output_filename, _header_lines() + _network_lines() + _family_lines(), networks)
+    elif networks is not None:
         logger.info("Export the representative network to output file %s.network.csv", config.output_filename)
         network_io.write(config.output_filename, _header_lines() + _network_lines(), networks)
     if rm_work_dir:
@@ -234,6 +248,8 @@ def _setup_work_dir():
         outputs += [(".clusters.csv", "cluster summary"), (".scores.csv", "member scores")]
     if config.network:
         outputs += [(".network.csv", "representative network")]
+    if config.network_families:
+        outputs += [(".families.csv", "molecular families")]
     for ext, what in outputs:
         fn = f"{config.output_filename}{ext}"
         if os.path.isfile(fn):
@@ -307,9 +323,15 @@ def _network_block(pipe, ds, charge, medoids, consensus, current_label):
     """`--network`, one charge: the links between its clusters' representatives (the medoids, or the consensus peaks the exported
     MGF holds) -> the charge's block of `network_io`"""
     cols = cluster.representative_network(ds, medoids, config.fragment_tol, config.network_max_shift, config.network_min_cosine,
-                                          config.network_min_matched_peaks, config.network_top_k, consensus=consensus, pipeline=pipe)
-    cols.update(charge=charge, first=current_label)
+                                          config.network_min_matched_peaks, config.network_top_k, consensus=consensus, pipeline=pipe,
+                                          on_device=config.network_families)
     logger.info("Representative network of charge %s: %d clusters, %d links", charge, len(medoids), len(cols["a"]))
+    if config.network_families:          # (the links stay on the device from the edge kernels to the family ids)
+        cols = cluster.network_families(cols, len(medoids), config.network_max_family_size, config.network_family_delta,
+                                        pipeline=pipe)
+        logger.info("Molecular families of charge %s: %d families, %d links cut in %d rounds", charge, cols["n_families"],
+                    cols["n_cut"], cols["n_rounds"])
+    cols.update(charge=charge, first=current_label)
     return cols
 
 

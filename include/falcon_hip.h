@@ -93,7 +93,8 @@ int fal_ctx_enable_timing(fal_ctx* ctx, int on);
  * which = 9: the pairs the Hungarian solver finished in the LAST fal_assign_nearest or fal_member_scores on this context;
  * which = 10: 1 when the last fal_cluster_graph_tiled ran per bucket tile, 0 when it took the per-row path;
  * which = 11: the tiles of that call whose eps-edges took the edge list's second pass;
- * which = 12: the pairs the greedy kernel finished in the LAST fal_network_edges on this context. */
+ * which = 12: the pairs the greedy kernel finished in the LAST fal_network_edges on this context;
+ * which = 13: the edges the LAST fal_network_families on this context cut. */
 int fal_ctx_counter(fal_ctx* ctx, int which, int64_t* value);
 
 /* ---- a1  bin geometry: reference spectrum.py:172-199 `get_dim` (float32) --- [host] */
@@ -668,6 +669,23 @@ int fal_network_edges(fal_ctx* ctx, const float* mz, const float* intensity, con
                       const int32_t* rows, const float* precursor_mz, int64_t n, double fragment_tol, double max_shift,
                       double min_cosine, int min_matched, int top_k, int32_t* edge_u, int32_t* edge_v, float* edge_sim,
                       int32_t* edge_matched, int64_t max_edges, int64_t* n_edges);
+
+/* ---- molecular families: the connected components of `n` nodes under the `m` edges (edge_u, edge_v i32[m], edge_sim f32[m];
+ *          fal_network_edges' output is the normal input, any order and duplicates give the same result), broken up until none
+ *          has more than max_size nodes (DESIGN.md "Molecular families"; max_size = 0: no cap).  Every edge starts alive.  A
+ *          pass takes the components of the alive edges; while one has more than max_size nodes the pass is a cutting round
+ *          r = 1, 2, ...: lo = the smallest sim among the alive edges of such a component (float32), and its alive edges with
+ *          (double)sim <= (double)lo + delta are cut in round r.  Components within the cap keep their edges.
+ * -> node_family i32[n]: the components of two or more nodes numbered 0, 1, ... by their smallest node, -1 for a node without a
+ *    surviving edge; node_size i32[n]: the nodes of the node's component (1 for those); edge_round i32[m]: 0 for a surviving
+ *    edge, else the round that cut it; *n_families and *n_rounds (host).  The result depends on the arguments alone.  m = 0:
+ *    every node -1 / 1.  n = 0 (with m = 0) is a no-op.  FAL_EINVAL, with nothing written and the context usable: an end
+ *    outside [0, n), u == v, a sim that is NaN, infinite or negative, max_size < 0, delta negative or NaN.  One stream
+ *    synchronisation per pass (*n_rounds + 1 passes: whether a component is above the cap) plus one for the counts.
+ *    fal_ctx_counter 13 = the edges cut. -------------------------------------------------------------------------------- [dev] */
+int fal_network_families(fal_ctx* ctx, const int32_t* edge_u, const int32_t* edge_v, const float* edge_sim, int64_t m, int64_t n,
+                         int max_size, double delta, int32_t* node_family, int32_t* node_size, int32_t* edge_round,
+                         int64_t* n_families, int64_t* n_rounds);
 
 /* ---- sort by precursor m/z (reference cluster.py:73-85 `.sort_values`): stable.
  *          order_out i64[n] (dataset row of sorted position), mz_sorted_out f32[n]. [dev] */
