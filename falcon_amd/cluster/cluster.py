@@ -938,6 +938,47 @@ def representative_network(dataset, medoids, fragment_tol: float, max_shift: flo
     return cols if on_device else {k: v.cpu().numpy() for k, v in cols.items()}
 
 
+def library_search(dataset, medoids, library, fragment_tol: float, precursor_tol: float, mode: str, analog: bool = False,
+                   max_shift: float = 200.0, min_cosine: float = 0.7, min_matched_peaks: int = 6, top_n: int = 1, consensus=None,
+                   pipeline: Optional[ClusterPipeline] = None):
+    """Library search of the clusters `generate_clusters` returned for `dataset` (`fal_library_search`; DESIGN.md "Library
+    search"): cluster c is a query with the peaks of its medoid's spectrum -- or, with `consensus` (the (indptr, mz, intensity)
+    triple `consensus_spectra` returns), its consensus peaks -- and the medoid's precursor m/z.  `library` is a SpectrumDataset
+    (or a dict with its columns) of reference spectra of the same charge.  Exact search: the library spectra inside
+    `precursor_tol` (`mode` "ppm" or "Da") of the query's precursor, scored by the greedy cosine; `analog`: those within
+    `max_shift` m/z, scored by the greedy modified cosine (peaks matching at the same m/z or shifted by the precursor
+    difference).  A pair is a hit with a score of at least `min_cosine` and at least `min_matched_peaks` matched peaks; a
+    cluster keeps its `top_n` best hits (0: all), equal scores in library order.
+
+    Returns a dict of host arrays in (cluster, rank) order: `cluster`, `library` int32 (cluster index, library row),
+    `similarity` float32, `matched` int32, `delta_mz` float32 = float32(precursor_mz[medoid] - library precursor_mz)."""
+    global _default_pipeline
+    dataset, library = _as_dataset(dataset), _as_dataset(library)
+    if mode not in ("ppm", "Da"):
+        raise ValueError('library_search: mode must be "ppm" or "Da"')
+    pipe = pipeline or _default_pipeline
+    if pipe is None:
+        pipe = _default_pipeline = ClusterPipeline()
+    ctx = pipe.ctx
+    import torch
+    m = ctx.to_dev(medoids, torch.int64)
+    pmz = ctx.to_dev(dataset.precursor_mz, torch.float32)[m]
+    if consensus is None:
+        indptr, mz, intensity, rows = dataset.indptr, dataset.mz, dataset.intensity, m.to(torch.int32)
+    else:
+        indptr, mz, intensity = consensus
+        rows = np.arange(len(m), dtype=np.int32)
+        if len(indptr) != len(m) + 1:
+            raise ValueError(f"consensus holds {len(indptr) - 1} spectra for {len(m)} clusters")
+    l_pmz = ctx.to_dev(library.precursor_mz, torch.float32)
+    l_rows = np.arange(int(l_pmz.numel()), dtype=np.int32)
+    q, l, sim, matched = ctx.library_search(mz, intensity, indptr, rows, pmz, library.mz, library.intensity, library.indptr, l_rows,
+                                            l_pmz, fragment_tol, precursor_tol, mode == "Da", analog, max_shift, min_cosine,
+                                            min_matched_peaks, top_n)
+    cols = dict(cluster=q, library=l, similarity=sim, matched=matched, delta_mz=pmz[q.long()] - l_pmz[l.long()])
+    return {k: v.cpu().numpy() for k, v in cols.items()}
+
+
 def network_families(network, n_clusters: int, max_size: int = 100, delta: float = 0.02,
                      pipeline: Optional[ClusterPipeline] = None):
     """Molecular families of the network `representative_network` returned for `n_clusters` clusters (`fal_network_families`;

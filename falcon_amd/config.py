@@ -72,6 +72,25 @@ class Config:
         p.add_argument("--network_family_delta", type=float, default=0.02,
                        help="--network_families: a round cuts the links of an oversized family whose cosine is within this "
                             "much of the family's weakest link (default: 0.02).")
+        p.add_argument("--library", nargs="+", default=None, metavar="FILE",
+                       help="Reference spectral library MGF files (GNPS style: PEPMASS, optional CHARGE, NAME= / COMPOUND_NAME=, "
+                            "SPECTRUMID=): also write <output>.library.csv, for every cluster representative its best library "
+                            "hits by greedy cosine among the library spectra of its charge (an entry without a charge is offered "
+                            "to every charge) inside --precursor_tol.  The library is preprocessed with the run's options, "
+                            "--scaling included.  The representative is the medoid, or with --export_representatives "
+                            "--representatives consensus the consensus spectrum.")
+        p.add_argument("--library_analog", action="store_true",
+                       help="--library: analog search -- library spectra within --library_max_shift of the representative's "
+                            "precursor, scored by the greedy modified cosine (peaks matching at the same m/z or shifted by the "
+                            "precursor difference).")
+        p.add_argument("--library_max_shift", type=float, default=200.0,
+                       help="--library_analog: largest precursor m/z difference of a hit (default: 200.0).")
+        p.add_argument("--library_min_cosine", type=float, default=0.7,
+                       help="--library: smallest cosine of a hit (0 <= c <= 1, default: 0.7).")
+        p.add_argument("--library_min_matched_peaks", type=int, default=6,
+                       help="--library: smallest number of matched peaks of a hit (default: 6).")
+        p.add_argument("--library_top_n", type=int, default=1,
+                       help="--library: the most hits reported for one representative, best first (default: 1; 0 = all).")
         p.add_argument("--assign_to", nargs="+", default=None, metavar="FILE",
                        help="Representative MGF files of earlier runs (--export_representatives output, one CLUSTER= id per "
                             "entry): a new spectrum whose nearest representative inside the precursor (and RT) tolerance lies "
@@ -255,6 +274,23 @@ class Config:
             self._parser.error(f"--network_max_family_size {ns['network_max_family_size']} is negative")
         if not ns["network_family_delta"] >= 0.0:
             self._parser.error(f"--network_family_delta {ns['network_family_delta']} is negative")
+        if ns["library"] is not None and isinstance(ns["library"], str):
+            ns["library"] = [ns["library"]]
+        if not 0.0 <= ns["library_min_cosine"] <= 1.0:
+            self._parser.error(f"--library_min_cosine {ns['library_min_cosine']} is outside [0, 1]")
+        if ns["library_min_matched_peaks"] < 0:
+            self._parser.error(f"--library_min_matched_peaks {ns['library_min_matched_peaks']} is negative")
+        if ns["library_top_n"] < 0:
+            self._parser.error(f"--library_top_n {ns['library_top_n']} is negative")
+        if not ns["library_max_shift"] >= 0.0:
+            self._parser.error(f"--library_max_shift {ns['library_max_shift']} is negative")
+        if ns["library"] and ns["assign_to"]:
+            self._parser.error("--library does not combine with --assign_to (the representatives of the existing clusters are "
+                               "not in the run)")
+        if ns["library"] and ns["distributed"]:
+            self._parser.error("--library does not combine with --distributed (the library search is not sharded)")
+        if ns["library_analog"] and not ns["library"]:
+            self._parser.error("--library_analog needs --library (it is a mode of the library search)")
         if not 1 <= ns["low_dim"] <= 800:
             raise ValueError("low_dim must be an integer in [1, 800] (README.md:114-117; the widest rows the kernels hold)")
         if ns["n_neighbors_ann"] < ns["n_neighbors"]:

@@ -18,6 +18,7 @@
 #include "common.h"
 #include "exwalk.h"
 #include "ivf.h"
+#include "netgreedy.h"
 #include "netmatch.h"
 #include "util.h"
 
@@ -154,13 +155,7 @@ __global__ __launch_bounds__(kNetBlock) void net_tile_kernel(const int64_t* __re
     }
 }
 
-// One wave per listed pair (sorted positions a < b).  Peak i of a belongs to lane i mod 64 (strip i / 64).  s_j[i]: the best free
-// partner the peak last found (>= 0), kNetStale before the first look, kNetNone when no free partner is left (none comes back:
-// the used peaks only grow), kNetTaken once the peak is accepted -- s_w[i] is its weight then.  A round: every lane brings its
-// peaks' offers up to date (an offer stands until its partner is used) and keeps the first in the order; the wave takes the
-// largest weight, among equals the lowest i (its j is the lowest of that weight: the look goes through b in ascending order).
-constexpr int kNetStale = -2, kNetNone = -1, kNetTaken = -3;
-
+// One wave per listed pair (sorted positions a < b): netgreedy.h's rounds, then the edge rule in lane 0.
 template <int kCap>
 __global__ __launch_bounds__(64) void net_greedy_kernel(const int2* __restrict__ list, const unsigned long long* __restrict__ n_list,
                                                         int64_t list_cap, ExactPeaks pk, const float* __restrict__ pmzs,
@@ -168,72 +163,19 @@ __global__ __launch_bounds__(64) void net_greedy_kernel(const int2* __restrict__
     __shared__ float s_w[kCap];
     __shared__ int s_j[kCap];
     __shared__ uint32_t s_used[kCap / 32];
-    const int lane = threadIdx.x;
     const int64_t cnt = min((int64_t)*n_list, list_cap);
     for (int64_t x = blockIdx.x; x < cnt; x += gridDim.x) {                   // (wave-uniform control flow)
         const int2 ab = list[x];
         const int64_t ra = pk.order[ab.x], rb = pk.order[ab.y];
         const int64_t ga = pk.indptr[ra], gb = pk.indptr[rb];
         const int la = (int)(pk.indptr[ra + 1] - ga), lb = (int)(pk.indptr[rb + 1] - gb);
-        if (la > kCap || lb > kCap) continue;                                 // (never: the tile kernel lists by size)
-        const float* amz = pk.mz + ga;
-        const float* ait = pk.it + ga;
-        const float* bmz = pk.mz + gb;
-        const float* bit = pk.it + gb;
-        const float shift = net_shift(pmzs[ab.x], pmzs[ab.y]);
-        for (int i = lane; i < la; i += 64) s_j[i] = kNetStale;
-        for (int q = lane; q < (lb + 31) / 32; q += 64) s_used[q] = 0u;
-        wave_lds_sync();
+        float sim = 0.f;
         int matched = 0;
-        for (;;) {
-            float bw = 0.f;
-            int bi = 0x7FFFFFFF, bj = -1;
-            for (int i = lane; i < la; i += 64) {
-                int cj = s_j[i];
-                if (cj == kNetNone || cj == kNetTaken) continue;
-                float w = 0.f;
-                if (cj >= 0 && !((s_used[cj >> 5] >> (cj & 31)) & 1u)) {
-                    w = s_w[i];
-                } else {                                                      // look again: the free b peaks of both windows
-                    const float av = amz[i], ai = ait[i];
-                    int z0, z1, s0, s1;
-                    net_window(av, bmz, lb, prm.tol, &z0, &z1);
-                    net_window(av - shift, bmz, lb, prm.tol, &s0, &s1);       // (shift <= 0: this window is not below the other)
-                    cj = kNetNone;
-                    for (int q = z0; q < z1; ++q) {
-                        if ((s_used[q >> 5] >> (q & 31)) & 1u) continue;
-                        const float wq = net_weight(ai, bit[q]);
-                        if (wq > w) w = wq, cj = q;
-                    }
-                    for (int q = max(s0, z1); q < s1; ++q) {
-                        if ((s_used[q >> 5] >> (q & 31)) & 1u) continue;
-                        const float wq = net_weight(ai, bit[q]);
-                        if (wq > w) w = wq, cj = q;
-                    }
-                    s_j[i] = cj;
-                    s_w[i] = w;
-                }
-                if (cj >= 0 && w > bw) bw = w, bi = i, bj = cj;               // (ascending i: the first of equal weights stays)
-            }
-            const uint32_t top = wave_max_u32(__float_as_uint(bw));           // (weights > 0: the bits order like the values)
-            if (top == 0u) break;
-            const uint32_t win = wave_min_u32(__float_as_uint(bw) == top ? (uint32_t)bi : 0xFFFFFFFFu);
-            const int j = __shfl(bj, (int)(win & 63u), 64);
-            if (lane == (int)(win & 63u)) {
-                s_j[win] = kNetTaken;
-                s_used[j >> 5] |= 1u << (j & 31);
-            }
-            matched += 1;
-            wave_lds_sync();
-        }
-        if (lane == 0) {
-            double score = 0.0;
-            for (int i = 0; i < la; ++i)
-                if (s_j[i] == kNetTaken) net_sum_add(score, s_w[i]);
-            const float sim = net_similarity(score);
-            if (net_is_edge(sim, matched, prm.min_cosine, prm.min_matched))
-                net_put_edge(ed, atomicAdd(ed.counts + NET_N_EDGES, 1ull), node[ab.x], node[ab.y], sim, matched);
-        }
+        if (!net_greedy_pair<kCap>(pk.mz + ga, pk.it + ga, la, pk.mz + gb, pk.it + gb, lb, net_shift(pmzs[ab.x], pmzs[ab.y]), prm.tol,
+                                   s_w, s_j, s_used, &sim, &matched))
+            continue;                                                         // (never: the tile kernel lists by size)
+        if (threadIdx.x == 0 && net_is_edge(sim, matched, prm.min_cosine, prm.min_matched))
+            net_put_edge(ed, atomicAdd(ed.counts + NET_N_EDGES, 1ull), node[ab.x], node[ab.y], sim, matched);
         wave_lds_sync();                                                      // the next pair's state goes over this one's
     }
 }

@@ -945,6 +945,48 @@ class Context:
                                             ptr(size), ptr(edge_round), C.byref(nf), C.byref(nr)), "fal_network_families")
         return family, size, edge_round, int(nf.value), int(nr.value)
 
+    # ------------------------------------------------------------------ library search
+    def library_search(self, q_mz, q_intensity, q_indptr, q_rows, q_precursor_mz, l_mz, l_intensity, l_indptr, l_rows,
+                       l_precursor_mz, fragment_tol: float, precursor_tol: float, tol_is_da: bool, analog: bool = False,
+                       max_shift: float = 200.0, min_cosine: float = 0.7, min_matched: int = 6, top_n: int = 1,
+                       max_hits: Optional[int] = None):
+        """`fal_library_search`: for every query its best hits in a library by greedy (modified) cosine (DESIGN.md "Library
+        search").  Each side is a peak CSR (mz / intensity f32, indptr i64) of its own: query v is row q_rows[v] (i32[nq]) with
+        precursor m/z q_precursor_mz[v] (f32[nq]), library entry w is row l_rows[w] of the second CSR.  Host or device arrays.
+        `max_hits`: the room of the first call (default max(top_n, 4) hits a query); a result that does not fit is fetched by a
+        second call with the room the first one reported.
+        -> query i32[m], library i32[m] (indices), similarity f32[m], matched i32[m] in (query, rank) order.  Device tensors; the
+        call synchronises up to five times."""
+        torch = _torch()
+        q_rows, l_rows = self.to_dev(q_rows, torch.int32), self.to_dev(l_rows, torch.int32)
+        q_pmz, l_pmz = self.to_dev(q_precursor_mz, torch.float32), self.to_dev(l_precursor_mz, torch.float32)
+        nq, nl = int(q_rows.numel()), int(l_rows.numel())
+        if q_pmz.numel() != nq or l_pmz.numel() != nl:
+            raise ValueError(f"library_search: {q_pmz.numel()} / {l_pmz.numel()} precursors for {nq} queries / {nl} library spectra")
+        q_mz, q_intensity, q_indptr, _ = self._peaks(q_mz, q_intensity, q_indptr, np.zeros(0, np.int64))
+        l_mz, l_intensity, l_indptr, _ = self._peaks(l_mz, l_intensity, l_indptr, np.zeros(0, np.int64))
+        q_csr, l_csr = int(q_indptr.numel()) - 1, int(l_indptr.numel()) - 1
+        if q_csr < 0 or l_csr < 0:
+            raise ValueError("library_search: indptr is empty")
+        room = int(max(int(top_n), 4) * nq if max_hits is None else max_hits)
+        m = C.c_int64()
+        ptr = lambda t: self._p(t if t is not None and t.numel() else None)
+        for _ in range(2):
+            query, library = self.empty((room,), torch.int32), self.empty((room,), torch.int32)
+            sim, matched = self.empty((room,), torch.float32), self.empty((room,), torch.int32)
+            rc = self.lib.fal_library_search(self._h, ptr(q_mz), ptr(q_intensity), ptr(q_indptr), q_csr, ptr(q_rows), ptr(q_pmz), nq,
+                                             ptr(l_mz), ptr(l_intensity), ptr(l_indptr), l_csr, ptr(l_rows), ptr(l_pmz), nl,
+                                             float(fragment_tol), float(precursor_tol), int(bool(tol_is_da)), int(bool(analog)),
+                                             float(max_shift), float(min_cosine), int(min_matched), int(top_n), ptr(query),
+                                             ptr(library), ptr(sim), ptr(matched), room, C.byref(m))
+            if rc == _lib.FAL_EINVAL and m.value > room:
+                room = int(m.value)              # the hits did not fit: once more with room for them
+                continue
+            break
+        check(rc, "fal_library_search")
+        k = int(m.value)
+        return query[:k], library[:k], sim[:k], matched[:k]
+
 
 class IvfIndex:
     """Opaque `fal_ivf` handle (keeps the vectors alive: the index borrows them)."""

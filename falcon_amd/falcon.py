@@ -28,7 +28,7 @@ import numpy as np
 from . import __version__
 from .cluster import cluster, spectrum
 from .config import config
-from .ms_io import csv_io, mgf_io, ms_io, network_io, summary_io
+from .ms_io import csv_io, library_io, mgf_io, ms_io, network_io, summary_io
 
 logger = logging.getLogger("falcon")
 
@@ -69,6 +69,8 @@ def _option_lines(header: bool = False) -> List[str]:
         extra.append(f"cluster_summary = {c.cluster_summary}")
     if c.network and not header:
         extra += _network_lines() + _family_lines()
+    if c.library and not header:
+        extra += _library_lines()
     return [
         f"work_dir = {c.work_dir}", f"overwrite = {c.overwrite}",
         f"export_representatives = {c.export_representatives}",
@@ -93,6 +95,14 @@ def _network_lines() -> List[str]:
     return [f"network = {c.network}", f"network_min_cosine = {c.network_min_cosine:.3f}",
             f"network_min_matched_peaks = {c.network_min_matched_peaks}", f"network_top_k = {c.network_top_k}",
             f"network_max_shift = {c.network_max_shift:.3f}"]
+
+
+def _library_lines() -> List[str]:
+    """the option lines of `--library`: in the log and in the `#` header of <output>.library.csv alone"""
+    c = config
+    return [f"library = {' '.join(c.library)}", f"library_analog = {c.library_analog}", f"library_max_shift = {c.library_max_shift:.3f}",
+            f"library_min_cosine = {c.library_min_cosine:.3f}", f"library_min_matched_peaks = {c.library_min_matched_peaks}",
+            f"library_top_n = {c.library_top_n}"]
 
 
 def _family_lines() -> List[str]:
@@ -131,6 +141,8 @@ def _run(args) -> int:
     library = {}
     summaries = [] if config.cluster_summary else None
     networks = [] if config.network else None
+    hits = [] if config.library else None
+    reference = _load_annotation_library(pipe.ctx) if config.library else None
     if config.assign_to:
         library, current_label = _load_library(spectra_dir, pipe.ctx)
     for charge in charges:                                                                     # falcon.py:153
@@ -152,6 +164,8 @@ def _run(args) -> int:
             summaries.append(_summary_block(pipe, ds, part, charge, labels, medoids, consensus, current_label))
         if networks is not None:
             networks.append(_network_block(pipe, ds, charge, medoids, consensus, current_label))
+        if hits is not None:
+            hits.append(_library_block(pipe, ds, charge, medoids, consensus, current_label, reference, spectra_dir))
         current_label = _emit_charge(part, charge, labels, medoids, current_label, rows_all, representatives, consensus,
                                      csv_blocks=csv_blocks)
     _write_outputs(rows_all, representatives, pipe.ctx, csv_blocks=csv_blocks)
@@ -166,6 +180,9 @@ def _run(args) -> int:
     elif networks is not None:
         logger.info("Export the representative network to output file %s.network.csv", config.output_filename)
         network_io.write(config.output_filename, _header_lines() + _network_lines(), networks)
+    if hits is not None:
+        logger.info("Export the library hits to output file %s.library.csv", config.output_filename)
+        library_io.write(config.output_filename, _header_lines() + _library_lines(), hits)
     if rm_work_dir:
         shutil.rmtree(config.work_dir)
     return 0
@@ -250,6 +267,8 @@ def _setup_work_dir():
         outputs += [(".network.csv", "representative network")]
     if config.network_families:
         outputs += [(".families.csv", "molecular families")]
+    if config.library:
+        outputs += [(".library.csv", "library hits")]
     for ext, what in outputs:
         fn = f"{config.output_filename}{ext}"
         if os.path.isfile(fn):
@@ -332,6 +351,55 @@ def _network_block(pipe, ds, charge, medoids, consensus, current_label):
         logger.info("Molecular families of charge %s: %d families, %d links cut in %d rounds", charge, cols["n_families"],
                     cols["n_cut"], cols["n_rounds"])
     cols.update(charge=charge, first=current_label)
+    return cols
+
+
+def _load_annotation_library(ctx):
+    """`--library`: the entries of the reference library files, preprocessed with the run's options (scaling included: a
+    reference library holds raw intensities, unlike `--assign_to`'s exported representatives) -> dict of host columns by entry
+    that survived: the peak CSR, precursor_mz f32, charge i32 (0: none) and the annotation strings"""
+    _, min_mz, max_mz = spectrum.get_dim(config.min_mz, config.max_mz, config.fragment_tol)
+    counts = {}
+    specs = mgf_io.read_annotation_library([os.path.abspath(fn) for fn in config.library], counts)
+    logger.info("Read %d library spectra from %d file(s), skipped %d entries without a usable precursor or with a malformed peak "
+                "line", len(specs), len(config.library), counts["skipped"])
+    text = lambda k: np.array([str(s[k]) for s in specs], dtype=str)
+    cols = dict(library_id=text("identifier"), name=text("name"), library_file=np.array([os.path.basename(s["filename"]) for s in specs],
+                                                                                        dtype=str),
+                adduct=text("adduct"), smiles=text("smiles"), inchikey=text("inchikey"), ionmode=text("ionmode"))
+    pmz = np.array([s["precursor_mz"] for s in specs], np.float64)
+    charge = np.array([int(s["precursor_charge"]) for s in specs], np.int32)
+    if not specs:
+        return dict(cols, precursor_mz=np.zeros(0, np.float32), charge=charge, mz=np.zeros(0, np.float32),
+                    intensity=np.zeros(0, np.float32), indptr=np.zeros(1, np.int64))
+    mz, it, indptr = _raw_csr(specs)
+    valid, oip, omz, oit = _process(ctx, mz, it, indptr, pmz, charge, min_mz, max_mz)
+    logger.info("Skipped %d library spectra the preprocessing rejects", int((~valid).sum()))
+    rows = np.flatnonzero(valid)
+    pos, off = _take_rows(oip, rows)
+    return dict({k: v[rows] for k, v in cols.items()}, precursor_mz=pmz[rows].astype(np.float32), charge=charge[rows],
+                mz=omz[pos].astype(np.float32), intensity=oit[pos].astype(np.float32), indptr=off)
+
+
+def _library_block(pipe, ds, charge, medoids, consensus, current_label, reference, spectra_dir):
+    """`--library`, one charge: the best hits of its clusters' representatives (the medoids, or the consensus peaks the exported
+    MGF holds) among the library entries of the charge and those without one -> the charge's block of `library_io`.  The
+    charge's library is also left in the work directory (`reference_charge_<z>.npz`): what the run searched"""
+    z = 0 if charge == "None" else int(charge)
+    rows = np.flatnonzero((reference["charge"] == z) | (reference["charge"] == 0))
+    pos, off = _take_rows(reference["indptr"], rows)
+    lib = dict({k: reference[k][rows] for k in ("library_id", "name", "library_file", "adduct", "smiles", "inchikey", "ionmode",
+                                                "charge")},
+               precursor_mz=reference["precursor_mz"][rows], retention_time=np.full(len(rows), -1.0, np.float32),
+               mz=reference["mz"][pos], intensity=reference["intensity"][pos], indptr=off)
+    np.savez(os.path.join(spectra_dir, f"reference_charge_{charge}.npz"), **lib)
+    cols = cluster.library_search(ds, medoids, _dataset(lib), config.fragment_tol, config.precursor_tol[0], config.precursor_tol[1],
+                                  config.library_analog, config.library_max_shift, config.library_min_cosine,
+                                  config.library_min_matched_peaks, config.library_top_n, consensus=consensus, pipeline=pipe)
+    logger.info("Library search of charge %s: %d clusters against %d library spectra, %d hits for %d clusters", charge, len(medoids),
+                len(rows), len(cols["cluster"]), len(np.unique(cols["cluster"])))
+    cols.update({k: lib[k] for k in ("library_id", "name", "library_file", "adduct", "smiles", "inchikey")},
+                library_precursor_mz=lib["precursor_mz"], charge=charge, first=current_label)
     return cols
 
 

@@ -129,6 +129,63 @@ def read_library(filenames) -> list:
     return out
 
 
+ANNOTATION_KEYS = ("adduct", "smiles", "inchikey", "ionmode")
+
+
+def read_annotation_library(filenames, counts: Optional[dict] = None) -> list:
+    """The entries of reference spectral library MGFs (`--library`; GNPS style), in order: `get_spectra`'s dicts --
+    `precursor_charge` 0 for an entry without CHARGE= or with CHARGE=0 -- plus `name` (NAME=, else COMPOUND_NAME=, else ""),
+    `filename`, and `adduct`, `smiles`, `inchikey`, `ionmode` as strings ("" when absent).  `identifier` is SPECTRUMID=, else
+    TITLE=, else `<file name>:<entry number>` (the file's base name; entries count from 1, skipped ones included).  An entry
+    with no usable precursor (PEPMASS missing, unparsable or <= 0) or with a malformed peak line is skipped; `counts` (a dict)
+    receives `entries` and `skipped`.  A host reader: libraries are small next to the inputs."""
+    out, n_entries, n_skipped = [], 0, 0
+    for fn in filenames:
+        entry = 0
+        with open(fn, "r") as f:
+            params, mzs, its, inside, bad = {}, [], [], False, False
+            for line in f:
+                line = line.strip()
+                if not line or line[0] in "#;!/":
+                    continue
+                if line == "BEGIN IONS":
+                    params, mzs, its, inside, bad = {}, [], [], True, False
+                elif line == "END IONS":
+                    if not inside:
+                        continue
+                    inside = False
+                    entry += 1
+                    try:
+                        pmz = float(params["pepmass"].split()[0])
+                        charge = _parse_charge(params["charge"]) if params.get("charge") else 0
+                    except (ValueError, KeyError, IndexError):
+                        bad = True
+                    if bad or not pmz > 0.0 or not np.isfinite(pmz):
+                        n_skipped += 1
+                        continue
+                    spec = {"identifier": params.get("spectrumid") or params.get("title") or f"{os.path.basename(fn)}:{entry}",
+                            "precursor_mz": pmz, "precursor_charge": charge,
+                            "retention_time": -1.0, "mz": np.asarray(mzs, np.float64), "intensity": np.asarray(its, np.float32),
+                            "name": params.get("name") or params.get("compound_name") or "", "filename": fn}
+                    spec.update({k: params.get(k, "") for k in ANNOTATION_KEYS})
+                    out.append(spec)
+                elif inside:
+                    if "=" in line and not (line[0].isdigit() or line[0] == "."):
+                        k, v = line.split("=", 1)
+                        params[k.strip().lower()] = v.strip()
+                    else:
+                        tok = line.split()
+                        try:
+                            mzs.append(float(tok[0]))
+                            its.append(float(tok[1]) if len(tok) > 1 else 0.0)
+                        except ValueError:
+                            bad = True
+        n_entries += entry
+    if counts is not None:
+        counts.update(entries=n_entries, skipped=n_skipped)
+    return out
+
+
 def raw_csr(specs):
     """spectra of one peak file -> raw CSR (mz f64, intensity f32, indptr i64), peaks sorted by m/z inside every spectrum
     (stable), which is what spectrum_utils does when the reference constructs an MsmsSpectrum"""

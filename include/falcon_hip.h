@@ -94,7 +94,8 @@ int fal_ctx_enable_timing(fal_ctx* ctx, int on);
  * which = 10: 1 when the last fal_cluster_graph_tiled ran per bucket tile, 0 when it took the per-row path;
  * which = 11: the tiles of that call whose eps-edges took the edge list's second pass;
  * which = 12: the pairs the greedy kernel finished in the LAST fal_network_edges on this context;
- * which = 13: the edges the LAST fal_network_families on this context cut. */
+ * which = 13: the edges the LAST fal_network_families on this context cut;
+ * which = 14: the pairs the greedy kernels finished in the LAST fal_library_search on this context. */
 int fal_ctx_counter(fal_ctx* ctx, int which, int64_t* value);
 
 /* ---- a1  bin geometry: reference spectrum.py:172-199 `get_dim` (float32) --- [host] */
@@ -686,6 +687,38 @@ int fal_network_edges(fal_ctx* ctx, const float* mz, const float* intensity, con
 int fal_network_families(fal_ctx* ctx, const int32_t* edge_u, const int32_t* edge_v, const float* edge_sim, int64_t m, int64_t n,
                          int max_size, double delta, int32_t* node_family, int32_t* node_size, int32_t* edge_round,
                          int64_t* n_families, int64_t* n_rounds);
+
+/* ---- library search: for each of `nq` queries its best hits among `nl` library spectra, by greedy (modified) cosine (DESIGN.md
+ *          "Library search").  Query v is row q_rows[v] (i32[nq]) of the peaks CSR q_mz / q_intensity f32, q_indptr
+ *          i64[q_csr_rows + 1] (m/z ascending inside a row) with precursor m/z q_precursor_mz[v] (f32[nq]); library entry w is
+ *          row l_rows[w] (i32[nl]) of a second, separate peaks CSR l_* with precursor l_precursor_mz[w]; both sides are of one
+ *          precursor charge; nq, nl < 2^31.
+ *          A pair (query, library) with precursors pq, pl is in scope when, analog = 0 (exact mode): with diff = (float)(pq - pl),
+ *          fabs(tol_is_da ? (double)diff : (double)(diff / pl) * 1e6) <= precursor_tol (fal_assign_nearest's test without a
+ *          retention-time rule); analog = 1: fabs((double)(float)(pl - pq)) <= max_shift (fal_network_edges' test).  Only pairs
+ *          in scope are scored.  The pair's a is the side with the lower float32 precursor, with equal precursors the query;
+ *          shift = analog ? (float)(pmz[a] - pmz[b]) : 0.0f (<= 0).
+ *          Peaks i of a and j of b are a candidate when (double)fabsf(amz[i] - bmz[j]) <= fragment_tol or
+ *          (double)fabsf((amz[i] - shift) - bmz[j]) <= fragment_tol (float32 subtractions in this order; one test in exact mode)
+ *          and the float32 product w = ait[i] * bit[j] is > 0.  Candidates are taken by (w descending, i ascending, j ascending)
+ *          and accepted when neither peak was accepted before: the greedy (modified) cosine of GNPS and matchms, NOT the optimal
+ *          assignment.  score = the float64 sum of the accepted w in ascending i; sim = (float)fmax(0, fmin(score, 1)); matched
+ *          = the number accepted.  The pair is a hit when matched >= max(min_matched, 1) and sim >= (float)min_cosine.  A
+ *          query's hits are ranked by (sim descending, library index ascending); top_n > 0: a hit stays when its rank is below
+ *          top_n; top_n = 0: every hit stays.  There is no mutual rule.
+ * -> the hits (hit_query i32, hit_library i32 indices, hit_sim f32, hit_matched i32; room for max_hits each) in (query, rank)
+ *    order and *n_hits (host).  The result depends on the arguments alone.  More hits than max_hits: FAL_EINVAL with *n_hits set
+ *    (call again with room for them); nothing is written then.  A pair in scope with a side of more than FAL_NET_MAX_PEAKS
+ *    peaks fails the call with FAL_EUNSUPPORTED (the same row outside every scope fails nothing); a row outside its CSR, or of
+ *    more than 2^24 peaks: FAL_EINVAL.  nq = 0 or nl = 0 is a no-op with *n_hits = 0.  At most five stream synchronisations: the
+ *    tile count; the list and hit counts (again, up to twice, when a list or the hit buffer was too short); with top_n > 0 the
+ *    kept hits.  fal_ctx_counter 14 = the pairs the greedy kernels finished. ---------------------------------------------- [dev] */
+int fal_library_search(fal_ctx* ctx, const float* q_mz, const float* q_intensity, const int64_t* q_indptr, int64_t q_csr_rows,
+                       const int32_t* q_rows, const float* q_precursor_mz, int64_t nq, const float* l_mz, const float* l_intensity,
+                       const int64_t* l_indptr, int64_t l_csr_rows, const int32_t* l_rows, const float* l_precursor_mz, int64_t nl,
+                       double fragment_tol, double precursor_tol, int tol_is_da, int analog, double max_shift, double min_cosine,
+                       int min_matched, int top_n, int32_t* hit_query, int32_t* hit_library, float* hit_sim, int32_t* hit_matched,
+                       int64_t max_hits, int64_t* n_hits);
 
 /* ---- sort by precursor m/z (reference cluster.py:73-85 `.sort_values`): stable.
  *          order_out i64[n] (dataset row of sorted position), mz_sorted_out f32[n]. [dev] */
