@@ -153,6 +153,8 @@ _SIGNATURES = {
                            c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, P(c_int64)], c_int),
     "fal_network_families": ([c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int, c_double, c_void_p, c_void_p, c_void_p,
                               P(c_int64), P(c_int64)], c_int),
+    "fal_network_propagate": ([c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_int, c_double, c_void_p, c_void_p,
+                               c_void_p, c_void_p, P(c_int64), P(c_int64)], c_int),
     "fal_library_search": ([c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p,
                             c_int64, c_void_p, c_void_p, c_int64, c_double, c_double, c_int, c_int, c_double, c_double, c_int, c_int,
                             c_void_p, c_void_p, c_void_p, c_void_p, c_int64, P(c_int64)], c_int),

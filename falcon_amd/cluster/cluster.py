@@ -1008,6 +1008,40 @@ def network_families(network, n_clusters: int, max_size: int = 100, delta: float
     return out
 
 
+def propagate_annotations(families, hits, n_clusters: int, max_hops: int = 3, min_score: float = 0.0,
+                          pipeline: Optional[ClusterPipeline] = None):
+    """The library's names carried through the molecular families (`fal_network_propagate`; DESIGN.md "Annotation propagation").
+    `families` is the dict `network_families` returned for `n_clusters` clusters (its `a`, `b`, `similarity`: the surviving
+    links), `hits` the dict `library_search` returned for the same clusters.  A cluster with a hit is annotated by its rank-1
+    hit, the first entry of its run in `hits`.  From the annotated clusters the walk goes level by level, at most `max_hops`
+    links far: a link offers its unreached end the other end's score times the link's similarity (an annotated cluster scores
+    1), offers below `min_score` do not count, a cluster takes the greatest offer, of equal ones the lowest cluster's.
+
+    Returns host arrays over the clusters that are annotated or reached, in ascending cluster order: `cluster` int32, `hops`
+    int32 (0: annotated itself), `source` int32 (the annotated cluster the name comes from), `via` int32 (the cluster that
+    handed it on, -1 at hops 0), `score` float32 (the product of the similarities along the path), `hit` int32 (the index into
+    `hits` of the source's rank-1 entry); and `n_seeds`, `n_reached`, `n_levels`."""
+    global _default_pipeline
+    pipe = pipeline or _default_pipeline
+    if pipe is None:
+        pipe = _default_pipeline = ClusterPipeline()
+    ctx = pipe.ctx
+    n = int(n_clusters)
+    hit_cluster = np.asarray(hits["cluster"], np.int64)
+    if len(hit_cluster) and not (0 <= hit_cluster.min() and hit_cluster.max() < n):
+        raise ValueError(f"propagate_annotations: a hit of a cluster outside the {n} clusters")
+    first = np.flatnonzero(np.r_[True, hit_cluster[1:] != hit_cluster[:-1]]) if len(hit_cluster) else np.zeros(0, np.int64)
+    seed = np.full(n, -1, np.int32)
+    seed[hit_cluster[first][::-1]] = first[::-1].astype(np.int32)          # (a cluster with two runs keeps the first)
+    source, hops, parent, score, n_reached, n_levels = ctx.network_propagate(families["a"], families["b"], families["similarity"], n,
+                                                                             seed, max_hops, min_score)
+    source, hops = source.cpu().numpy(), hops.cpu().numpy()
+    rows = np.flatnonzero(hops >= 0)
+    return dict(cluster=rows.astype(np.int32), hops=hops[rows], source=source[rows], via=parent.cpu().numpy()[rows],
+                score=score.cpu().numpy()[rows], hit=seed[source[rows]], n_seeds=int((seed >= 0).sum()), n_reached=n_reached,
+                n_levels=n_levels)
+
+
 def write_representatives(filename: str, dataset: SpectrumDataset, medoids, cluster_ids, identifiers, charge: int = 0,
                           consensus=None, pipeline: Optional[ClusterPipeline] = None) -> str:
     """Write the representatives of `dataset`'s clusters to the MGF file `filename`, formatted on the device

@@ -91,6 +91,17 @@ class Config:
                        help="--library: smallest number of matched peaks of a hit (default: 6).")
         p.add_argument("--library_top_n", type=int, default=1,
                        help="--library: the most hits reported for one representative, best first (default: 1; 0 = all).")
+        p.add_argument("--library_propagate", action="store_true",
+                       help="--library with --network --network_families: also carry the library's names through the molecular "
+                            "families and write <output>.annotations.csv -- for every cluster that has a library hit or lies "
+                            "within --library_propagate_hops links of one, the nearest named cluster of its family, the links "
+                            "between them and the product of their cosines.  Pass --network_max_family_size 0 to walk whole "
+                            "components.")
+        p.add_argument("--library_propagate_hops", type=int, default=3,
+                       help="--library_propagate: the most links between a cluster and the named cluster its annotation comes "
+                            "from (1 to 64, default: 3).")
+        p.add_argument("--library_propagate_min_score", type=float, default=0.0,
+                       help="--library_propagate: smallest product of the cosines along a path (0 <= s <= 1, default: 0.0).")
         p.add_argument("--assign_to", nargs="+", default=None, metavar="FILE",
                        help="Representative MGF files of earlier runs (--export_representatives output, one CLUSTER= id per "
                             "entry): a new spectrum whose nearest representative inside the precursor (and RT) tolerance lies "
@@ -291,6 +302,14 @@ class Config:
             self._parser.error("--library does not combine with --distributed (the library search is not sharded)")
         if ns["library_analog"] and not ns["library"]:
             self._parser.error("--library_analog needs --library (it is a mode of the library search)")
+        if ns["library_propagate"] and not ns["library"]:
+            self._parser.error("--library_propagate needs --library (it carries the library's hits on)")
+        if ns["library_propagate"] and not (ns["network"] and ns["network_families"]):
+            self._parser.error("--library_propagate needs --network --network_families (it walks the families' links)")
+        if not 1 <= ns["library_propagate_hops"] <= 64:
+            self._parser.error(f"--library_propagate_hops {ns['library_propagate_hops']} is outside [1, 64]")
+        if not 0.0 <= ns["library_propagate_min_score"] <= 1.0:
+            self._parser.error(f"--library_propagate_min_score {ns['library_propagate_min_score']} is outside [0, 1]")
         if not 1 <= ns["low_dim"] <= 800:
             raise ValueError("low_dim must be an integer in [1, 800] (README.md:114-117; the widest rows the kernels hold)")
         if ns["n_neighbors_ann"] < ns["n_neighbors"]:

@@ -37,7 +37,7 @@ void set_error(const char* fmt, ...);
     } while (0)
 
 constexpr int kNumStages = 9;
-constexpr int kNumSlots = 70;   // scratch slots of a context (ivf.h names them)
+constexpr int kNumSlots = 71;   // scratch slots of a context (ivf.h names them)
 enum Stage { ST_VECTORIZE = 0, ST_BUILD = 1, ST_COARSE = 2, ST_SCAN = 3, ST_SELECT = 4,
              ST_FILTER = 5, ST_DBSCAN = 6, ST_TAIL = 7,
              ST_KERNEL = 8 };   // the launches of the cosine kernel alone (dense_kernel / scan16_kernel / list16_kernel / ivf_list4_kernel;
@@ -76,7 +76,7 @@ struct fal_ctx {
     int32_t* fb_host = nullptr;           // pinned, 16 words, zeroed at creation: [0] / [2] fallback queries of the last prefiltered
                                           // search (flat / IVF buckets), [1] ambiguous rows of the last k-means pass
     int32_t* zero_dev = nullptr;          // 16 zero words on the device (stream-ordered resets of fb_host)
-    int64_t counters[15] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+    int64_t counters[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
 
     // the tables fal_mgf_index / fal_mzml_index left in their slots (SLOT_MGF .. SLOT_MGF4, SLOT_MZML .. SLOT_MZML4) for
     // fal_mgf_parse / fal_mzml_parse: the text they describe, the counts the host read back (extra: MGF's peaks), the capacities

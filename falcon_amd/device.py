@@ -945,6 +945,31 @@ class Context:
                                             ptr(size), ptr(edge_round), C.byref(nf), C.byref(nr)), "fal_network_families")
         return family, size, edge_round, int(nf.value), int(nr.value)
 
+    def network_propagate(self, u, v, sim, n: int, seed, max_hops: int = 3, min_score: float = 0.0):
+        """`fal_network_propagate`: the annotations of the seeded nodes carried along the links (u, v i32[m], sim f32[m]; host or
+        device arrays, the surviving links of `network_families` as they come), level by level, at most `max_hops` links far
+        (DESIGN.md "Annotation propagation").  `seed` i32[n]: >= 0 marks an annotated node, -1 one that is not.  A link offers
+        its unreached end the score of the other end times its sim; offers below `min_score` do not count; the greatest wins,
+        of equal ones the lowest parent.
+        -> source, hops, parent i32[n] (-1: not reached), score f32[n] as device tensors, n_reached, n_levels.  The call
+        synchronises once."""
+        torch = _torch()
+        u, v, sim = self.to_dev(u, torch.int32), self.to_dev(v, torch.int32), self.to_dev(sim, torch.float32)
+        seed = self.to_dev(seed, torch.int32)
+        m, n = int(u.numel()), int(n)
+        if v.numel() != m or sim.numel() != m:
+            raise ValueError(f"network_propagate: the link columns do not all have {m} rows")
+        if n < 0 or seed.numel() != n:
+            raise ValueError(f"network_propagate: {seed.numel()} seeds for {n} nodes")
+        source, hops, parent = (self.empty((n,), torch.int32) for _ in range(3))
+        score = self.empty((n,), torch.float32)
+        reached, levels = C.c_int64(), C.c_int64()
+        ptr = lambda t: self._p(t if t.numel() else None)
+        check(self.lib.fal_network_propagate(self._h, ptr(u), ptr(v), ptr(sim), m, n, ptr(seed), int(max_hops), float(min_score),
+                                             ptr(source), ptr(hops), ptr(parent), ptr(score), C.byref(reached), C.byref(levels)),
+              "fal_network_propagate")
+        return source, hops, parent, score, int(reached.value), int(levels.value)
+
     # ------------------------------------------------------------------ library search
     def library_search(self, q_mz, q_intensity, q_indptr, q_rows, q_precursor_mz, l_mz, l_intensity, l_indptr, l_rows,
                        l_precursor_mz, fragment_tol: float, precursor_tol: float, tol_is_da: bool, analog: bool = False,

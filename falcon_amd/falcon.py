@@ -28,7 +28,7 @@ import numpy as np
 from . import __version__
 from .cluster import cluster, spectrum
 from .config import config
-from .ms_io import csv_io, library_io, mgf_io, ms_io, network_io, summary_io
+from .ms_io import annotation_io, csv_io, library_io, mgf_io, ms_io, network_io, summary_io
 
 logger = logging.getLogger("falcon")
 
@@ -70,7 +70,7 @@ def _option_lines(header: bool = False) -> List[str]:
     if c.network and not header:
         extra += _network_lines() + _family_lines()
     if c.library and not header:
-        extra += _library_lines()
+        extra += _library_lines() + _propagate_lines()
     return [
         f"work_dir = {c.work_dir}", f"overwrite = {c.overwrite}",
         f"export_representatives = {c.export_representatives}",
@@ -103,6 +103,16 @@ def _library_lines() -> List[str]:
     return [f"library = {' '.join(c.library)}", f"library_analog = {c.library_analog}", f"library_max_shift = {c.library_max_shift:.3f}",
             f"library_min_cosine = {c.library_min_cosine:.3f}", f"library_min_matched_peaks = {c.library_min_matched_peaks}",
             f"library_top_n = {c.library_top_n}"]
+
+
+def _propagate_lines() -> List[str]:
+    """the option lines of `--library_propagate`, none without the flag: behind `_library_lines()` in the log and at the end of
+    the `#` header of <output>.annotations.csv"""
+    c = config
+    if not c.library_propagate:
+        return []
+    return [f"library_propagate = {c.library_propagate}", f"library_propagate_hops = {c.library_propagate_hops}",
+            f"library_propagate_min_score = {c.library_propagate_min_score:.3f}"]
 
 
 def _family_lines() -> List[str]:
@@ -142,6 +152,7 @@ def _run(args) -> int:
     summaries = [] if config.cluster_summary else None
     networks = [] if config.network else None
     hits = [] if config.library else None
+    annotations = [] if config.library_propagate else None
     reference = _load_annotation_library(pipe.ctx) if config.library else None
     if config.assign_to:
         library, current_label = _load_library(spectra_dir, pipe.ctx)
@@ -166,6 +177,8 @@ def _run(args) -> int:
             networks.append(_network_block(pipe, ds, charge, medoids, consensus, current_label))
         if hits is not None:
             hits.append(_library_block(pipe, ds, charge, medoids, consensus, current_label, reference, spectra_dir))
+        if annotations is not None:          # (behind the charge's network and library blocks: it joins the two)
+            annotations.append(_propagate_block(pipe, ds, charge, medoids, networks[-1], hits[-1]))
         current_label = _emit_charge(part, charge, labels, medoids, current_label, rows_all, representatives, consensus,
                                      csv_blocks=csv_blocks)
     _write_outputs(rows_all, representatives, pipe.ctx, csv_blocks=csv_blocks)
@@ -183,6 +196,10 @@ def _run(args) -> int:
     if hits is not None:
         logger.info("Export the library hits to output file %s.library.csv", config.output_filename)
         library_io.write(config.output_filename, _header_lines() + _library_lines(), hits)
+    if annotations is not None:
+        logger.info("Export the propagated annotations to output file %s.annotations.csv", config.output_filename)
+        annotation_io.write(config.output_filename, _header_lines() + _network_lines() + _family_lines() + _library_lines() +
+                            _propagate_lines(), annotations)
     if rm_work_dir:
         shutil.rmtree(config.work_dir)
     return 0
@@ -269,6 +286,8 @@ def _setup_work_dir():
         outputs += [(".families.csv", "molecular families")]
     if config.library:
         outputs += [(".library.csv", "library hits")]
+    if config.library_propagate:
+        outputs += [(".annotations.csv", "propagated annotations")]
     for ext, what in outputs:
         fn = f"{config.output_filename}{ext}"
         if os.path.isfile(fn):
@@ -400,6 +419,23 @@ def _library_block(pipe, ds, charge, medoids, consensus, current_label, referenc
                 len(rows), len(cols["cluster"]), len(np.unique(cols["cluster"])))
     cols.update({k: lib[k] for k in ("library_id", "name", "library_file", "adduct", "smiles", "inchikey")},
                 library_precursor_mz=lib["precursor_mz"], charge=charge, first=current_label)
+    return cols
+
+
+def _propagate_block(pipe, ds, charge, medoids, network, hits):
+    """`--library_propagate`, one charge: the names of its clusters' rank-1 library hits carried along the surviving links of its
+    families (`network` and `hits` are the charge's blocks of `network_io` and `library_io`) -> the charge's block of
+    `annotation_io`"""
+    cols = cluster.propagate_annotations(network, hits, len(medoids), config.library_propagate_hops,
+                                         config.library_propagate_min_score, pipeline=pipe)
+    logger.info("Annotation propagation of charge %s: %d annotated clusters, %d more reached in %d levels", charge, cols["n_seeds"],
+                cols["n_reached"], cols["n_levels"])
+    pmz = np.asarray(ds.precursor_mz, np.float32)[np.asarray(medoids, np.int64)]
+    hit = cols["hit"]
+    cols.update({k: hits[k] for k in ("library_id", "name", "library_file", "adduct", "smiles", "inchikey")},
+                family=network["node_family"][cols["cluster"]], n_families=network["n_families"],
+                delta_mz=pmz[cols["cluster"]] - pmz[cols["source"]], library=hits["library"][hit],
+                library_cosine=hits["similarity"][hit], charge=charge, first=network["first"])
     return cols
 
 

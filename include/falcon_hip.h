@@ -95,7 +95,8 @@ int fal_ctx_enable_timing(fal_ctx* ctx, int on);
  * which = 11: the tiles of that call whose eps-edges took the edge list's second pass;
  * which = 12: the pairs the greedy kernel finished in the LAST fal_network_edges on this context;
  * which = 13: the edges the LAST fal_network_families on this context cut;
- * which = 14: the pairs the greedy kernels finished in the LAST fal_library_search on this context. */
+ * which = 14: the pairs the greedy kernels finished in the LAST fal_library_search on this context;
+ * which = 15: the nodes the LAST fal_network_propagate on this context reached (hops >= 1). */
 int fal_ctx_counter(fal_ctx* ctx, int which, int64_t* value);
 
 /* ---- a1  bin geometry: reference spectrum.py:172-199 `get_dim` (float32) --- [host] */
@@ -719,6 +720,26 @@ int fal_library_search(fal_ctx* ctx, const float* q_mz, const float* q_intensity
                        double fragment_tol, double precursor_tol, int tol_is_da, int analog, double max_shift, double min_cosine,
                        int min_matched, int top_n, int32_t* hit_query, int32_t* hit_library, float* hit_sim, int32_t* hit_matched,
                        int64_t max_hits, int64_t* n_hits);
+
+/* ---- annotation propagation: from the annotated nodes of `n` nodes along the `m` undirected links (edge_u, edge_v i32[m], edge_sim
+ *          f32[m]; the surviving links of fal_network_families are the normal input, any order and duplicates give the same
+ *          result), level by level (DESIGN.md "Annotation propagation").  node_seed i32[n]: >= 0 marks an annotated node (the
+ *          value is the caller's and is not interpreted), -1 one that is not.  Level 0: every annotated node has hops 0, source
+ *          itself, parent -1, score 1.0f.  Level d = 1 .. max_hops in this order: a link {a, b} with hops[a] == d - 1 and b not
+ *          yet reached offers b the candidate (a, c), c = score[a] * sim (one float32 product, not clamped); it counts when
+ *          c >= (float)min_score; a node with a counting candidate takes the one of the greatest c, equal c the lowest a, and
+ *          has hops d, parent a, source source[a], score c (a zero of either sign is +0).  A node reached at level d is no
+ *          parent within level d; levels win over scores.
+ * -> node_source, node_hops, node_parent i32[n], node_score f32[n] (a node not reached: -1, -1, -1, 0.0f); *n_reached = the nodes
+ *    with hops >= 1, *n_levels = the last level that reached a node (host).  The result depends on the arguments alone.  m = 0:
+ *    the annotated nodes at level 0, everything else not reached.  n = 0 (with m = 0) is a no-op.  FAL_EINVAL, with nothing
+ *    written and the context usable: an end outside [0, n), u == v, a sim that is NaN, infinite or negative, a seed below -1,
+ *    max_hops outside [1, 64], min_score NaN or outside [0, 1].  All levels are enqueued at once (a level behind one that reached
+ *    nothing returns at once); one stream synchronisation, for the error word and the counts.  fal_ctx_counter 15 = the nodes
+ *    reached. ------------------------------------------------------------------------------------------------------------ [dev] */
+int fal_network_propagate(fal_ctx* ctx, const int32_t* edge_u, const int32_t* edge_v, const float* edge_sim, int64_t m, int64_t n,
+                          const int32_t* node_seed, int max_hops, double min_score, int32_t* node_source, int32_t* node_hops,
+                          int32_t* node_parent, float* node_score, int64_t* n_reached, int64_t* n_levels);
 
 /* ---- sort by precursor m/z (reference cluster.py:73-85 `.sort_values`): stable.
  *          order_out i64[n] (dataset row of sorted position), mz_sorted_out f32[n]. [dev] */
