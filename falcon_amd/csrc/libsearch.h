@@ -33,4 +33,11 @@ __host__ __device__ __forceinline__ float lib_shift(int analog, float pmz_a, flo
     return analog ? net_shift(pmz_a, pmz_b) : 0.0f;
 }
 
+// the orientation of a (query, library) pair: a swap of the sides, and the shift in that order
+__host__ __device__ __forceinline__ NetOriented lib_orient(int analog, const NetRow& q, const NetRow& l) {
+    const bool qa = lib_query_is_a(q.pmz, l.pmz);
+    const NetRow &a = qa ? q : l, &b = qa ? l : q;
+    return NetOriented{a, b, lib_shift(analog, a.pmz, b.pmz)};
+}
+
 }  // namespace fal

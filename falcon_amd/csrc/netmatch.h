@@ -1,8 +1,8 @@
 // Network of the cluster representatives by greedy modified cosine (DESIGN.md "Representative network"): the pure core -- the
 // scope test of a pair of precursors, the two candidate tests of a pair of peaks, the window walk that counts a pair's candidates
-// (the cardinality prefilter and the conflict-free case), the order of the greedy matching, the clip of the score, the edge rule
-// and the key of the mutual top-k ranks.  Pure functions, shared by network.hip's kernels and the host build of the CPU tests
-// (-ffp-contract=off in both: every difference below is one float32 subtraction).
+// (the cardinality prefilter and the conflict-free case), the decision of a pair, the order of the greedy matching, the clip of
+// the score, the edge rule and the key of the mutual top-k ranks.  Pure functions, shared by the kernels of network.hip and
+// libsearch.hip (nettile.h) and the host build of the CPU tests (-ffp-contract=off in both: every difference is one float32 subtraction).
 #pragma once
 #include <math.h>
 #ifdef __HIPCC__
@@ -133,6 +133,27 @@ __host__ __device__ __forceinline__ float net_similarity(double score) { return 
 // a scored pair is an edge with at least min_matched (and at least one) accepted candidates and sim >= float32(min_cosine)
 __host__ __device__ __forceinline__ bool net_is_edge(float sim, int matched, double min_cosine, int min_matched) {
     return matched >= net_need(min_matched) && sim >= (float)min_cosine;
+}
+
+// ---- the decision of one pair ------------------------------------------------------------------------------------------------
+// One side of a pair: its peaks, their number, its precursor.  A pair in its orientation: a is the side with the lower precursor
+// (the network's sorted order as it stands; libsearch.h's lib_orient turns a (query, library) pair into it).
+struct NetRow { const float *mz, *it; int len; float pmz; };
+struct NetOriented { NetRow a, b; float shift; };
+__host__ __device__ __forceinline__ NetOriented net_orient(const NetRow& a, const NetRow& b) {
+    return NetOriented{a, b, net_shift(a.pmz, b.pmz)};
+}
+
+// The one copy of the sequence: the walk over a's peaks, the walk over b's only when a's leaves enough peaks with a partner, the
+// classification; sim and matched are the conflict-free pair's (NET_INLINE), 0 otherwise.
+struct NetPair { int kind; float sim; int matched; };
+__host__ __device__ __forceinline__ NetPair net_pair(const NetOriented& o, double tol, int need) {
+    const NetWalk wa = net_walk<true>(o.a.mz, o.a.it, o.a.len, o.b.mz, o.b.it, o.b.len, o.shift, tol);
+    if (wa.hit < need) return NetPair{NET_REJECT, 0.f, 0};
+    const NetWalk wb = net_walk<false>(o.b.mz, o.b.it, o.b.len, o.a.mz, o.a.it, o.a.len, o.shift, tol);
+    const int kind = net_classify(wa.hit, wa.widest, wb.hit, wb.widest, need);
+    if (kind != NET_INLINE) return NetPair{kind, 0.f, 0};
+    return NetPair{NET_INLINE, net_similarity(wa.score), wa.matched};
 }
 
 // ---- mutual top-k --------------------------------------------------------------------------------------------------------------

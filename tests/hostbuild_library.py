@@ -1,7 +1,7 @@
 """Host build of `csrc/libsearch.h` + `csrc/netmatch.h` for the CPU tests: the headers the kernels of libsearch.hip include,
 compiled with the host C++ compiler behind `extern "C"` entry points that run the whole rule -- scope, orientation, walks, greedy
-matching, sum, hit rule, top-n -- with the headers' functions.  The greedy matching is tests/hostbuild_network.py's; compiler
-discovery and flags as in tests/hostbuild.py (`-ffp-contract=off`)."""
+matching, sum, hit rule, top-n -- with the headers' functions.  The greedy matching and the scoring of an oriented pair are
+tests/hostbuild_network.py's; compiler discovery and flags as in tests/hostbuild.py (`-ffp-contract=off`)."""
 import ctypes as C
 
 import numpy as np
@@ -48,28 +48,10 @@ int64_t t_library(const float* qmz, const float* qit, const int64_t* qptr, const
             const int64_t gq = qptr[qrows[x]], gl = lptr[lrows[y]];
             const int lq = (int)(qptr[qrows[x] + 1] - gq), ll = (int)(lptr[lrows[y] + 1] - gl);
             if (lq > fal::kNetMaxPeaks || ll > fal::kNetMaxPeaks) return -5;
-            const bool qa = fal::lib_query_is_a(qp[x], lp[y]);
-            const float* amz = qa ? qmz + gq : lmz + gl;
-            const float* ait = qa ? qit + gq : lit + gl;
-            const float* bmz = qa ? lmz + gl : qmz + gq;
-            const float* bit = qa ? lit + gl : qit + gq;
-            const int la = qa ? lq : ll, lb = qa ? ll : lq;
-            const float shift = fal::lib_shift(analog, qa ? qp[x] : lp[y], qa ? lp[y] : qp[x]);
-            const fal::NetWalk wa = fal::net_walk<true>(amz, ait, la, bmz, bit, lb, shift, tol);
-            const fal::NetWalk wb = fal::net_walk<false>(bmz, bit, lb, amz, ait, la, shift, tol);
-            const int kind = fal::net_classify(wa.hit, wa.widest, wb.hit, wb.widest, need);
-            double score = wa.score;
-            int matched = wa.matched;
-            if (kind == fal::NET_REJECT) {
-                stats[1] += 1;
-                continue;
-            }
-            if (kind == fal::NET_GREEDY) {
-                stats[2] += 1;
-                greedy(amz, ait, la, bmz, bit, lb, shift, tol, &score, &matched);
-            }
-            const float sim = fal::net_similarity(score);
-            if (fal::net_is_edge(sim, matched, min_cosine, min_matched)) hits.push_back(Hit{(int32_t)x, (int32_t)y, sim, matched});
+            const fal::NetPair r = scored(fal::lib_orient(analog, fal::NetRow{qmz + gq, qit + gq, lq, qp[x]},
+                                                          fal::NetRow{lmz + gl, lit + gl, ll, lp[y]}), tol, need, stats);
+            if (r.kind != fal::NET_REJECT && fal::net_is_edge(r.sim, r.matched, min_cosine, min_matched))
+                hits.push_back(Hit{(int32_t)x, (int32_t)y, r.sim, r.matched});
         }
     // as libsearch.hip: the hits in (query, library) order, then a stable sort by the rank key
     std::sort(hits.begin(), hits.end(), [](const Hit& p, const Hit& q) { return p.q != q.q ? p.q < q.q : p.l < q.l; });

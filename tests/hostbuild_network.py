@@ -55,6 +55,19 @@ void greedy(const float* amz, const float* ait, int la, const float* bmz, const 
     *matched_out = matched;
 }
 
+// one oriented pair through the header's decision and, where it says so, the greedy matching above; stats[1]: pairs rejected by
+// cardinality, stats[2]: pairs of the greedy kernels
+fal::NetPair scored(const fal::NetOriented& o, double tol, int need, int64_t* stats) {
+    fal::NetPair r = fal::net_pair(o, tol, need);
+    if (r.kind != fal::NET_INLINE) stats[r.kind == fal::NET_REJECT ? 1 : 2] += 1;
+    if (r.kind == fal::NET_GREEDY) {
+        double score = 0.0;
+        greedy(o.a.mz, o.a.it, o.a.len, o.b.mz, o.b.it, o.b.len, o.shift, tol, &score, &r.matched);
+        r.sim = fal::net_similarity(score);
+    }
+    return r;
+}
+
 }  // namespace
 
 extern "C" {
@@ -80,22 +93,10 @@ int64_t t_network(const float* mz, const float* it, const int64_t* ptr, const in
             const int64_t ga = ptr[rows[a]], gb = ptr[rows[b]];
             const int la = (int)(ptr[rows[a] + 1] - ga), lb = (int)(ptr[rows[b] + 1] - gb);
             if (la > fal::kNetMaxPeaks || lb > fal::kNetMaxPeaks) return -5;
-            const float shift = fal::net_shift(pmz[a], pmz[b]);
-            const fal::NetWalk wa = fal::net_walk<true>(mz + ga, it + ga, la, mz + gb, it + gb, lb, shift, tol);
-            const fal::NetWalk wb = fal::net_walk<false>(mz + gb, it + gb, lb, mz + ga, it + ga, la, shift, tol);
-            const int kind = fal::net_classify(wa.hit, wa.widest, wb.hit, wb.widest, need);
-            double score = wa.score;
-            int matched = wa.matched;
-            if (kind == fal::NET_REJECT) {
-                stats[1] += 1;
-                continue;
-            }
-            if (kind == fal::NET_GREEDY) {
-                stats[2] += 1;
-                greedy(mz + ga, it + ga, la, mz + gb, it + gb, lb, shift, tol, &score, &matched);
-            }
-            const float sim = fal::net_similarity(score);
-            if (fal::net_is_edge(sim, matched, min_cosine, min_matched)) edges.push_back(Edge{std::min(a, b), std::max(a, b), sim, matched});
+            const fal::NetPair r = scored(fal::net_orient(fal::NetRow{mz + ga, it + ga, la, pmz[a]}, fal::NetRow{mz + gb, it + gb, lb, pmz[b]}),
+                                          tol, need, stats);
+            if (r.kind != fal::NET_REJECT && fal::net_is_edge(r.sim, r.matched, min_cosine, min_matched))
+                edges.push_back(Edge{std::min(a, b), std::max(a, b), r.sim, r.matched});
         }
     std::sort(edges.begin(), edges.end(), [](const Edge& p, const Edge& q) { return p.u != q.u ? p.u < q.u : p.v < q.v; });
     std::vector<char> drop(edges.size(), 0);
