@@ -28,6 +28,9 @@ FAL_EINVAL = -1
 NET_MAX_PEAKS = 4096
 # fal_csv_*: the most bytes one number takes (csrc/csvwrite.h kCsvNumMax), the rows the merge sort's first pass sorts per block
 CSV_NUM_MAX, CSV_SORT_BLOCK = 19, 1024
+# fal_records_*: the most fields of a unit, the most bytes of its literals and the field kinds (include/falcon_hip.h FAL_REC_*)
+REC_MAX_FIELDS, REC_MAX_LITERALS = 32, 4096
+REC_KINDS = {"i32": 0, "i64": 1, "f32": 2, "text": 3}
 # fal_mzml_index / fal_mzml_parse: the same for mzML text (include/falcon_hip.h)
 MZML_FLAG_STRUCT, MZML_FLAG_MARKUP, MZML_FLAG_TAGS = 1, 2, 4
 MZML_ST_OK, MZML_ST_SKIP, MZML_ST_HOST = 0, 1, 2
@@ -45,6 +48,13 @@ _lib: Optional[C.CDLL] = None
 
 c_void_p, c_int, c_int64, c_uint32, c_float, c_double = C.c_void_p, C.c_int, C.c_int64, C.c_uint32, C.c_float, C.c_double
 P = C.POINTER
+
+
+class RecField(C.Structure):
+    """include/falcon_hip.h `fal_rec_field`: one field of a record writer's unit (pointers: device memory)"""
+    _fields_ = [("column", c_void_p), ("ptr", c_void_p), ("index", c_void_p), ("rows", c_int64), ("blob_bytes", c_int64),
+                ("kind", C.c_int32), ("prefix", C.c_int32 * 2), ("suffix", C.c_int32 * 2)]
+
 
 _SIGNATURES = {
     "fal_version": ([], c_int),
@@ -137,6 +147,10 @@ _SIGNATURES = {
     "fal_csv_write": ([c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_int64,
                        c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_void_p, c_int64, c_int64, c_void_p, c_int64,
                        c_void_p], c_int),
+    "fal_records_write_sizes": ([c_void_p, c_int64, c_void_p, c_int, c_void_p, c_int64, c_int, c_int, c_int, c_int, c_void_p, c_void_p,
+                                 P(c_int64)], c_int),
+    "fal_records_write": ([c_void_p, c_int64, c_void_p, c_int, c_void_p, c_int64, c_int, c_int, c_int, c_int, c_void_p, c_int64, c_int64,
+                           c_void_p, c_int64, c_void_p], c_int),
     "fal_mzml_index": ([c_void_p, c_void_p, c_int64, P(c_int64)], c_int),
     "fal_mzml_parse": ([c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                         c_void_p, c_void_p], c_int),

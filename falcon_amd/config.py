@@ -72,6 +72,12 @@ class Config:
         p.add_argument("--network_family_delta", type=float, default=0.02,
                        help="--network_families: a round cuts the links of an oversized family whose cosine is within this "
                             "much of the family's weakest link (default: 0.02).")
+        p.add_argument("--network_graphml", action="store_true",
+                       help="--network: also write <output>.network.graphml, one GraphML file for Cytoscape, Gephi or networkx: "
+                            "a node per cluster (clusters without a link included), an edge per row of <output>.network.csv, "
+                            "and on them the attributes of the run's other files -- the representative's precursor and the "
+                            "cluster's size, with --network_families the family, with --library the rank-1 hit, with "
+                            "--library_propagate the propagated annotation.")
         p.add_argument("--library", nargs="+", default=None, metavar="FILE",
                        help="Reference spectral library MGF files (GNPS style: PEPMASS, optional CHARGE, NAME= / COMPOUND_NAME=, "
                             "SPECTRUMID=): also write <output>.library.csv, for every cluster representative its best library "
@@ -158,6 +164,9 @@ class Config:
         p.add_argument("--csv_writer", type=str, default="device", choices=["device", "host"],
                        help="Sort the rows of the cluster CSV and format their text on the GPU (device), or with the host "
                             "writer; the file is the same byte for byte.")
+        p.add_argument("--graphml_writer", type=str, default="device", choices=["device", "host"],
+                       help="--network_graphml: format the node and edge text on the GPU (device), or with the host writer; the "
+                            "file is the same byte for byte.")
         p.add_argument("--distributed", action="store_true",
                        help="Run as one rank of a multi-GPU job launched by `python -m torch.distributed.run --module "
                             "falcon_amd.falcon ...`: the precursor windows / buckets of every charge are dealt to the ranks, "
@@ -281,6 +290,10 @@ class Config:
             self._parser.error("--network does not combine with --distributed (the network is not sharded)")
         if ns["network_families"] and not ns["network"]:
             self._parser.error("--network_families needs --network (the families are the components of its links)")
+        if ns["network_graphml"] and not ns["network"]:
+            self._parser.error("--network_graphml needs --network (it is the network's links and clusters in one file)")
+        if ns["graphml_writer"] not in ("device", "host"):
+            self._parser.error(f"--graphml_writer {ns['graphml_writer']}: device or host")
         if ns["network_max_family_size"] < 0:
             self._parser.error(f"--network_max_family_size {ns['network_max_family_size']} is negative")
         if not ns["network_family_delta"] >= 0.0:

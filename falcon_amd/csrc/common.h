@@ -37,7 +37,7 @@ void set_error(const char* fmt, ...);
     } while (0)
 
 constexpr int kNumStages = 9;
-constexpr int kNumSlots = 71;   // scratch slots of a context (ivf.h names them)
+constexpr int kNumSlots = 72;   // scratch slots of a context (ivf.h names them)
 enum Stage { ST_VECTORIZE = 0, ST_BUILD = 1, ST_COARSE = 2, ST_SCAN = 3, ST_SELECT = 4,
              ST_FILTER = 5, ST_DBSCAN = 6, ST_TAIL = 7,
              ST_KERNEL = 8 };   // the launches of the cosine kernel alone (dense_kernel / scan16_kernel / list16_kernel / ivf_list4_kernel;

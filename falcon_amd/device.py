@@ -545,6 +545,69 @@ class Context:
         sizes, offsets, _ = self.csv_write_sizes(cols)            # (sizes: alive until the last chunk, as the buffers are)
         yield from self._write_chunks(cols["rows"], offsets, max_bytes, copy, lambda a, b, d, h: self.csv_write(cols, offsets, a, b, d, h))
 
+    def _records_table(self, table):
+        """a record table -- dict(n, head, tail, fields) with head / tail bytes and per field dict(kind "i32" / "i64" / "f32" /
+        "text", column, ptr (text: i64[rows + 1]), index (i32[n] or None), prefix, suffix (bytes)) -- as the entry points' arguments:
+        the columns as device tensors of the kinds' types, the literals as ranges of one blob (equal literals share their bytes)
+        and the `fal_rec_field` array.  The dict keeps every tensor alive."""
+        torch = _torch()
+        dtypes = {"i32": torch.int32, "i64": torch.int64, "f32": torch.float32}
+        n, fields = int(table["n"]), list(table["fields"])
+        blob, where = bytearray(), {}
+
+        def literal(b: bytes):
+            if b not in where:
+                where[b] = (len(blob), len(blob) + len(b))
+                blob.extend(b)
+            return where[b]
+
+        head, tail = literal(bytes(table["head"])), literal(bytes(table["tail"]))
+        recs, keep = (_lib.RecField * max(len(fields), 1))(), []
+        for rec, f in zip(recs, fields):
+            text = f["kind"] == "text"
+            col = self._text_to_dev(f["column"]) if text else self.to_dev(f["column"], dtypes[f["kind"]])
+            ptr = self.to_dev(f["ptr"], torch.int64) if text else None
+            index = None if f.get("index") is None else self.to_dev(f["index"], torch.int32)
+            rows = int(ptr.shape[0]) - 1 if text else int(col.shape[0])
+            if (text and rows < 0) or (index is None and rows < n) or (index is not None and int(index.shape[0]) != n):
+                raise ValueError(f"format_records: a field of {rows} rows{'' if index is None else ' and its index'} for {n} units")
+            keep += [col, ptr, index]
+            rec.column = col.data_ptr() if col.numel() else None
+            rec.ptr = ptr.data_ptr() if text else None
+            rec.index = index.data_ptr() if index is not None and n else None
+            rec.rows, rec.blob_bytes, rec.kind = rows, col.numel() if text else 0, _lib.REC_KINDS[f["kind"]]
+            rec.prefix[:], rec.suffix[:] = literal(bytes(f["prefix"])), literal(bytes(f["suffix"]))
+        return dict(n=n, fields=recs, n_fields=len(fields), literals=self._text_to_dev(bytes(blob)), head=head, tail=tail, keep=keep)
+
+    def _records_args(self, c):
+        lit = c["literals"]
+        return [c["n"], C.cast(c["fields"], C.c_void_p), c["n_fields"], self._p(lit) if lit.numel() else None, lit.numel(), *c["head"],
+                *c["tail"]]
+
+    def records_write_sizes(self, cols):
+        """`fal_records_write_sizes` of a `_records_table` -> (sizes i64[n], offsets i64[n + 1] on the device, total bytes).
+        Synchronises once."""
+        return self._write_sizes("fal_records_write_sizes", self._records_args(cols), cols["n"])
+
+    def records_write(self, cols, offsets, first: int, last: int, out, host_out=None):
+        """`fal_records_write`: the text of units [first, last) into the uint8 device tensor (or view) `out`; `host_out`: a pinned
+        uint8 host tensor of the same size that receives a copy.  Synchronises once.  FalconHipError (code `_lib.FAL_EINVAL`,
+        nothing written) when `out` is too small."""
+        self._write_range("fal_records_write", self._records_args(cols), offsets, first, last, out, host_out)
+
+    def format_records(self, table, max_bytes: Optional[int] = None, copy: bool = True):
+        """The text of the n units of a record table (`_records_table` states its form; DESIGN.md "Records of fields out of the
+        device" the field model) as a generator of uint8 host arrays that together are the text: per unit the head, every present
+        field as prefix, value, suffix, and the tail.  Arrays or device tensors.  Chunks are cut on unit boundaries at about
+        `max_bytes` (default `mgf_io.DEFAULT_CHUNK_BYTES`); one larger unit grows its chunk.  Every chunk is formatted into one
+        device buffer and copied through one pinned host buffer, with one stream synchronisation; `copy=False` yields views of
+        that pinned buffer, valid until the next chunk is asked for."""
+        cols = self._records_table(table)
+        if cols["n"] == 0:
+            return
+        sizes, offsets, _ = self.records_write_sizes(cols)        # (sizes: alive until the last chunk, as the buffers are)
+        yield from self._write_chunks(cols["n"], offsets, max_bytes, copy, lambda a, b, d, h: self.records_write(cols, offsets, a, b, d, h))
+
     def mzml_index(self, d_text):
         """`fal_mzml_index` of mzML text on the device (uint8 tensor) -> (spectra, tags inside spectra, `_lib.MZML_FLAG_*` bits,
         tags).  Synchronises once.  The tables stay in the context for the `mzml_parse` of the same tensor."""

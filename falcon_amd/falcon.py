@@ -28,7 +28,7 @@ import numpy as np
 from . import __version__
 from .cluster import cluster, spectrum
 from .config import config
-from .ms_io import annotation_io, csv_io, library_io, mgf_io, ms_io, network_io, summary_io
+from .ms_io import annotation_io, csv_io, graphml_io, library_io, mgf_io, ms_io, network_io, summary_io
 
 logger = logging.getLogger("falcon")
 
@@ -69,6 +69,8 @@ def _option_lines(header: bool = False) -> List[str]:
         extra.append(f"cluster_summary = {c.cluster_summary}")
     if c.network and not header:
         extra += _network_lines() + _family_lines()
+        if c.network_graphml:            # (in the log alone: no file's `#` header carries it)
+            extra.append(f"network_graphml = {c.network_graphml}")
     if c.library and not header:
         extra += _library_lines() + _propagate_lines()
     return [
@@ -134,6 +136,7 @@ def _run(args) -> int:
     logger.debug("mzml_reader = %s", config.mzml_reader)     # (the same)
     logger.debug("mgf_writer = %s", config.mgf_writer)       # (the same)
     logger.debug("csv_writer = %s", config.csv_writer)       # (the same)
+    logger.debug("graphml_writer = %s", config.graphml_writer)       # (the same)
     if config.distributed:
         return _run_distributed()
 
@@ -153,6 +156,7 @@ def _run(args) -> int:
     networks = [] if config.network else None
     hits = [] if config.library else None
     annotations = [] if config.library_propagate else None
+    graphs = [] if config.network_graphml else None
     reference = _load_annotation_library(pipe.ctx) if config.library else None
     if config.assign_to:
         library, current_label = _load_library(spectra_dir, pipe.ctx)
@@ -179,6 +183,9 @@ def _run(args) -> int:
             hits.append(_library_block(pipe, ds, charge, medoids, consensus, current_label, reference, spectra_dir))
         if annotations is not None:          # (behind the charge's network and library blocks: it joins the two)
             annotations.append(_propagate_block(pipe, ds, charge, medoids, networks[-1], hits[-1]))
+        if graphs is not None:               # (behind the charge's other blocks: its nodes and edges carry their columns)
+            graphs.append(_graphml_block(part, charge, labels, medoids, current_label, networks[-1], hits[-1] if hits else None,
+                                         annotations[-1] if annotations else None))
         current_label = _emit_charge(part, charge, labels, medoids, current_label, rows_all, representatives, consensus,
                                      csv_blocks=csv_blocks)
     _write_outputs(rows_all, representatives, pipe.ctx, csv_blocks=csv_blocks)
@@ -200,6 +207,11 @@ def _run(args) -> int:
         logger.info("Export the propagated annotations to output file %s.annotations.csv", config.output_filename)
         annotation_io.write(config.output_filename, _header_lines() + _network_lines() + _family_lines() + _library_lines() +
                             _propagate_lines(), annotations)
+    if graphs is not None:
+        logger.info("Export the network as GraphML to output file %s.network.graphml", config.output_filename)
+        graphml_io.write(config.output_filename, _header_lines() + _network_lines() + _family_lines() +
+                         (_library_lines() if config.library else []) + _propagate_lines(), graphs, pipe.ctx, config.graphml_writer,
+                         families=config.network_families, library=bool(config.library), propagate=config.library_propagate)
     if rm_work_dir:
         shutil.rmtree(config.work_dir)
     return 0
@@ -284,6 +296,8 @@ def _setup_work_dir():
         outputs += [(".network.csv", "representative network")]
     if config.network_families:
         outputs += [(".families.csv", "molecular families")]
+    if config.network_graphml:
+        outputs += [(".network.graphml", "representative network as GraphML")]
     if config.library:
         outputs += [(".library.csv", "library hits")]
     if config.library_propagate:
@@ -437,6 +451,17 @@ def _propagate_block(pipe, ds, charge, medoids, network, hits):
                 delta_mz=pmz[cols["cluster"]] - pmz[cols["source"]], library=hits["library"][hit],
                 library_cosine=hits["similarity"][hit], charge=charge, first=network["first"])
     return cols
+
+
+def _graphml_block(part, charge, labels, medoids, current_label, network, hits, annotations):
+    """`--network_graphml`, one charge: per cluster the representative's precursor m/z and retention time (float32, as the cluster
+    CSV prints them) and the member count, beside the charge's blocks of `network_io`, `library_io` and `annotation_io` (None
+    without their options) -> the charge's block of `graphml_io`"""
+    m = np.asarray(medoids, np.int64)
+    return dict(charge=charge, first=current_label, precursor_mz=np.asarray(part["precursor_mz"])[m].astype(np.float32),
+                retention_time=np.asarray(part["retention_time"])[m].astype(np.float32),
+                size=np.bincount(np.asarray(labels, np.int64), minlength=len(m)).astype(np.int32), network=network, library=hits,
+                annotations=annotations)
 
 
 def _emit_charge(part, charge, labels, medoids, current_label, rows_all, representatives, consensus=None, csv_blocks=None) -> int:

@@ -543,6 +543,47 @@ int fal_csv_write(fal_ctx* ctx, const int32_t* order, int64_t rows, const int32_
                   const float* precursor_mz, const float* retention_time, const int64_t* cluster, int64_t n, int quote_cr,
                   const int64_t* offsets, int64_t first, int64_t last, uint8_t* out, int64_t out_bytes, uint8_t* host_out);
 
+/* ---- columns -> the text of n units, each a record of fields (the device writer of <out>.network.graphml; DESIGN.md "Records of
+ *          fields out of the device" states the field model; falcon_amd/ms_io/graphml_io.py's node_units / edge_units are what it
+ *          mirrors: for the same columns the bytes are equal).
+ * A unit's text: the head literal, every present field in turn as prefix literal, value, suffix literal, then the tail literal.
+ *          Literals are [begin, end) ranges of one blob literals u8[literal_bytes] on the device, literal_bytes <=
+ *          FAL_REC_MAX_LITERALS.  fields: n_fields <= FAL_REC_MAX_FIELDS entries in host memory whose pointers are device memory.
+ * A field: kind FAL_REC_I32 / I64 / F32 with column i32 / i64 / f32 [rows], or FAL_REC_TEXT with column u8[blob_bytes] and ptr
+ *          i64[rows + 1] (row r's bytes [ptr[r], ptr[r + 1])).  index: NULL (unit u reads row u; rows >= n), or i32[n]: unit u reads
+ *          row index[u], a negative entry means the field is absent.  A field is also absent when its float32 is not finite or its
+ *          text is empty.  Integers are decimal, a float32 is str(np.float32(x)), text is XML character data: & < > become &amp;
+ *          &lt; &gt;, '\r' becomes &#13;, '\t', '\n' and every byte from 0x20 up are copied.
+ * fal_records_write_sizes -> sizes_out i64[n], offsets_out i64[n + 1] (their exclusive scan, the total last) and *total_out (host).
+ *          One stream synchronisation.
+ * fal_records_write: the text of units [first, last) into out[0, out_bytes) at offsets[k] - offsets[first].  out needs no
+ *          alignment.  FAL_EINVAL, and nothing written, when out_bytes < offsets[last] - offsets[first]; no byte outside a unit's
+ *          own range is ever stored, whatever the offsets hold.  host_out: NULL, or pinned host memory of out_bytes bytes that
+ *          receives a copy of out before the call's one stream synchronisation.  No host work per unit.
+ * FAL_EINVAL also, with nothing read outside an array: an index at or beyond its column's rows, a ptr that does not ascend inside
+ *          its blob, a text byte below 0x20 other than '\t', '\n', '\r', more than FAL_REC_MAX_FIELDS fields, a literal range outside
+ *          the literal blob.  FAL_EINTERNAL: a unit's text is not the size the sizing call gave. ----------------------- [dev] */
+#define FAL_REC_MAX_FIELDS 32
+#define FAL_REC_MAX_LITERALS 4096
+#define FAL_REC_I32 0
+#define FAL_REC_I64 1
+#define FAL_REC_F32 2
+#define FAL_REC_TEXT 3
+typedef struct fal_rec_field {
+    const void* column;
+    const int64_t* ptr;
+    const int32_t* index;
+    int64_t rows, blob_bytes;
+    int32_t kind;
+    int32_t prefix[2], suffix[2];
+} fal_rec_field;
+int fal_records_write_sizes(fal_ctx* ctx, int64_t n, const fal_rec_field* fields, int n_fields, const uint8_t* literals,
+                            int64_t literal_bytes, int head_begin, int head_end, int tail_begin, int tail_end, int64_t* sizes_out,
+                            int64_t* offsets_out, int64_t* total_out);
+int fal_records_write(fal_ctx* ctx, int64_t n, const fal_rec_field* fields, int n_fields, const uint8_t* literals, int64_t literal_bytes,
+                      int head_begin, int head_end, int tail_begin, int tail_end, const int64_t* offsets, int64_t first, int64_t last,
+                      uint8_t* out, int64_t out_bytes, uint8_t* host_out);
+
 /* ---- mzML structure -> per-spectrum columns + the tables of fal_decode_peaks (the device reader; DESIGN.md "mzML on the
  *          device" states the grammar; falcon_amd/ms_io/mzml_io.read_chunks is the reader it mirrors and the one that decides
  *          whatever it leaves open).
