@@ -10,6 +10,7 @@
 // the Hungarian solver.  A query's running minimum is the 64-bit key of assignrep.h: reduced over the wave on the DPP network,
 // kept in a register of the lane that owns the row, one global atomicMin per query and workgroup at the end; the solver kernel
 // mins into the same keys.  The minimum of a set of keys does not depend on the order they arrive in.
+// exwalk.h's: the staging, the walk, the append, the 64-bit wave minimum and the host's settle loop of the fallback list.
 #include <math.h>
 #include <algorithm>
 #include "assignrep.h"
@@ -19,8 +20,6 @@
 #include "peakmatch.h"
 
 namespace fal {
-
-constexpr int64_t kAsFallbackBudget = 1ll << 22;   // fallback pairs the list holds before the host has seen a count (32 MB)
 
 struct AsSide {
     ExactPeaks pk;              // peaks CSR + order (sorted position -> row of the CSR)
@@ -33,13 +32,6 @@ struct AsRule {
     double tol, rt_tol;
     int is_da;
 };
-
-// minimum of the wave's keys, in every lane: the high words first, then the low words of the lanes that hold that minimum
-__device__ __forceinline__ uint64_t as_wave_min(uint64_t key) {
-    const uint32_t hi = wave_min_u32((uint32_t)(key >> 32));
-    const uint32_t lo = wave_min_u32((uint32_t)(key >> 32) == hi ? (uint32_t)key : 0xFFFFFFFFu);
-    return ((uint64_t)hi << 32) | (uint64_t)lo;
-}
 
 __device__ __forceinline__ float as_lane_f32(float v, int lane) {            // (lane: wave-uniform)
     return __uint_as_float((uint32_t)__builtin_amdgcn_readlane((int)__float_as_uint(v), lane));
@@ -123,7 +115,7 @@ __global__ __launch_bounds__(256) void assign_score_kernel(AsSide q, AsSide l, A
                 else
                     fall = true;
             }
-            const uint64_t wk = as_wave_min(key);
+            const uint64_t wk = ex_wave_min_u64(key);
             if (lane == k) {
                 best = wk < best ? wk : best;
                 cnt += __popcll(vm);
@@ -213,18 +205,11 @@ extern "C" int fal_assign_nearest(fal_ctx* ctx, const float* q_mz, const float* 
         const int64_t tiles = ceil_div(nq, kExTile), chunks = ceil_div(nl, kExTile);
         // slices of a tile's library range: one, unless the tiles alone leave compute units idle
         const int64_t slices = std::min<int64_t>(std::min<int64_t>(chunks, 65535), std::max<int64_t>(1, ceil_div(4ll * ctx->num_cus, tiles)));
-        unsigned char* pin = nullptr;
-        FAL_TRY(ctx->pinned_reserve(64, (void**)&pin));
-        unsigned long long* h = reinterpret_cast<unsigned long long*>(pin);
-        int32_t* h_err = reinterpret_cast<int32_t*>(pin + 32);
-        int64_t fb_cap = std::max<int64_t>(1, std::min<int64_t>(nq * nl, kAsFallbackBudget));
         ctx->stage_reset(ST_KERNEL);
-        for (;;) {
-            int2* fb = nullptr;
-            FAL_TRY(ctx->reserve(SLOT_ASSIGN2, sizeof(int2) * (size_t)fb_cap, (void**)&fb));
+        // every round clears the keys and counts again: the keys are a minimum, the same pairs give the same result
+        return ex_settle_fallback(ctx, SLOT_ASSIGN2, nq * nl, misc, "fal_assign_nearest", [&](int2* fb, int64_t fb_cap) -> int {
             FAL_CHECK_HIP(hipMemsetAsync(keys, 0xFF, sizeof(unsigned long long) * (size_t)nq, st));
             FAL_CHECK_HIP(hipMemsetAsync(n_cand, 0, sizeof(int32_t) * (size_t)nq, st));
-            FAL_CHECK_HIP(hipMemsetAsync(d_fb, 0, sizeof(unsigned long long), st));
             {
                 StageScope ts(ctx, ST_KERNEL);
                 hipLaunchKernelGGL(assign_score_kernel, dim3((unsigned)tiles, (unsigned)slices), dim3(256), 0, st, q, l, rule, keys, n_cand,
@@ -233,21 +218,8 @@ extern "C" int fal_assign_nearest(fal_ctx* ctx, const float* q_mz, const float* 
             hipLaunchKernelGGL(assign_fallback_kernel, dim3((unsigned)std::min<int64_t>(ceil_div(fb_cap, 256), (int64_t)ctx->num_cus * 8)),
                                dim3(256), 0, st, fb, d_fb, fb_cap, q.pk, l.pk, keys);
             hipLaunchKernelGGL(assign_unpack_kernel, dim3(ugrid), dim3(256), 0, st, keys, nq, l_order, best_row, best_dist);
-            FAL_CHECK_HIP(hipGetLastError());
-            // the one wait of the call: the fallback count and the error word
-            FAL_CHECK_HIP(hipMemcpyAsync(h, d_fb, sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
-            FAL_CHECK_HIP(hipMemcpyAsync(h_err, misc, sizeof(int32_t), hipMemcpyDeviceToHost, st));
-            FAL_CHECK_HIP(hipStreamSynchronize(st));
-            FAL_REQUIRE(*h_err == 0, FAL_EUNSUPPORTED,
-                        "fal_assign_nearest: more than %d peaks of one spectrum chain inside the fragment tolerance", kMaxComp);
-            ctx->counters[9] = (int64_t)*h;
-            if ((int64_t)*h <= fb_cap) break;
-            // more fallback pairs than the list held (the count is exact: slots past the end are counted, not written):
-            // once more with room for all of them -- the keys are a minimum, the same pairs give the same result
-            fb_cap = (int64_t)*h;
-            ctx->release(SLOT_ASSIGN2);
-        }
-        return FAL_OK;
+            return FAL_OK;
+        });
     }
     FAL_CHECK_HIP(hipMemsetAsync(keys, 0xFF, sizeof(unsigned long long) * (size_t)nq, st));
     FAL_CHECK_HIP(hipMemsetAsync(n_cand, 0, sizeof(int32_t) * (size_t)nq, st));

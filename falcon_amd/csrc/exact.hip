@@ -300,8 +300,7 @@ static int read_err(fal_ctx* ctx, const int32_t* d_err, const char* what) {
     int32_t* h = reinterpret_cast<int32_t*>(pin + 32);
     FAL_CHECK_HIP(hipMemcpyAsync(h, d_err, sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
     FAL_CHECK_HIP(hipStreamSynchronize(ctx->stream));
-    FAL_REQUIRE(*h == 0, FAL_EUNSUPPORTED, "%s: more than %d peaks of one spectrum chain inside the fragment tolerance", what, kMaxComp);
-    return FAL_OK;
+    return ex_check_err(*h, what);
 }
 
 // unsorted directed entries -> CSR rows (columns in any order), all on the device; the arrays live in SLOT_EXACT4

@@ -1,6 +1,9 @@
-// The pair walk exact mode and the representative search share: the tile constants, the staging of a tile side's peak lists in
-// LDS, pair_score's window walk with scalar state only, and the wave-compacted append.  Device code; one copy of the walk.
+// What the matched-peak tile kernels share (exact mode, the representative search, the member scores, the network / library
+// pair tile): the tile constants, the staging of a tile side's peak lists in LDS, pair_score's window walk with scalar state
+// only, the wave-compacted append, the 64-bit wave minimum and, for the host, the error word's message and the settle loop of a
+// fallback list.  Included by .hip units only; one copy of each.
 #pragma once
+#include <algorithm>
 #include "common.h"
 #include "peakmatch.h"
 
@@ -94,6 +97,52 @@ __device__ __forceinline__ bool ex_stage(const ExactPeaks& pk, int32_t r0, int n
     }
     __syncthreads();
     return fits;
+}
+
+// minimum of the wave's 64-bit keys, in every lane: the high words first, then the low words of the lanes that hold that minimum
+__device__ __forceinline__ uint64_t ex_wave_min_u64(uint64_t key) {
+    const uint32_t hi = wave_min_u32((uint32_t)(key >> 32));
+    const uint32_t lo = wave_min_u32((uint32_t)(key >> 32) == hi ? (uint32_t)key : 0xFFFFFFFFu);
+    return ((uint64_t)hi << 32) | (uint64_t)lo;
+}
+
+// ---- the host side: the error word, and the fallback list of a call that settles in one wait ---------------------------------
+constexpr int64_t kExFallbackBudget = 1ll << 22;   // fallback pairs the list holds before the host has seen a count (32 MB)
+
+// the error word a solver kernel sets when a component has more than kMaxComp query peaks
+inline int ex_check_err(int32_t err, const char* what) {
+    FAL_REQUIRE(err == 0, FAL_EUNSUPPORTED, "%s: more than %d peaks of one spectrum chain inside the fragment tolerance", what, kMaxComp);
+    return FAL_OK;
+}
+
+// The fallback list (in `slot`) of a call that scores at most max_pairs pairs: enqueue(fb, fb_cap) launches the caller's kernels,
+// which count the listed pairs in misc[2..3] and set the error word misc[0] (misc: zeroed by the caller).  One wait for both;
+// counters[9] = the listed pairs.  More of them than the list held (the count is exact: slots past the end are counted, not
+// written): once more with room for all of them -- the same pairs give the same result.
+template <class Enqueue>
+inline int ex_settle_fallback(fal_ctx* ctx, int slot, int64_t max_pairs, int32_t* misc, const char* what, Enqueue enqueue) {
+    hipStream_t st = ctx->stream;
+    unsigned long long* d_fb = reinterpret_cast<unsigned long long*>(misc + 2);
+    unsigned char* pin = nullptr;
+    FAL_TRY(ctx->pinned_reserve(64, (void**)&pin));
+    unsigned long long* h = reinterpret_cast<unsigned long long*>(pin);
+    int32_t* h_err = reinterpret_cast<int32_t*>(pin + 32);
+    int64_t fb_cap = std::max<int64_t>(1, std::min<int64_t>(max_pairs, kExFallbackBudget));
+    for (;;) {
+        int2* fb = nullptr;
+        FAL_TRY(ctx->reserve(slot, sizeof(int2) * (size_t)fb_cap, (void**)&fb));
+        FAL_CHECK_HIP(hipMemsetAsync(d_fb, 0, sizeof(unsigned long long), st));
+        FAL_TRY(enqueue(fb, fb_cap));
+        FAL_CHECK_HIP(hipGetLastError());
+        FAL_CHECK_HIP(hipMemcpyAsync(h, d_fb, sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+        FAL_CHECK_HIP(hipMemcpyAsync(h_err, misc, sizeof(int32_t), hipMemcpyDeviceToHost, st));
+        FAL_CHECK_HIP(hipStreamSynchronize(st));
+        FAL_TRY(ex_check_err(*h_err, what));
+        ctx->counters[9] = (int64_t)*h;
+        if ((int64_t)*h <= fb_cap) return FAL_OK;
+        fb_cap = (int64_t)*h;
+        ctx->release(slot);
+    }
 }
 
 }  // namespace fal

@@ -7,7 +7,8 @@
 // representatives are staged in LDS once per tile (exwalk.h's scheme and budget: kExLdsPeaks peaks a side; a side that does not
 // fit is read from global memory).  Every lane then scores its member against its run's representative with the scalar window
 // walk.  A pair with a component of two or more query peaks goes to a fallback list that a second kernel finishes with the
-// Hungarian solver; every member is written by exactly one of the two kernels.
+// Hungarian solver; every member is written by exactly one of the two kernels.  exwalk.h's: the walk, the append, the 64-bit
+// wave minimum and the host's settle loop of the fallback list; ms_stage below is its ex_stage for rows the lanes bring.
 //
 // The summary is one wave per cluster over the cluster's segment of the same order: lane l walks members l, l + 64, ... -- chain
 // l of memberscore.h -- and the 64 chain sums are added in lane order, so a cluster's bits depend on its members alone.
@@ -24,7 +25,6 @@ namespace fal {
 namespace {
 
 constexpr int kMsBlock = 256;
-constexpr int64_t kMsFallbackBudget = 1ll << 22;   // fallback pairs the list holds before the host has seen a count (32 MB)
 static_assert(kMsChains == 64, "one chain of the float64 sum per lane of the summary's wave");
 
 struct MsCsr {
@@ -186,13 +186,6 @@ __global__ __launch_bounds__(kMsBlock) void ms_fallback_kernel(const int2* __res
     }
 }
 
-// minimum of the wave's keys, in every lane: the high words first, then the low words of the lanes that hold that minimum
-__device__ __forceinline__ uint64_t ms_wave_min_key(uint64_t key) {
-    const uint32_t hi = wave_min_u32((uint32_t)(key >> 32));
-    const uint32_t lo = wave_min_u32((uint32_t)(key >> 32) == hi ? (uint32_t)key : 0xFFFFFFFFu);
-    return ((uint64_t)hi << 32) | (uint64_t)lo;
-}
-
 __device__ __forceinline__ float ms_wave_fmin(float v) {
     for (int d = 32; d > 0; d >>= 1) v = fminf(v, __shfl_xor(v, d, 64));
     return v;
@@ -225,7 +218,7 @@ __global__ __launch_bounds__(kMsBlock) void ms_summary_kernel(const int64_t* __r
         }
         double total = 0.0;
         for (int l = 0; l < kMsChains; ++l) ms_total_add(total, __shfl(chain, l, 64));
-        f.key = ms_wave_min_key(f.key);
+        f.key = ex_wave_min_u64(f.key);
         f.pmz_min = ms_wave_fmin(f.pmz_min);
         f.pmz_max = ms_wave_fmax(f.pmz_max);
         f.rt_min = ms_wave_fmin(f.rt_min);
@@ -304,16 +297,9 @@ extern "C" int fal_member_scores(fal_ctx* ctx, const float* mz, const float* int
     const MsCsr m{mz, intensity, indptr, n}, rep{rep_mz, rep_intensity, rep_indptr, n_rep};
     const int64_t tiles = ceil_div(n, kExTile);
     const unsigned grid = (unsigned)std::min<int64_t>(tiles, (int64_t)ctx->num_cus * 12);
-    unsigned char* pin = nullptr;
-    FAL_TRY(ctx->pinned_reserve(64, (void**)&pin));
-    unsigned long long* h = reinterpret_cast<unsigned long long*>(pin);
-    int32_t* h_err = reinterpret_cast<int32_t*>(pin + 32);
-    int64_t fb_cap = std::max<int64_t>(1, std::min<int64_t>(n, kMsFallbackBudget));
     ctx->stage_reset(ST_KERNEL);
-    for (;;) {
-        int2* fb = nullptr;
-        FAL_TRY(ctx->reserve(SLOT_MSCORE2, sizeof(int2) * (size_t)fb_cap, (void**)&fb));
-        FAL_CHECK_HIP(hipMemsetAsync(d_fb, 0, sizeof(unsigned long long), st));
+    // every round runs both kernels again: every member is written again by one of the two, the same pairs give the same result
+    return ex_settle_fallback(ctx, SLOT_MSCORE2, n, misc, "fal_member_scores", [&](int2* fb, int64_t fb_cap) -> int {
         {
             StageScope ts(ctx, ST_KERNEL);
             hipLaunchKernelGGL(ms_score_kernel, dim3(grid), dim3(64), 0, st, m, rep, key, row, n, n_clusters, rep_row, fragment_tol,
@@ -321,21 +307,8 @@ extern "C" int fal_member_scores(fal_ctx* ctx, const float* mz, const float* int
         }
         hipLaunchKernelGGL(ms_fallback_kernel, dim3((unsigned)std::min<int64_t>(ceil_div(fb_cap, kMsBlock), (int64_t)ctx->num_cus * 8)),
                            dim3(kMsBlock), 0, st, fb, d_fb, fb_cap, m, rep, fragment_tol, similarity, matched, misc);
-        FAL_CHECK_HIP(hipGetLastError());
-        // the one wait of the call: the fallback count and the error word
-        FAL_CHECK_HIP(hipMemcpyAsync(h, d_fb, sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
-        FAL_CHECK_HIP(hipMemcpyAsync(h_err, misc, sizeof(int32_t), hipMemcpyDeviceToHost, st));
-        FAL_CHECK_HIP(hipStreamSynchronize(st));
-        FAL_REQUIRE(*h_err == 0, FAL_EUNSUPPORTED,
-                    "fal_member_scores: more than %d peaks of one spectrum chain inside the fragment tolerance", kMaxComp);
-        ctx->counters[9] = (int64_t)*h;
-        if ((int64_t)*h <= fb_cap) break;
-        // more fallback pairs than the list held (the count is exact: slots past the end are counted, not written): once more
-        // with room for all of them -- every member is written again by one of the two kernels, the same pairs give the same result
-        fb_cap = (int64_t)*h;
-        ctx->release(SLOT_MSCORE2);
-    }
-    return FAL_OK;
+        return FAL_OK;
+    });
 }
 
 extern "C" int fal_cluster_summary(fal_ctx* ctx, const int32_t* labels, int64_t n, int64_t n_clusters, const float* similarity,

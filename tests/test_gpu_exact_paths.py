@@ -23,7 +23,7 @@ from tests.test_gpu_exact import _block_matrix, _expected_csr, _gpu_clusters, _p
 
 pytestmark = pytest.mark.gpu
 
-LDS_PEAKS = 3200             # csrc/exact.hip kExLdsPeaks
+LDS_PEAKS = 3200             # csrc/exwalk.h kExLdsPeaks
 TILE = 64                    # kExTile
 EDGE_BUDGET = 2 ** 25        # kExEdgeBudget
 
