@@ -231,6 +231,14 @@ __device__ __forceinline__ uint32_t wave_max_u32(uint32_t u) {
     return (uint32_t)__builtin_amdgcn_readlane(v, 63) ^ 0x80000000u;
 }
 
+// The plain butterfly for what the DPP scans above do not take (float, double, 64-bit): levels 32, 16, 8, 4, 2, 1 over
+// __shfl_xor, every lane ends with the result.  For the float and double sums this order is part of the result.
+template <class T, class Op>
+__device__ __forceinline__ T wave_xor_reduce(T v, Op op) {
+    for (int off = 32; off >= 1; off >>= 1) v = op(v, __shfl_xor(v, off, 64));
+    return v;
+}
+
 // sum over the 16 lanes of a DPP row (a quarter wave), every lane of the row gets it: four rotations inside the row
 __device__ __forceinline__ int row16_sum(int v) {
     v += __builtin_amdgcn_update_dpp(0, v, 0x121, 0xF, 0xF, false);            // row_ror:1

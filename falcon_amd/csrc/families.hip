@@ -15,6 +15,7 @@
 #include "common.h"
 #include "ivf.h"
 #include "netfamily.h"
+#include "unionfind.h"
 #include "util.h"
 
 namespace fal {
@@ -41,49 +42,31 @@ __global__ void fam_init_kernel(int64_t n, int32_t* __restrict__ parent, int32_t
     }
 }
 
-// graph.hip's union-find: parent links only ever point to smaller nodes; path halving while the hooks run ...
-__device__ __forceinline__ int32_t fam_find(int32_t* parent, int32_t x) {
-    int32_t p = __hip_atomic_load(&parent[x], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    while (p != x) {
-        const int32_t g = __hip_atomic_load(&parent[p], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (g != p) __hip_atomic_store(&parent[x], g, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        x = p;
-        p = g;
-    }
-    return x;
-}
-
-// ... and none in the find behind the last hook (graph.hip, uf_find_final: a halving store of another thread could leave a
-// non-root where a node's root was expected).  Read-only, and in a launch of its own behind the hook kernel's: nothing writes
-// `parent` while it runs, so plain loads do (graph.hip's find shares its launch with stores and loads atomically)
-__device__ __forceinline__ int32_t fam_find_final(const int32_t* parent, int32_t x) {
-    int32_t p = parent[x];
-    while (p != x) {
-        x = p;
-        p = parent[x];
-    }
-    return x;
-}
-
+// unionfind.h's union-find: path halving while the hooks run ...  (The loop is uf_union's, left written out: called as
+// uf_union<kUfAgent>(parent, eu[e], ev[e]) the kernel compiles to the same 139 instructions and registers in another block order,
+// and a kernel whose listing moves is not kept without a measurement -- profiles/NOTES.md, "One union-find header".)
 __global__ void fam_hook_kernel(const int32_t* __restrict__ eu, const int32_t* __restrict__ ev, const int32_t* __restrict__ round,
                                 int64_t m, int32_t* __restrict__ parent) {
     for (int64_t e = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; e < m; e += (int64_t)gridDim.x * blockDim.x) {
         if (round[e] != 0) continue;
         int32_t a = eu[e], b = ev[e];
-        while (true) {
-            a = fam_find(parent, a);
-            b = fam_find(parent, b);
+        while (true) {                                                        // uf_union's loop, written out (see above)
+            a = uf_find<kUfAgent>(parent, a);
+            b = uf_find<kUfAgent>(parent, b);
             if (a == b) break;
-            if (a < b) { const int32_t t = a; a = b; b = t; }                 // a > b: the larger root goes under the smaller
-            if (atomicCAS(&parent[a], a, b) == a) break;
+            if (a < b) { const int32_t t = a; a = b; b = t; }
+            if (uf_cas(&parent[a], a, b) == a) break;
         }
     }
 }
 
+// ... and none in the find behind the last hook (unionfind.h, uf_find_final).  That find runs in a launch of its own behind the
+// hook kernel's: nothing writes `parent` while it runs, so plain loads do (the root passes of graph.hip and linkage.hip share
+// their launch with stores and load atomically -- another instruction form).
 // root[i] = the smallest node of i's component; size[root] = its nodes.  parent is read only: the roots go to their own array
 __global__ void fam_find_kernel(const int32_t* __restrict__ parent, int64_t n, int32_t* __restrict__ root, int32_t* __restrict__ size) {
     for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-        const int32_t r = fam_find_final(parent, (int32_t)i);
+        const int32_t r = uf_find_final<kUfPlainLoads>(parent, (int32_t)i);
         root[i] = r;
         atomicAdd(&size[r], 1);
     }

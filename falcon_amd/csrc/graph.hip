@@ -7,6 +7,7 @@
 #include <math.h>
 #include "common.h"
 #include "ivf.h"
+#include "unionfind.h"
 #include "util.h"
 
 namespace fal {
@@ -97,44 +98,6 @@ __global__ __launch_bounds__(256) void dbscan_core_kernel(const int32_t* __restr
     }
 }
 
-__device__ __forceinline__ int32_t uf_find(int32_t* parent, int32_t x) {
-    // path halving; parent links only ever point to smaller ids
-    int32_t p = __hip_atomic_load(&parent[x], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    while (p != x) {
-        const int32_t g = __hip_atomic_load(&parent[p], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (g != p) __hip_atomic_store(&parent[x], g, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        x = p;
-        p = g;
-    }
-    return x;
-}
-
-// The find of the FINAL pass (every row -> its root, after all unions): no path halving.  With halving, a thread that has
-// loaded parent[i] and parent[parent[i]] may store that grandparent into parent[i] AFTER the row's own thread has stored
-// the root there -- parent[i] then names an ancestor that is not the root and the row gets the label slot of a non-root
-// (found by a 3,000-row chain in tests/test_gpu_linkage.py; shallow trees make it rare, not impossible).  Read-only finds
-// race with nothing: whatever a concurrent reader sees in parent[i] (the old link or the root) is an ancestor.
-__device__ __forceinline__ int32_t uf_find_final(const int32_t* parent, int32_t x) {
-    int32_t p = __hip_atomic_load(&parent[x], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    while (p != x) {
-        x = p;
-        p = __hip_atomic_load(&parent[x], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-    return x;
-}
-
-// hook the larger root under the smaller one (so every component's root is its lowest core row)
-__device__ __forceinline__ void uf_union(int32_t* parent, int32_t a, int32_t b) {
-    while (true) {
-        a = uf_find(parent, a);
-        b = uf_find(parent, b);
-        if (a == b) return;
-        if (a < b) { const int32_t t = a; a = b; b = t; }     // a > b
-        const int32_t old = atomicCAS(&parent[a], a, b);
-        if (old == a) return;
-    }
-}
-
 // dbscan_core_kernel for front-packed rows of known length (`count` = a8's nb_count): eight threads per row look at the
 // stored neighbours only, the row's verdict is the OR over their lanes
 __global__ __launch_bounds__(256) void dbscan_core_counted_kernel(const int32_t* __restrict__ nb_idx, const float* __restrict__ nb_dist,
@@ -159,7 +122,8 @@ __global__ __launch_bounds__(256) void dbscan_core_counted_kernel(const int32_t*
     }
 }
 
-// eight threads per row, one per stored edge (slots s, s + 8, ... below the row's extent): core->core edges are united,
+// eight threads per row, one per stored edge (slots s, s + 8, ... below the row's extent): core->core edges are united
+// (unionfind.h: the larger root under the smaller, so every component's root is its lowest core row),
 // core->border edges vote for the border point's lowest-index core in-neighbour.  (One thread per SLOT read 8 n_neighbors
 // bytes of every core row: 0.39 ms per 1 M spectra; one wave per row left most lanes idle behind four dependent loads.)
 __global__ __launch_bounds__(256) void dbscan_edges_kernel(const int32_t* __restrict__ nb_idx, const float* __restrict__ nb_dist,
@@ -173,19 +137,21 @@ __global__ __launch_bounds__(256) void dbscan_edges_kernel(const int32_t* __rest
         for (int s = (int)(e % kEdgeThreads); s < ext; s += kEdgeThreads) {
             const int32_t j = nb_idx[i * k + s];
             if (!edge_ok(j, nb_dist[i * k + s], i, eps, n)) continue;
-            if (core[j]) uf_union(parent, (int32_t)i, j);
+            if (core[j]) uf_union<kUfAgent>(parent, (int32_t)i, j);
             else atomicMin(&border_src[j], (int32_t)i);
         }
     }
 }
 
+// every core row -> its component's root, its lowest core row.  The finds are read-only: this pass stores roots into parent[]
+// while other threads still walk it (why: unionfind.h)
 __global__ void dbscan_roots_kernel(const int32_t* __restrict__ core, int32_t* __restrict__ parent, int64_t n,
                                     int32_t* __restrict__ is_root) {
     for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
         int32_t r = 0;
         if (core[i]) {
-            const int32_t root = uf_find_final(parent, (int32_t)i);
-            __hip_atomic_store(&parent[i], root, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            const int32_t root = uf_find_final<kUfAgent>(parent, (int32_t)i);
+            uf_store<kUfAgent>(&parent[i], root);
             r = root == (int32_t)i;
         }
         is_root[i] = r;

@@ -49,12 +49,6 @@ __global__ __launch_bounds__(64) void kmeans_init_kernel(const float* __restrict
     for (int e = threadIdx.x; e < d / 4; e += 64) o[e] = s[e];
 }
 
-__device__ __forceinline__ double wave_xor_sum_d(double v) {
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
-    return v;
-}
-
 // ------------------------------------------------------------------------------------------
 // k-means update from the SPARSE form of the rows.  A vectorised spectrum has at most as many non-zero components as peaks
 // (~50 of 400), and adding a zero never changes a float32 sum (the accumulators start at +0.0), so summing a list's members
@@ -295,7 +289,7 @@ __global__ __launch_bounds__(64) void centroid_update_kernel(const uint16_t* __r
             part += (double)r[p].w * (double)r[p].w;
         }
     }
-    const double nr = wave_xor_sum_d(part);
+    const double nr = wave_xor_reduce(part, [](double a, double b) { return a + b; });
     const float inv = nr > 0.0 ? (float)__ddiv_rn(1.0, __dsqrt_rn(nr)) : 0.f;
     float4* o = reinterpret_cast<float4*>(C + (b.list0 + li) * d);
     uint2* o16 = C16 ? reinterpret_cast<uint2*>(C16 + (b.list0 + li) * d) : nullptr;

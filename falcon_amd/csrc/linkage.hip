@@ -5,7 +5,7 @@
 //
 // Cut at a threshold t < 1 a flat cluster can only join spectra of one connected component of the graph of edges with
 // d <= t (single: the components themselves; complete / average: a merge across two components has height 1).  So:
-//   1. lock-free union-find over the stored edges with d <= t (both directions) -> components, root = lowest row;
+//   1. lock-free union-find (unionfind.h) over the stored edges with d <= t (both directions) -> components, root = lowest row;
 //   2. single linkage: done.  complete / average: one wave per component of >= 2 rows -- dense matrix of the component
 //      (d(i, j) = the smaller of the stored directions, 1 where neither is stored), naive agglomeration with the
 //      Lance-Williams update in float64 (scipy's formulas), always merging the pair with the smallest height (ties:
@@ -24,6 +24,7 @@
 #include "ivf.h"
 #include "util.h"
 #include "peakmatch.h"
+#include "unionfind.h"
 
 namespace fal {
 
@@ -34,37 +35,6 @@ namespace fal {
 // bounded by its bucket, a bucket by batch_size, and the m x m float64 matrix (8.6 GB at 32,768 rows) is the memory the
 // reference's own condensed matrix takes twice over.
 constexpr int kLinkageWaveMax = 256;
-
-__device__ __forceinline__ int32_t lk_find(int32_t* parent, int32_t x) {
-    int32_t p = __hip_atomic_load(&parent[x], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    while (p != x) {
-        const int32_t g = __hip_atomic_load(&parent[p], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (g != p) __hip_atomic_store(&parent[x], g, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        x = p;
-        p = g;
-    }
-    return x;
-}
-
-// the final pass's find: read-only (graph.hip, uf_find_final: halving stores of other threads could overwrite a row's root)
-__device__ __forceinline__ int32_t lk_find_final(const int32_t* parent, int32_t x) {
-    int32_t p = __hip_atomic_load(&parent[x], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    while (p != x) {
-        x = p;
-        p = __hip_atomic_load(&parent[x], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-    return x;
-}
-
-__device__ __forceinline__ void lk_union(int32_t* parent, int32_t a, int32_t b) {
-    while (true) {
-        a = lk_find(parent, a);
-        b = lk_find(parent, b);
-        if (a == b) return;
-        if (a < b) { const int32_t t = a; a = b; b = t; }     // hook the larger root under the smaller
-        if (atomicCAS(&parent[a], a, b) == a) return;
-    }
-}
 
 __global__ void lk_init_kernel(int32_t* __restrict__ parent, int32_t* __restrict__ count, int32_t* __restrict__ rep, int64_t n) {
     for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
@@ -80,7 +50,7 @@ __global__ void lk_edges_kernel(const int32_t* __restrict__ nb_idx, const float*
     for (int64_t e = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; e < total; e += (int64_t)gridDim.x * blockDim.x) {
         const int64_t i = e / k;
         const int32_t j = nb_idx[e];
-        if (j >= 0 && (int64_t)j < n && (int64_t)j != i && nb_dist[e] <= t) lk_union(parent, (int32_t)i, j);
+        if (j >= 0 && (int64_t)j < n && (int64_t)j != i && nb_dist[e] <= t) uf_union<kUfAgent>(parent, (int32_t)i, j);
     }
 }
 
@@ -90,14 +60,14 @@ __global__ void lk_edges_csr_kernel(const int64_t* __restrict__ ptr, const int32
     for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
         for (int64_t e = ptr[i]; e < ptr[i + 1]; ++e) {
             const int32_t j = idx[e];
-            if (j >= 0 && (int64_t)j < n && (int64_t)j != i && dist[e] <= t) lk_union(parent, (int32_t)i, j);
+            if (j >= 0 && (int64_t)j < n && (int64_t)j != i && dist[e] <= t) uf_union<kUfAgent>(parent, (int32_t)i, j);
         }
 }
 
 __global__ void lk_roots_kernel(int32_t* __restrict__ parent, int32_t* __restrict__ count, int64_t n) {
     for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-        const int32_t root = lk_find_final(parent, (int32_t)i);
-        __hip_atomic_store(&parent[i], root, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        const int32_t root = uf_find_final<kUfAgent>(parent, (int32_t)i);
+        uf_store<kUfAgent>(&parent[i], root);
         atomicAdd(&count[root], 1);
     }
 }

@@ -187,13 +187,11 @@ __global__ __launch_bounds__(kMsBlock) void ms_fallback_kernel(const int2* __res
 }
 
 __device__ __forceinline__ float ms_wave_fmin(float v) {
-    for (int d = 32; d > 0; d >>= 1) v = fminf(v, __shfl_xor(v, d, 64));
-    return v;
+    return wave_xor_reduce(v, [](float a, float b) { return fminf(a, b); });
 }
 
 __device__ __forceinline__ float ms_wave_fmax(float v) {
-    for (int d = 32; d > 0; d >>= 1) v = fmaxf(v, __shfl_xor(v, d, 64));
-    return v;
+    return wave_xor_reduce(v, [](float a, float b) { return fmaxf(a, b); });
 }
 
 // one wave per cluster: lane l folds members l, l + 64, ... of the cluster's segment (chain l), then the chains in lane order

@@ -61,12 +61,6 @@ __device__ __forceinline__ void entry_ranges(const MgfEntries& e, int64_t k, int
     }
 }
 
-__device__ __forceinline__ int64_t wave_sum_i64(int64_t v) {
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d, 64);
-    return v;
-}
-
 // ---- sizes: one wave per entry ----------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void mgf_write_sizes_kernel(MgfEntries e, int64_t n, int64_t* __restrict__ sizes,
                                                               unsigned long long* __restrict__ meta) {
@@ -79,7 +73,7 @@ __global__ __launch_bounds__(256) void mgf_write_sizes_kernel(MgfEntries e, int6
         int64_t len = 0;
         if (lane < kMgfFields) len = mgf_field_len(lane, e.pm[k], e.charge[k], e.rt[k], e.cluster[k]);
         for (int64_t j = p0 + lane; j < p1; j += 64) len += mgf_peak_len(e.mz[j], e.intensity[j]);
-        len = wave_sum_i64(len);
+        len = wave_xor_reduce(len, [](int64_t a, int64_t b) { return a + b; });
         if (lane == 0) {
             sizes[k] = kMgfHeadLen + (t1 - t0) + len + kMgfTailLen;
             if (bad) atomicOr(&meta[META_FLAGS], (unsigned long long)TW_BAD_INPUT);

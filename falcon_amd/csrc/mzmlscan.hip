@@ -118,6 +118,7 @@ __global__ __launch_bounds__(256) void mzml_spectra_kernel(const MzTag* __restri
             if (cb < cap_spectra) spec_close[cb] = (int32_t)k;
             inside = (long long)k;
         }
+        // (common.h's wave_xor_reduce, left written out: the call reorders the kernel's prologue -- profiles/NOTES.md)
         for (int d = 32; d > 0; d >>= 1) inside += __shfl_xor(inside, d, 64);
         const bool any_bad = __ballot(bad) != 0;
         if ((threadIdx.x & 63) == 0) {

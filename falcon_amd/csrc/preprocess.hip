@@ -34,22 +34,6 @@ struct PrepParams {
     int scaling;              // 0 none, 1 root, 2 log, 3 rank
 };
 
-__device__ __forceinline__ double wave_min_f64(double v) {
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) v = fmin(v, __shfl_xor(v, off, 64));
-    return v;
-}
-__device__ __forceinline__ double wave_max_f64(double v) {
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) v = fmax(v, __shfl_xor(v, off, 64));
-    return v;
-}
-__device__ __forceinline__ float wave_max_f32(float v) {
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) v = fmaxf(v, __shfl_xor(v, off, 64));
-    return v;
-}
-
 // count, min and max m/z of the peaks flagged 1 (spectrum.py:27-52 needs len, mz[0], mz[-1])
 __device__ __forceinline__ bool still_valid(const double* __restrict__ mz, const uint8_t* __restrict__ flag, int64_t b,
                                             int64_t e, int lane, const PrepParams& p, int* count_out) {
@@ -64,8 +48,8 @@ __device__ __forceinline__ bool still_valid(const double* __restrict__ mz, const
         }
         cnt += __popcll(__ballot(k));
     }
-    lo = wave_min_f64(lo);
-    hi = wave_max_f64(hi);
+    lo = wave_xor_reduce(lo, [](double a, double b) { return fmin(a, b); });
+    hi = wave_xor_reduce(hi, [](double a, double b) { return fmax(a, b); });
     *count_out = cnt;
     return cnt >= max(p.min_peaks, 1) && (hi - lo) >= p.min_mz_range;
 }
@@ -113,7 +97,7 @@ __global__ __launch_bounds__(256) void prep_flags_kernel(const double* __restric
                 const int64_t j = j0 + lane;
                 if (j < e && flag[j]) mx = fmaxf(mx, intensity[j]);
             }
-            mx = wave_max_f32(mx);
+            mx = wave_xor_reduce(mx, [](float a, float b) { return fmaxf(a, b); });
             const float thr = p.min_intensity * mx;
             int kept = 0;
             for (int64_t j0 = b; j0 < e; j0 += 64) {
@@ -223,6 +207,8 @@ __global__ __launch_bounds__(256) void prep_emit_kernel(const double* __restrict
                 acc = acc + x * x;
             }
         }
+        // (common.h's wave_xor_reduce, left written out: called from here it swaps two instructions of prep_emit_kernel's
+        //  listing, and a listing that moves is not kept without a measurement -- profiles/NOTES.md)
 #pragma unroll
         for (int off = 32; off >= 1; off >>= 1) acc += __shfl_xor(acc, off, 64);
         const float nrm = (float)sqrt(acc);

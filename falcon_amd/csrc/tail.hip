@@ -15,6 +15,7 @@
 #include "common.h"
 #include "ivf.h"
 #include "tiles.h"
+#include "unionfind.h"
 #include "util.h"
 
 namespace fal {
@@ -511,36 +512,6 @@ __device__ __forceinline__ int block_excl_scan(int v, int* s_w, int* total) {
     return off + inc - v;
 }
 
-// graph.hip's union-find on a tile's parent[] in LDS (tile-local rows): links only ever point to smaller rows
-__device__ __forceinline__ int32_t tile_find(int32_t* parent, int32_t x) {
-    int32_t p = __hip_atomic_load(&parent[x], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-    while (p != x) {
-        const int32_t g = __hip_atomic_load(&parent[p], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-        if (g != p) __hip_atomic_store(&parent[x], g, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-        x = p;
-        p = g;
-    }
-    return x;
-}
-// read-only: the finds after the last union (why: graph.hip uf_find_final)
-__device__ __forceinline__ int32_t tile_find_final(const int32_t* parent, int32_t x) {
-    int32_t p = __hip_atomic_load(&parent[x], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-    while (p != x) {
-        x = p;
-        p = __hip_atomic_load(&parent[x], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-    }
-    return x;
-}
-__device__ __forceinline__ void tile_union(int32_t* parent, int32_t a, int32_t b) {
-    while (true) {                             // (the one loop bounded by other waves' progress: every retry follows a link to a smaller row)
-        a = tile_find(parent, a);
-        b = tile_find(parent, b);
-        if (a == b) return;
-        if (a < b) { const int32_t t = a; a = b; b = t; }
-        if (atomicCAS(&parent[a], a, b) == a) return;
-    }
-}
-
 // a9 of one tile.  -> labels[row] = the cluster's rank among the TILE's clusters (by lowest core row) or -1;
 // cnt[0][t] = clusters, cnt[1][t] = labelled rows, cnt[2][t] = 1 when a stored id lies outside the tile, cnt[3][t] = 1 when
 // the tile's eps-edges did not fit its list and the core rows were read a second time.
@@ -622,12 +593,12 @@ __global__ __launch_bounds__(kTileThreads) void tile_dbscan_kernel(const int32_t
     }
     __syncthreads();
     // the eps-edges (their sources are core by definition): core -> core united, core -> border votes for the border's lowest
-    // core in-neighbour
+    // core in-neighbour.  unionfind.h's union-find on the tile's parent[] in LDS (tile-local rows, workgroup scope)
     const int ne = s_ne;
     if (ne <= cap) {
         for (int e = tid; e < ne; e += kTileThreads) {
             const int li = (int)(edges[e] >> 16), lj = (int)(edges[e] & 0xFFFFu);
-            if (__hip_atomic_load(&vote[lj], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) == kCore) tile_union(parent, li, lj);
+            if (__hip_atomic_load(&vote[lj], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) == kCore) uf_union<kUfWorkgroup>(parent, li, lj);
             else atomicMin(&vote[lj], li);
         }
     } else {
@@ -643,15 +614,15 @@ __global__ __launch_bounds__(kTileThreads) void tile_dbscan_kernel(const int32_t
                 if (j < 0 || (int64_t)j >= n) continue;
                 const int lj = j - r0;
                 if (lj < 0 || lj >= m || lj == li || !(d <= eps)) continue;
-                if (__hip_atomic_load(&vote[lj], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) == kCore) tile_union(parent, li, lj);
+                if (__hip_atomic_load(&vote[lj], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) == kCore) uf_union<kUfWorkgroup>(parent, li, lj);
                 else atomicMin(&vote[lj], li);
             }
         }
     }
     __syncthreads();
-    for (int li = tid; li < m; li += kTileThreads)
+    for (int li = tid; li < m; li += kTileThreads)                  // read-only finds behind the last union (why: unionfind.h)
         if (vote[li] == kCore)
-            __hip_atomic_store(&parent[li], tile_find_final(parent, li), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+            uf_store<kUfWorkgroup>(&parent[li], uf_find_final<kUfWorkgroup>(parent, li));
     __syncthreads();
     // rank of every root among the tile's roots
     int n_roots = 0;

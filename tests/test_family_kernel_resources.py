@@ -49,7 +49,7 @@ def test_integer_atomics_only_no_lds_dma_and_no_inline_assembly(asm):
     assert "global_load_lds" not in asm
     for name, body in bodies.items():
         assert not any(s.startswith("buffer_load") and " lds" in s for s in body), name
-    src = open(os.path.join(L.CSRC, "families.hip")).read() + open(os.path.join(L.CSRC, "netfamily.h")).read()
+    src = "".join(open(os.path.join(L.CSRC, f)).read() for f in ("families.hip", "netfamily.h", "unionfind.h"))
     assert "global_load_lds" not in src and "lds_dma16(" not in src
     assert not re.search(r"\b(asm|__asm__?)\b", src), "no LDS-DMA helper, no inline assembly"
     assert not re.search(r"atomic\w*\s*\(\s*\(?\s*(float|double)", src)
