@@ -6,16 +6,13 @@
 // rocprim's stable merge sort of the row indices under (file_rank, csv_natural_cmp of the ids, index).  The comparator reads the
 // id blob through id_ptr, which the check pass has bounded; an index outside [0, n) compares by itself alone and reads nothing.
 //
-// fal_csv_write_sizes (one synchronisation, at its end): a lane per row adds up its text, then the library's scan turns the sizes
-// into offsets.
+// fal_csv_write_sizes (one synchronisation, at its end): a lane per row adds up its text (textwrite.h's sizes_by_lane), then the
+// library's scan turns the sizes into offsets.
 //
-// fal_csv_write (one synchronisation, at its end): a lane per row, a wave per tile of 64 consecutive rows.  A round measures the
-// rows again (the digits are made once per round and kept for the text), places them in the wave's LDS tile at a wave prefix sum
-// of their lengths -- as many leading rows as the tile takes -- and the lanes format their rows there.  The tile is textwrite.h's
-// Tile around the round's first byte, flushed whole at the round's end.  A row that no tile takes (longer than kCsvTile - 15
-// bytes) is written by its lane alone, straight into its own range.  Every row's length is checked against
-// offsets[k + 1] - offsets[k] and every round's range against [0, offsets[last] - offsets[first]] <= out_bytes before anything of
-// it is stored.
+// fal_csv_write (one synchronisation, at its end): a lane per row, a wave per tile of 64 consecutive rows -- textwrite.h's
+// write_units_by_lane, which has the rounds, the tile and every bound on a store.  What this unit gives it is CsvUnits: a lane
+// keeps its row measured (the digits are made once per round and kept for the text), and a row that no tile takes (longer than
+// kCsvTile - 15 bytes) is written by its lane alone, straight into its own range.
 #include <algorithm>
 #include <rocprim/device/device_merge_sort.hpp>
 #include "common.h"
@@ -111,78 +108,25 @@ struct CsvRowLess {
     }
 };
 
-// ---- sizes: a lane per row ----------------------------------------------------------------------------------------------------------
+// ---- the rows as textwrite.h's lane-per-unit writers take them ----------------------------------------------------------------------------
+struct CsvUnits {
+    typedef CsvRow Unit;                                                         // the row measured: its digits are made once and kept for the text
+    static constexpr bool kLongByWave = false;                                   // a row that no tile takes: lane 0 alone, straight into its range
+    const CsvColumns& c;
+    __device__ CsvRow load(int64_t k, bool* bad) const { return load_row(c, k, bad); }
+    __device__ int64_t len(const CsvRow& row) const { return csv_row_len(row); }
+    __device__ int64_t write(uint8_t* dst, const CsvRow& row, int64_t) const { return csv_write_row(dst, row); }
+};
+
 __global__ __launch_bounds__(256) void csv_write_sizes_kernel(CsvColumns c, int64_t rows, int64_t* __restrict__ sizes,
                                                               unsigned long long* __restrict__ meta) {
-    const int64_t step = (int64_t)gridDim.x * blockDim.x;
-    bool any_bad = false;
-    for (int64_t k = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; k < rows; k += step) {
-        bool bad;
-        const CsvRow r = load_row(c, k, &bad);
-        sizes[k] = bad ? 0 : csv_row_len(r);
-        any_bad |= bad;
-    }
-    if (any_bad) atomicOr(&meta[META_FLAGS], (unsigned long long)TW_BAD_INPUT);
+    sizes_by_lane(CsvUnits{c}, rows, sizes, meta);
 }
 
-// ---- write: a lane per row, a wave per tile of 64 rows -----------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void csv_write_kernel(CsvColumns c, const int64_t* __restrict__ offsets, int64_t first, int64_t last,
                                                         uint8_t* __restrict__ out, int64_t out_bytes, unsigned long long* __restrict__ meta) {
     __shared__ __attribute__((aligned(16))) uint8_t tiles[4][kCsvTile];
-    const int lane = threadIdx.x & 63;
-    uint8_t* tile = tiles[threadIdx.x >> 6];
-    const int64_t base = offsets[first], need = offsets[last] - base;
-    if (need < 0 || need > out_bytes) {                                          // uniform over the grid: nothing is written
-        if (blockIdx.x == 0 && threadIdx.x == 0) atomicOr(&meta[META_FLAGS], (unsigned long long)TW_TOO_SMALL);
-        return;
-    }
-    const int64_t waves = (int64_t)gridDim.x * (blockDim.x >> 6), n_tiles = (last - first + 63) / 64;
-    for (int64_t t = blockIdx.x * (int64_t)(blockDim.x >> 6) + (threadIdx.x >> 6); t < n_tiles; t += waves) {
-        const int64_t k1 = std::min<int64_t>(first + 64 * (t + 1), last);
-        int64_t r = first + 64 * t;
-        while (r < k1) {                                                         // (r, k1: the same in every lane)
-            const int64_t k = r + lane;
-            const bool on = k < k1;
-            bool bad = false;
-            CsvRow row = {};
-            int64_t len = 0;
-            if (on) {
-                row = load_row(c, k, &bad);
-                len = csv_row_len(row);
-                bad |= len != offsets[k + 1] - offsets[k];
-            }
-            const int64_t g0 = offsets[r] - base;
-            if (__ballot(bad) != 0ull || g0 < 0 || g0 > need) {                 // columns or offsets that are not the sizing pass's
-                if (lane == 0) atomicOr(&meta[META_FLAGS], (unsigned long long)TW_BAD_INPUT);
-                break;
-            }
-            const int mis = (int)(reinterpret_cast<uintptr_t>(out + g0) & 15);
-            const int cap = kCsvTile - mis;
-            const int clen = (int)std::min<int64_t>(len, kCsvTile + 1);         // (64 of them stay far below 2^31)
-            const int incl = wave_prefix_sum(clen);
-            const int cnt = __popcll(__ballot(on && incl <= cap));              // the leading rows the tile takes (incl ascends)
-            if (cnt == 0) {                                                      // row r alone is longer than a tile
-                const int64_t len0 = __shfl((long long)len, 0, 64);
-                if (g0 + len0 > need) {
-                    if (lane == 0) atomicOr(&meta[META_FLAGS], (unsigned long long)TW_BAD_INPUT);
-                    break;
-                }
-                if (lane == 0 && csv_write_row(out + g0, row) != len0) atomicOr(&meta[META_FLAGS], (unsigned long long)TW_OVERFLOW);
-                r += 1;
-                continue;
-            }
-            const int total = __shfl(incl, cnt - 1, 64);
-            if (g0 + total > need) {
-                if (lane == 0) atomicOr(&meta[META_FLAGS], (unsigned long long)TW_BAD_INPUT);
-                break;
-            }
-            if (lane < cnt && csv_write_row(tile + mis + incl - clen, row) != len) atomicOr(&meta[META_FLAGS], (unsigned long long)TW_OVERFLOW);
-            Tile text{tile, out + g0 - mis, out + g0 + total, mis, mis + total, false};       // [mis, mis + total): this round's text
-            tile_flush(text, true, lane);
-            wave_lds_sync();                                                     // (the next round writes the tile again)
-            r += cnt;
-        }
-    }
+    write_units_by_lane<kCsvTile>(CsvUnits{c}, tiles[threadIdx.x >> 6], offsets, first, last, out, out_bytes, meta);
 }
 
 FAL_WARM_KERNEL(csv_write_kernel);

@@ -5,11 +5,11 @@
 // fal_mgf_write_sizes (one synchronisation, at its end): one wave per entry adds up its text -- the lanes take the peak lines 64
 // at a time, lanes 0-3 the four fields behind the title -- then the library's scan (device_scan_i64) turns the sizes into offsets.
 //
-// fal_mgf_write (one synchronisation, at its end): one wave per entry.  The wave owns a kWriteTile-byte LDS tile (textwrite.h's
-// Tile).  A round appends up to 64 pieces (a peak line per lane; the head; a stretch of the title; the four fields; the tail) at
-// offsets from a wave prefix sum of their lengths -- the digits are computed again rather than kept from the sizing pass -- and
-// then flushes the tile's complete 16-byte units; what is left (under 16 bytes) moves to the front of the tile.  Every store is
-// bounded by the entry's own range [offset[k], offset[k + 1]) - offset[first], checked against out_bytes before anything is written.
+// fal_mgf_write (one synchronisation, at its end): one wave per entry.  The wave owns a kWriteTile-byte LDS tile and appends the
+// entry to it with textwrite.h's pieces: the head from lane 0; the title copied lane-strided; the four fields and then the peak
+// lines, 64 at a time, a lane each at a wave prefix sum of their lengths (the digits are computed again rather than kept from
+// the sizing pass); the tail.  Every store is bounded by the entry's own range [offset[k], offset[k + 1]) - offset[first],
+// checked against out_bytes before anything is written.
 #include <algorithm>
 #include "common.h"
 #include "mgfwrite.h"
@@ -18,9 +18,9 @@
 namespace fal {
 namespace {
 
-constexpr int kWriteTile = 3136;                 // >= 31 bytes carried over + 64 peak lines of kMgfPeakMax bytes; a multiple of 16
-constexpr int kTitleChunk = 2048;                // title bytes appended per round
-static_assert(31 + 64 * kMgfPeakMax <= kWriteTile && 31 + kTitleChunk <= kWriteTile && 31 + kMgfHeadLen <= kWriteTile &&
+constexpr int kWriteTile = 3136;                 // >= the bytes carried over + 64 peak lines of kMgfPeakMax bytes; a multiple of 16
+constexpr int kTitleChunk = 2048;                // title bytes appended per piece
+static_assert(kTileCarry + 64 * kMgfPeakMax <= kWriteTile && kTileCarry + kTitleChunk <= kWriteTile && kTileCarry + kMgfHeadLen <= kWriteTile &&
                   kWriteTile % 16 == 0, "the tile takes one round's text behind what the last flush left");
 
 struct MgfEntries {
@@ -101,50 +101,22 @@ __global__ __launch_bounds__(256) void mgf_write_kernel(MgfEntries e, const int6
         int64_t p0, p1, t0, t1;
         bool bad;
         entry_ranges(e, k, &p0, &p1, &t0, &t1, &bad);
-        Tile t;
-        t.tile = tiles[threadIdx.x >> 6];
-        const int mis = (int)(reinterpret_cast<uintptr_t>(out + g0) & 15);
-        t.gbase = out + g0 - mis;
-        t.end = out + g1;
-        t.lo = t.hi = mis;
-        t.overflow = false;
-        // BEGIN IONS / TITLE=
-        if (lane == 0) mgf_write_head(t.tile + t.hi);
-        t.hi += kMgfHeadLen;
-        for (int64_t c = t0; c < t1; c += kTitleChunk) {
-            const int m = (int)std::min<int64_t>(kTitleChunk, t1 - c);
-            for (int i = lane; i < m; i += 64) t.tile[t.hi + i] = e.title[c + i];
-            t.hi += m;
-            tile_flush(t, false, lane);
-        }
-        // the four fields, a lane each
-        {
-            const float pm = e.pm[k], rt = e.rt[k];
-            const int32_t ch = e.charge[k];
-            const int64_t cl = e.cluster[k];
-            const int len = lane < kMgfFields ? mgf_field_len(lane, pm, ch, rt, cl) : 0;
-            const int incl = wave_prefix_sum(len);
-            if (lane < kMgfFields) mgf_write_field(t.tile + t.hi + incl - len, lane, pm, ch, rt, cl);
-            t.hi += __shfl(incl, 63, 64);
-            tile_flush(t, false, lane);
-        }
-        // the peak lines, 64 at a time
-        for (int64_t g = p0; g < p1; g += 64) {
+        Tile t = tile_open(tiles[threadIdx.x >> 6], out + g0, out + g1);
+        tile_append_by_lane0(t, kMgfHeadLen, lane, [](uint8_t* dst) { mgf_write_head(dst); });      // BEGIN IONS / TITLE=
+        tile_append_bytes<kTitleChunk>(t, e.title + t0, t1 - t0, lane);
+        const float pm = e.pm[k], rt = e.rt[k];                                  // the four fields, a lane each
+        const int32_t ch = e.charge[k];
+        const int64_t cl = e.cluster[k];
+        tile_append_by_lanes(t, lane < kMgfFields ? mgf_field_len(lane, pm, ch, rt, cl) : 0, lane,
+                             [&](uint8_t* dst) { mgf_write_field(dst, lane, pm, ch, rt, cl); });
+        for (int64_t g = p0; g < p1; g += 64) {                                  // the peak lines, 64 at a time
             const int64_t j = g + lane;
             const bool on = j < p1;
             const float m = on ? e.mz[j] : 0.f, v = on ? e.intensity[j] : 0.f;
-            const int len = on ? mgf_peak_len(m, v) : 0;
-            const int incl = wave_prefix_sum(len);
-            if (on) mgf_write_peak(t.tile + t.hi + incl - len, m, v);
-            t.hi += __shfl(incl, 63, 64);
-            tile_flush(t, false, lane);
+            tile_append_by_lanes(t, on ? mgf_peak_len(m, v) : 0, lane, [&](uint8_t* dst) { mgf_write_peak(dst, m, v); });
         }
-        if (lane == 0) mgf_write_tail(t.tile + t.hi);
-        t.hi += kMgfTailLen;
-        tile_flush(t, true, lane);
-        const bool shortfall = t.gbase + t.hi != t.end;                          // (less text than the sizes said)
-        if (lane == 0 && (t.overflow || shortfall)) atomicOr(&meta[META_FLAGS], (unsigned long long)TW_OVERFLOW);
-        wave_lds_sync();
+        tile_append_by_lane0(t, kMgfTailLen, lane, [](uint8_t* dst) { mgf_write_tail(dst); });      // END IONS
+        tile_close(t, lane, meta);
     }
 }
 

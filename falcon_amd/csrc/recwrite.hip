@@ -3,17 +3,14 @@
 // fal_rec_field); the kinds, the absence rule, the number text and the XML character data are recwrite.h's (shared with the CPU
 // tests); DESIGN.md "Records of fields out of the device" has the field model and the one file written with it (GraphML).
 //
-// fal_records_write_sizes (one synchronisation, at its end): a lane per unit adds up its text, then the library's scan turns the
-// sizes into offsets.
+// fal_records_write_sizes (one synchronisation, at its end): a lane per unit adds up its text (textwrite.h's sizes_by_lane), then
+// the library's scan turns the sizes into offsets.
 //
-// fal_records_write (one synchronisation, at its end): csvwrite.hip's shape -- a lane per unit, a wave per tile of 64 consecutive
-// units.  The workgroup stages the literal blob in LDS once; the field table is a kernel argument.  A round measures the units
-// again, places them in the wave's LDS tile (textwrite.h's Tile around the round's first byte) at a wave prefix sum of their
-// lengths -- as many leading units as the tile takes -- the lanes format there and the tile is flushed whole.  A unit that no tile
-// takes is written by the whole wave: piece after piece is appended to the tile (a literal; a number; kRecTextChunk text bytes per
-// lane at a wave prefix sum of their character data) and the tile's complete 16-byte units are flushed behind every piece.  Every
-// unit's length is checked against offsets[k + 1] - offsets[k] and every round's range against [0, offsets[last] -
-// offsets[first]] <= out_bytes before anything of it is stored.
+// fal_records_write (one synchronisation, at its end): a lane per unit, a wave per tile of 64 consecutive units -- textwrite.h's
+// write_units_by_lane, which has the rounds, the tile and every bound on a store.  What this unit gives it is RecUnits.  The
+// workgroup stages the literal blob in LDS once; the field table is a kernel argument.  A unit that no tile takes is written by
+// the whole wave with textwrite.h's pieces: a literal copied lane-strided; a number from lane 0; kRecTextChunk text bytes per lane
+// at a wave prefix sum of their character data.
 #include <stddef.h>
 #include <algorithm>
 #include "common.h"
@@ -25,9 +22,8 @@ namespace {
 
 constexpr int kRecTile = 8192;                   // bytes of a wave's tile; a multiple of 16
 constexpr int kRecTextChunk = 16;                // text bytes a lane takes per round of the long-unit path
-constexpr int kRecCarry = 31;                    // bytes a flush that is not the last may leave in the tile
-static_assert(kRecTile % 16 == 0 && kRecCarry + 64 * kRecTextChunk * kRecEntityMax <= kRecTile && kRecCarry + kRecLitMax <= kRecTile &&
-                  kRecCarry + kRecNumMax <= kRecTile,
+static_assert(kRecTile % 16 == 0 && kTileCarry + 64 * kRecTextChunk * kRecEntityMax <= kRecTile && kTileCarry + kRecLitMax <= kRecTile &&
+                  kTileCarry + kRecNumMax <= kRecTile,
               "the tile takes one piece of a long unit behind what the last flush left");
 static_assert(sizeof(RecField) == sizeof(fal_rec_field) && offsetof(RecField, index) == offsetof(fal_rec_field, index) &&
                   offsetof(RecField, blob_bytes) == offsetof(fal_rec_field, blob_bytes) && offsetof(RecField, kind) == offsetof(fal_rec_field, kind) &&
@@ -37,48 +33,54 @@ static_assert(kRecMaxFields == FAL_REC_MAX_FIELDS && kRecLitMax == FAL_REC_MAX_L
                   REC_F32 == FAL_REC_F32 && REC_TEXT == FAL_REC_TEXT,
               "the header states the limits and the kinds");
 
-// ---- sizes: a lane per unit -----------------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void rec_write_sizes_kernel(RecTable t, int64_t n, int64_t* __restrict__ sizes,
-                                                              unsigned long long* __restrict__ meta) {
-    const int64_t step = (int64_t)gridDim.x * blockDim.x;
-    bool any_bad = false;
-    for (int64_t k = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; k < n; k += step) {
-        bool bad = false;
-        const int64_t len = rec_unit_len(t, k, &bad);
-        sizes[k] = bad ? 0 : len;
-        any_bad |= bad;
-    }
-    if (any_bad) atomicOr(&meta[META_FLAGS], (unsigned long long)TW_BAD_INPUT);
-}
-
-// ---- the long-unit path: the wave appends pieces to its tile ---------------------------------------------------------------------------
-__device__ __forceinline__ void tile_append_literal(Tile& t, const uint8_t* lit, const int32_t* range, int lane) {
-    const int m = range[1] - range[0];
-    for (int i = lane; i < m; i += 64) t.tile[t.hi + i] = lit[range[0] + i];
-    t.hi += m;
-    tile_flush(t, false, lane);
-}
-
-__device__ __forceinline__ void tile_append_number(Tile& t, const RecValue& v, int lane) {
-    if (lane == 0) rec_write_number(t.tile + t.hi, v);
-    t.hi += (int)rec_value_len(v);
-    tile_flush(t, false, lane);
-}
-
+// kRecTextChunk text bytes per lane as character data, 64 lanes a piece (p, n: the same in every lane)
 __device__ __forceinline__ void tile_append_xml(Tile& t, const uint8_t* p, int64_t n, int lane) {
-    for (int64_t c = 0; c < n; c += 64 * kRecTextChunk) {                        // (n: the same in every lane)
+    for (int64_t c = 0; c < n; c += 64 * kRecTextChunk) {
         const int64_t a = std::min<int64_t>(c + (int64_t)lane * kRecTextChunk, n), b = std::min<int64_t>(a + kRecTextChunk, n);
         int len = 0;
         for (int64_t i = a; i < b; ++i) len += rec_xml_byte_len(p[i]);
-        const int incl = wave_prefix_sum(len);
-        uint8_t* dst = t.tile + t.hi + incl - len;
-        for (int64_t i = a; i < b; ++i) dst += rec_xml_write_byte(dst, p[i]);
-        t.hi += __shfl(incl, 63, 64);
-        tile_flush(t, false, lane);
+        tile_append_by_lanes(t, len, lane, [&](uint8_t* dst) {
+            for (int64_t i = a; i < b; ++i) dst += rec_xml_write_byte(dst, p[i]);
+        });
     }
 }
 
-// ---- write: a lane per unit, a wave per tile of 64 units ---------------------------------------------------------------------------------
+// ---- the units as textwrite.h's lane-per-unit writers take them ----------------------------------------------------------------------------
+struct RecUnits {
+    typedef int64_t Unit;                                                        // the unit's length: a lane formats from the columns again
+    static constexpr bool kLongByWave = true;
+    const RecTable& t;
+    const uint8_t* lit;                                                          // the literal blob (in LDS; the sizes need none)
+    __device__ int64_t load(int64_t k, bool* bad) const { return rec_unit_len(t, k, bad); }
+    __device__ int64_t len(int64_t unit) const { return unit; }
+    __device__ int64_t write(uint8_t* dst, int64_t, int64_t k) const { return rec_write_unit(dst, t, lit, k); }
+    __device__ void literal(Tile& text, const int32_t* range, int lane) const {
+        tile_append_bytes<kRecLitMax>(text, lit + range[0], range[1] - range[0], lane);
+    }
+    // a unit that no tile takes: the whole wave writes it, piece after piece through the tile
+    __device__ void long_unit(uint8_t* tile, uint8_t* dst, int64_t len, int64_t k, unsigned long long* meta) const {
+        const int lane = threadIdx.x & 63;
+        Tile text = tile_open(tile, dst, dst + len);
+        literal(text, t.head, lane);
+        for (int j = 0; j < t.n_fields; ++j) {
+            bool unused = false;
+            const RecValue v = rec_load(t.f[j], k, &unused);                    // (unit k in every lane)
+            if (!v.present) continue;
+            literal(text, t.f[j].prefix, lane);
+            if (v.kind == REC_TEXT) tile_append_xml(text, v.p, v.n, lane);
+            else tile_append_by_lane0(text, (int)rec_value_len(v), lane, [&](uint8_t* d) { rec_write_number(d, v); });
+            literal(text, t.f[j].suffix, lane);
+        }
+        literal(text, t.tail, lane);
+        tile_close(text, lane, meta);
+    }
+};
+
+__global__ __launch_bounds__(256) void rec_write_sizes_kernel(RecTable t, int64_t n, int64_t* __restrict__ sizes,
+                                                              unsigned long long* __restrict__ meta) {
+    sizes_by_lane(RecUnits{t, nullptr}, n, sizes, meta);
+}
+
 __global__ __launch_bounds__(256) void rec_write_kernel(RecTable t, const uint8_t* __restrict__ literals, int lit_bytes,
                                                         const int64_t* __restrict__ offsets, int64_t first, int64_t last,
                                                         uint8_t* __restrict__ out, int64_t out_bytes, unsigned long long* __restrict__ meta) {
@@ -86,73 +88,7 @@ __global__ __launch_bounds__(256) void rec_write_kernel(RecTable t, const uint8_
     __shared__ __attribute__((aligned(16))) uint8_t lit[kRecLitMax];
     for (int i = threadIdx.x; i < lit_bytes; i += blockDim.x) lit[i] = literals[i];              // (lit_bytes <= kRecLitMax: the host checked)
     __syncthreads();
-    const int lane = threadIdx.x & 63;
-    uint8_t* tile = tiles[threadIdx.x >> 6];
-    const int64_t base = offsets[first], need = offsets[last] - base;
-    if (need < 0 || need > out_bytes) {                                          // uniform over the grid: nothing is written
-        if (blockIdx.x == 0 && threadIdx.x == 0) atomicOr(&meta[META_FLAGS], (unsigned long long)TW_TOO_SMALL);
-        return;
-    }
-    const int64_t waves = (int64_t)gridDim.x * (blockDim.x >> 6), n_tiles = (last - first + 63) / 64;
-    for (int64_t w = blockIdx.x * (int64_t)(blockDim.x >> 6) + (threadIdx.x >> 6); w < n_tiles; w += waves) {
-        const int64_t k1 = std::min<int64_t>(first + 64 * (w + 1), last);
-        int64_t r = first + 64 * w;
-        while (r < k1) {                                                         // (r, k1: the same in every lane)
-            const int64_t k = r + lane;
-            const bool on = k < k1;
-            bool bad = false;
-            int64_t len = 0;
-            if (on) {
-                len = rec_unit_len(t, k, &bad);
-                bad |= len != offsets[k + 1] - offsets[k];
-            }
-            const int64_t g0 = offsets[r] - base;
-            if (__ballot(bad) != 0ull || g0 < 0 || g0 > need) {                 // columns or offsets that are not the sizing pass's
-                if (lane == 0) atomicOr(&meta[META_FLAGS], (unsigned long long)TW_BAD_INPUT);
-                break;
-            }
-            const int mis = (int)(reinterpret_cast<uintptr_t>(out + g0) & 15);
-            const int cap = kRecTile - mis;
-            const int clen = (int)std::min<int64_t>(len, kRecTile + 1);         // (64 of them stay far below 2^31)
-            const int incl = wave_prefix_sum(clen);
-            const int cnt = __popcll(__ballot(on && incl <= cap));              // the leading units the tile takes (incl ascends)
-            if (cnt == 0) {                                                      // unit r alone is longer than a tile: the whole wave writes it
-                const int64_t len0 = __shfl((long long)len, 0, 64);
-                if (g0 + len0 > need) {
-                    if (lane == 0) atomicOr(&meta[META_FLAGS], (unsigned long long)TW_BAD_INPUT);
-                    break;
-                }
-                Tile text{tile, out + g0 - mis, out + g0 + len0, mis, mis, false};
-                tile_append_literal(text, lit, t.head, lane);
-                for (int j = 0; j < t.n_fields; ++j) {
-                    bool unused = false;
-                    const RecValue v = rec_load(t.f[j], r, &unused);            // (unit r in every lane)
-                    if (!v.present) continue;
-                    tile_append_literal(text, lit, t.f[j].prefix, lane);
-                    if (v.kind == REC_TEXT) tile_append_xml(text, v.p, v.n, lane);
-                    else tile_append_number(text, v, lane);
-                    tile_append_literal(text, lit, t.f[j].suffix, lane);
-                }
-                tile_append_literal(text, lit, t.tail, lane);
-                tile_flush(text, true, lane);
-                const bool shortfall = text.gbase + text.hi != text.end;         // (less text than the sizes said)
-                if (lane == 0 && (text.overflow || shortfall)) atomicOr(&meta[META_FLAGS], (unsigned long long)TW_OVERFLOW);
-                wave_lds_sync();
-                r += 1;
-                continue;
-            }
-            const int total = __shfl(incl, cnt - 1, 64);
-            if (g0 + total > need) {
-                if (lane == 0) atomicOr(&meta[META_FLAGS], (unsigned long long)TW_BAD_INPUT);
-                break;
-            }
-            if (lane < cnt && rec_write_unit(tile + mis + incl - clen, t, lit, k) != len) atomicOr(&meta[META_FLAGS], (unsigned long long)TW_OVERFLOW);
-            Tile text{tile, out + g0 - mis, out + g0 + total, mis, mis + total, false};       // [mis, mis + total): this round's text
-            tile_flush(text, true, lane);
-            wave_lds_sync();                                                     // (the next round writes the tile again)
-            r += cnt;
-        }
-    }
+    write_units_by_lane<kRecTile>(RecUnits{t, lit}, tiles[threadIdx.x >> 6], offsets, first, last, out, out_bytes, meta);
 }
 
 FAL_WARM_KERNEL(rec_write_kernel);

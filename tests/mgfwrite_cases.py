@@ -87,22 +87,23 @@ def _csr(sizes, rng, lo=1e-3, hi=2000.0):
 
 
 PEAK_COUNTS = (0, 1, 63, 64, 65, 200, 5000)
-TITLE_LENGTHS = (0, 1, 255, 5000)
+TITLE_LENGTHS = (0, 1, 255, 2047, 2048, 2049, 5000)      # (2,048: the title bytes the write kernel appends per piece)
 
 
 def entry_cases() -> Entries:
     """peaks of 0, 1, 63, 64, 65, 200 and 5,000 (a raw-sized entry); charge none / positive / negative / two-digit; cluster ids 0
-    and 2^40; titles of 0, 1, 255 and 5,000 bytes and a non-ASCII UTF-8 one; retention time -1.0.  Values lie in [1e-3, 2000]:
-    the reader's fast forms (the round trip reads them back)."""
+    and 2^40; titles of 0, 1, 255, 2,047, 2,048, 2,049 and 5,000 bytes and a non-ASCII UTF-8 one; retention time -1.0.  Values
+    lie in [1e-3, 2000]: the reader's fast forms (the round trip reads them back)."""
     rng = np.random.default_rng(7)
-    sizes = list(PEAK_COUNTS) + [3, 17, 5, 0, 9]
+    sizes = list(PEAK_COUNTS) + [3, 17, 5, 0, 9, 2, 0, 4]
     mz, it, indptr = _csr(sizes, rng)
     n = len(sizes)
-    charge = np.array([0, 2, -1, 12, 3, -14, 0, 2, 2, 3, 1, 2], np.int32)[:n]
-    cluster = np.array([0, 1 << 40, 5, 6, 7, 8, 9, 10, 11, 12, 13, 123456789012], np.int64)[:n]
+    charge = np.array([0, 2, -1, 12, 3, -14, 0, 2, 2, 3, 1, 2, 2, 0, 3], np.int32)[:n]
+    cluster = np.array([0, 1 << 40, 5, 6, 7, 8, 9, 10, 11, 12, 13, 123456789012, 14, 15, 16], np.int64)[:n]
     # (the two titles the device reader leaves to the host -- a line above its limit, a non-ASCII byte -- sit on small entries)
     title = ["", "x", "t" * 255, "id3", "id4", "mzspec:PXD000001:run:scan:7", "a=b c", "  padded",
-             "L" * 5000, "spéctre 质谱 μ", "id10", "id11"][:n]
+             "L" * 5000, "spéctre 质谱 μ", "id10", "id11", "A" * 2047, "B" * 2048, "C" * 2049][:n]
+    assert sorted(len(t) for t in title if len(t) in TITLE_LENGTHS) == sorted(TITLE_LENGTHS)
     pm = np.exp(rng.uniform(np.log(50.0), np.log(2000.0), n)).astype(np.float32)
     rt = rng.uniform(0.0, 2000.0, n).astype(np.float32)
     rt[2], rt[7] = -1.0, -1.0

@@ -148,8 +148,9 @@ def run_all(ctx):
 @pytest.mark.parametrize("name", CASE_SETS)
 def test_device_text_equals_write_spectra(ctx, name):
     """entry_cases: 0 / 1 / 63 / 64 / 65 / 200 / 5,000 peaks, every charge form, cluster ids 0 and 2^40, titles of 0 / 1 / 255 /
-    5,000 bytes and a non-ASCII one, RT -1; number_entries: every exponent x the edge mantissas through the device compile of
-    the formatter; shuffled_rows: `rows` shuffled with repeats (entry_cases has the identity of the consensus form)"""
+    2,047 / 2,048 / 2,049 (around the title bytes the kernel appends per piece) / 5,000 bytes and a non-ASCII one, RT -1;
+    number_entries: every exponent x the edge mantissas through the device compile of the formatter; shuffled_rows: `rows`
+    shuffled with repeats (entry_cases has the identity of the consensus form)"""
     check_case_set(ctx, name)
 
 
