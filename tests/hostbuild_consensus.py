@@ -64,7 +64,8 @@ int64_t t_consensus(const float* mz, const float* it, const int64_t* ptr, int64_
         }
         if (!done) {
             const int64_t r = medoids[c];
-            for (int64_t j = ptr[r]; j < ptr[r + 1]; ++j, ++w) out_mz[w] = mz[j], out_it[w] = it[j];
+            if (r >= 0 && r < n)                             // (a medoid that is no row copies nothing: cons_out_counts_kernel)
+                for (int64_t j = ptr[r]; j < ptr[r + 1]; ++j, ++w) out_mz[w] = mz[j], out_it[w] = it[j];
             status[c] = FAL_CONS_ST_FALLBACK;
         }
         out_ptr[c + 1] = w;
@@ -95,7 +96,9 @@ def consensus(lib, mz, intensity, indptr, labels, medoids, fragment_tol, min_fra
     mz, it = np.ascontiguousarray(mz, np.float32), np.ascontiguousarray(intensity, np.float32)
     ptr = np.ascontiguousarray(indptr, np.int64)
     labels, medoids = np.ascontiguousarray(labels, np.int32), np.ascontiguousarray(medoids, np.int32)
-    nc, cap = len(medoids), max(len(mz), 1)
+    # room: every peak once, and once more the medoid's of a cluster that falls back to a row of another cluster
+    inside = medoids[(medoids >= 0) & (medoids < len(labels))]
+    nc, cap = len(medoids), max(len(mz) + int(np.diff(ptr)[inside].sum()), 1)
     out_ptr, out_mz, out_it = np.zeros(nc + 1, np.int64), np.zeros(cap, np.float32), np.zeros(cap, np.float32)
     status = np.zeros(max(nc, 1), np.int32)
     w = lib.t_consensus(_p(mz), _p(it), _p(ptr), len(labels), _p(labels), _p(medoids), nc, float(fragment_tol),

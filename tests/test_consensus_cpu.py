@@ -144,6 +144,49 @@ def test_restatement_does_not_depend_on_row_order_without_m_z_ties():
         assert np.array_equal(x, y)
 
 
+# ---- the designed cases: each reaches its decision on the restatement alone, and the header agrees ---------------------------
+def _reference(case):
+    p = case["part"]
+    return cc.consensus_reference(p["mz"], p["intensity"], p["indptr"], p["labels"], p["medoids"], case["tol"], case["q"])
+
+
+@pytest.mark.parametrize("name", list(cc.DECISION_CASES))
+def test_decision_case_shows_its_witness(name):
+    from falcon_amd import _lib
+    assert cc.CUT == _lib.CONS_LDS_PEAKS
+    case = cc.DECISION_CASES[name]()
+    case["witness"](_reference(case))
+
+
+@pytest.mark.parametrize("name", list(cc.DECISION_CASES))
+def test_host_build_equals_the_restatement_on_the_decision_cases(lib, name):
+    case = cc.DECISION_CASES[name]()
+    _check(lib, case["part"], case["tol"], case["q"])
+
+
+def test_restatement_ignores_labels_and_medoids_outside_the_partition():
+    """rows labelled -1 or >= n_clusters belong to no cluster whatever they hold; a medoid outside [0, n) copies nothing"""
+    mz, it, indptr = _csr([([100.0], [1.0]), ([100.0], [1.0]), ([200.0], [1.0]), ([300.0], [1.0])])
+    ref = cc.consensus_reference(mz, it, indptr, np.array([-1, 0, 5, 0], np.int32), np.array([4, 4, -1], np.int32), 0.05, 1.0)
+    assert ref[0].tolist() == [0, 0, 0, 0] and ref[3].tolist() == [cc.FALLBACK] * 3        # {100}, {300}: no group of two
+    ref = cc.consensus_reference(mz, it, indptr, np.array([-1, 0, 5, 0], np.int32), np.array([2, 4, -1], np.int32), 0.05, 0.5)
+    assert ref[0].tolist() == [0, 2, 2, 2] and _same(ref[1], [100.0, 300.0]) and ref[3].tolist() == [0, cc.FALLBACK, cc.FALLBACK]
+
+
+@pytest.mark.parametrize("builder", [cc.lds_turns, cc.flat_turns], ids=["lds_turns", "flat_turns"])
+def test_turn_case_gathered_from_its_library_is_the_restatement_of_the_whole(builder):
+    """at a nominal 2 CUs: the expected output gathered from the library's equals the restatement run on every cluster of the
+    case, and the case meets its turn conditions"""
+    part, pick, cond = builder(2)
+    assert all(cond.values()), cond
+    lib = (cc.lds_turns_library if builder is cc.lds_turns else cc.flat_turns_library)()[0]
+    want = cc.gather_expected(_reference(dict(part=lib, tol=0.05, q=0.25)), pick)
+    ref = _reference(dict(part=part, tol=0.05, q=0.25))
+    assert np.array_equal(ref[0], want[0]) and np.array_equal(ref[3], want[3])
+    assert np.array_equal(cc.bits(ref[1]), cc.bits(want[1])) and np.array_equal(cc.bits(ref[2]), cc.bits(want[2]))
+    assert (ref[3] == cc.FALLBACK).any() and (np.diff(ref[0]) > 1).any()
+
+
 # ---- options ---------------------------------------------------------------------------------------------------------------
 def _parse(args):
     from falcon_amd.config import Config
