@@ -21,6 +21,10 @@ PEAK_STATUS = {1: "bad descriptor", 2: "bad base64", 4: "bad zlib header", 8: "b
                256: "bad MS-Numpress stream"}
 # fal_mgf_index / fal_mgf_parse: flags of a text the host reader has to read, and the per-spectrum status (include/falcon_hip.h)
 MGF_FLAG_BYTES, MGF_FLAG_LINES, MGF_ST_HOST = 1, 2, 1
+# fal_mgf_parse_ex / fal_mgf_headers / fal_text_rows: the optional-key bit, the key table's limits, kinds and states, the widest row
+MGF_OPT_TITLE, MGF_MAX_KEYS, MGF_MAX_KEY_BYTES, TEXT_MAX_WIDTH = 1, 16, 32, 256
+MGF_KEY_SPAN, MGF_KEY_INT = 0, 1
+MGF_KEY_ABSENT, MGF_KEY_PRESENT, MGF_KEY_HOST = 0, 1, 2
 # fal_mgf_write: the most bytes one number takes (csrc/mgfwrite.h kMgfNumMax)
 MGF_NUM_MAX = 23
 FAL_EINVAL = -1
@@ -137,6 +141,10 @@ _SIGNATURES = {
     "fal_mgf_index": ([c_void_p, c_void_p, c_int64, P(c_int64)], c_int),
     "fal_mgf_parse": ([c_void_p, c_void_p, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                        c_void_p, c_void_p, c_void_p, c_void_p], c_int),
+    "fal_mgf_parse_ex": ([c_void_p, c_void_p, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                          c_void_p, c_void_p, c_void_p, c_void_p, c_int], c_int),
+    "fal_mgf_headers": ([c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p], c_int),
+    "fal_text_rows": ([c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int64, c_int64, c_int, c_void_p, c_void_p], c_int),
     "fal_mgf_write_sizes": ([c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_void_p,
                              c_void_p, c_void_p, c_int64, c_void_p, c_void_p, P(c_int64)], c_int),
     "fal_mgf_write": ([c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_void_p,

@@ -154,7 +154,8 @@ class Config:
                             "min_matched_peaks) before clustering.")
         p.add_argument("--device", type=int, default=0, help="HIP device ordinal.")
         p.add_argument("--mgf_reader", type=str, default="device", choices=["device", "host"],
-                       help="MGF input: parse the text on the GPU (device), or with the host reader; the outputs are the same.")
+                       help="MGF input, --library and --assign_to files: parse the text on the GPU (device), or with the host "
+                            "readers; the outputs are the same.")
         p.add_argument("--mzml_reader", type=str, default="host", choices=["device", "host"],
                        help="mzML input: scan the XML structure on the GPU (device), or with the host reader (the default until "
                             "tools/mzml_rate.py has shown the device reader faster); the outputs are the same.")

@@ -19,9 +19,15 @@
 // a time staged into the wave's LDS tile, a line per lane: header lines give title / pepmass / charge / rtinseconds (the last
 // line of a key wins), peak lines convert two tokens and land at the spectrum's slot in line order (a scratch copy); the sort
 // of peakdecode.hip (peaksort.h) moves them to the output.  Every write is bounded by the slot the index counted.
+// fal_mgf_parse_ex is that call with a set of optional keys (FAL_MGF_OPT_TITLE: no TITLE is no reason for the host).
+//
+// fal_mgf_headers: a third consumer of the same index, the parse kernel's form: per spectrum and key of the caller's table
+// (mgfkeys.h) the value range of the last header line of that key, a state, and for an integer key the value of its fast form.
+// fal_text_rows: byte ranges of a text -> zero-padded rows of one width (the readers' string columns); needs no index.
 #include <algorithm>
 #include "common.h"
 #include "ivf.h"
+#include "mgfkeys.h"
 #include "mgfparse.h"
 #include "peaksort.h"
 #include "textscan.h"
@@ -225,7 +231,7 @@ __global__ __launch_bounds__(256) void mgf_parse_kernel(const uint8_t* __restric
                                                         const uint8_t* __restrict__ cls, const int32_t* __restrict__ spec_begin,
                                                         const int32_t* __restrict__ spec_end, int64_t n_spec,
                                                         const int64_t* __restrict__ indptr, int64_t nnz_cap, double* __restrict__ tmp_mz,
-                                                        float* __restrict__ tmp_it, MgfOut out) {
+                                                        float* __restrict__ tmp_it, MgfOut out, int optional_keys) {
     __shared__ __attribute__((aligned(16))) uint8_t tiles[4][kWaveStage + 16];
     const int lane = threadIdx.x & 63;
     uint8_t* tile = tiles[threadIdx.x >> 6];
@@ -326,7 +332,7 @@ __global__ __launch_bounds__(256) void mgf_parse_kernel(const uint8_t* __restric
                 rt = __shfl(val, src, 64);
             }
         }
-        host = __ballot(host) != 0 || !has_title || !has_pm || !pm_ok || (has_ch && !ch_ok) || (has_rt && !rt_ok);
+        host = __ballot(host) != 0 || (!has_title && !(optional_keys & FAL_MGF_OPT_TITLE)) || !has_pm || !pm_ok || (has_ch && !ch_ok) || (has_rt && !rt_ok);
         if (lane == 0) {
             out.pmz[s] = has_pm && pm_ok ? pm : 0.0;
             out.charge[s] = has_ch && ch_ok ? ch : 0;
@@ -352,6 +358,109 @@ __global__ __launch_bounds__(256) void mgf_sort_kernel(const int64_t* __restrict
         if (e > nnz_cap) continue;                                             // (the entry point refuses such a capacity)
         wave_sort_peaks(e - b, lane, [&](int64_t j) { return tmp_mz[b + j]; }, [&](int64_t j) { return tmp_it[b + j]; }, out_mz + b,
                         out_it + b);
+    }
+}
+
+// ---- header values by a key table: one wave per spectrum -----------------------------------------------------------------------
+// mgf_parse_kernel's form over the same index.  A line per lane gives the index of its key in the table (-1: none, or no header
+// line); one ballot of "any table key" gates the ballots per key, whose highest lane -- the spectrum's last such line so far --
+// wins.  Lane k carries key k's result across the turns, so no per-key array is indexed by a loop counter.
+static_assert(kMgfMaxKeys == FAL_MGF_MAX_KEYS && kMgfMaxKeyBytes == FAL_MGF_MAX_KEY_BYTES && MGF_VAL_SPAN == FAL_MGF_KEY_SPAN &&
+                  MGF_VAL_INT == FAL_MGF_KEY_INT && MGF_STATE_ABSENT == FAL_MGF_KEY_ABSENT && MGF_STATE_PRESENT == FAL_MGF_KEY_PRESENT &&
+                  MGF_STATE_HOST == FAL_MGF_KEY_HOST && kMgfMaxKeys <= 64,
+              "mgfkeys.h and include/falcon_hip.h name the same table limits, kinds and states");
+__global__ __launch_bounds__(256) void mgf_headers_kernel(const uint8_t* __restrict__ text, int64_t n, const int32_t* __restrict__ start,
+                                                          const uint8_t* __restrict__ cls, const int32_t* __restrict__ spec_begin,
+                                                          const int32_t* __restrict__ spec_end, int64_t n_spec, MgfKeyTable table,
+                                                          int64_t* __restrict__ span_out, int64_t* __restrict__ value_out,
+                                                          int32_t* __restrict__ state_out) {
+    __shared__ __attribute__((aligned(16))) uint8_t tiles[4][kWaveStage + 16];
+    __shared__ MgfKeyTable keys;
+    {
+        const uint32_t* src = reinterpret_cast<const uint32_t*>(&table);
+        uint32_t* dst = reinterpret_cast<uint32_t*>(&keys);
+        for (int i = threadIdx.x; i < (int)(sizeof(MgfKeyTable) / 4); i += 256) dst[i] = src[i];
+    }
+    __syncthreads();
+    const int n_keys = keys.n;
+    const int lane = threadIdx.x & 63;
+    uint8_t* tile = tiles[threadIdx.x >> 6];
+    const int64_t waves = (int64_t)gridDim.x * (blockDim.x >> 6);
+    for (int64_t s = blockIdx.x * (int64_t)(blockDim.x >> 6) + (threadIdx.x >> 6); s < n_spec; s += waves) {
+        const int64_t b = spec_begin[s], e = spec_end[s];
+        int my_state = MGF_STATE_ABSENT;                                       // lane k: key k
+        int64_t my_lo = 0, my_hi = 0, my_val = 0;
+        for (int64_t g = b + 1; g < e; g += 64) {
+            const int64_t g1 = std::min<int64_t>(g + 64, e);
+            const int64_t b0 = start[g], b1 = std::min<int64_t>(start[g1], n), a0 = b0 & ~(int64_t)15;
+            const bool staged = b1 - a0 <= kWaveStage;                         // wave-uniform
+            if (staged) stage_bytes(text, n, b0, b1, tile, lane, 64);
+            wave_lds_sync();
+            const int64_t line = g + lane;
+            int idx = -1, st = MGF_STATE_PRESENT;
+            int64_t v_lo = 0, v_hi = 0, ival = 0;
+            if (line < g1) {
+                const int c = cls[line];
+                if ((c & MGF_KIND) == MGF_HEADER) {
+                    const int64_t ls = start[line];
+                    const int len = (int)(start[line + 1] - 1 - ls);
+                    const uint8_t* p = staged ? tile + (ls - a0) : text + ls;
+                    int lo = 0, hi = len, klo, khi, a, z;
+                    mgf_strip(p, &lo, &hi);
+                    mgf_split(p, lo, hi, &klo, &khi, &a, &z);
+                    idx = mgf_table_key(p + klo, khi - klo, keys.bytes, keys.len, n_keys);
+                    if (idx >= 0) {
+                        v_lo = ls + a;
+                        v_hi = ls + z;
+                        if (c & MGF_LONG) st = MGF_STATE_HOST;
+                        else if (keys.kind[idx] == MGF_VAL_INT && z > a && !mgf_parse_int(p + a, z - a, &ival)) st = MGF_STATE_HOST;
+                    }
+                }
+            }
+            if (__ballot(idx >= 0) == 0) continue;                             // no table key among these lines
+            for (int k = 0; k < n_keys; ++k) {
+                const uint64_t m = __ballot(idx == k);
+                if (m == 0) continue;
+                const int src = 63 - __builtin_clzll(m);
+                const int st_k = __shfl(st, src, 64);
+                const int64_t lo_k = __shfl(v_lo, src, 64), hi_k = __shfl(v_hi, src, 64), val_k = __shfl(ival, src, 64);
+                if (lane == k) {
+                    my_state = st_k;
+                    my_lo = lo_k;
+                    my_hi = hi_k;
+                    my_val = st_k == MGF_STATE_PRESENT ? val_k : 0;
+                }
+            }
+        }
+        if (lane < n_keys) {
+            const int64_t at = s * n_keys + lane;                              // < n_spec * n_keys
+            span_out[2 * at] = my_lo;
+            span_out[2 * at + 1] = my_hi;
+            value_out[at] = my_val;
+            state_out[at] = my_state;
+        }
+    }
+}
+
+// ---- byte ranges -> fixed-width rows ---------------------------------------------------------------------------------------------
+// a thread per four bytes of a row; a range outside the text gives a zero row and sets the call's range flag
+constexpr unsigned long long kTextFlagRange = 1;
+__global__ __launch_bounds__(256) void text_rows_kernel(const uint8_t* __restrict__ text, int64_t n_bytes, const int64_t* __restrict__ span,
+                                                        int64_t stride, int64_t column, int64_t n, int width, uint8_t* __restrict__ rows_out,
+                                                        int32_t* __restrict__ long_out, unsigned long long* __restrict__ meta) {
+    const int groups = (width + 3) / 4;
+    const int64_t total = n * groups, step = (int64_t)gridDim.x * blockDim.x;
+    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < total; i += step) {
+        const int64_t r = i / groups;
+        const int q = (int)(i - r * groups);
+        const int64_t from = span[(r * stride + column) * 2], to = span[(r * stride + column) * 2 + 1];
+        const bool ok = from >= 0 && to >= from && to <= n_bytes;
+        const int64_t len = ok ? to - from : 0;
+        if (q == 0) {
+            long_out[r] = len > width ? 1 : 0;
+            if (!ok) atomicOr(&meta[META_FLAGS], kTextFlagRange);
+        }
+        for (int c = 4 * q; c < std::min(4 * q + 4, width); ++c) rows_out[r * width + c] = c < len ? text[from + c] : (uint8_t)0;
     }
 }
 
@@ -416,11 +525,13 @@ extern "C" int fal_mgf_index(fal_ctx* ctx, const uint8_t* text, int64_t n_bytes,
     return FAL_OK;
 }
 
-extern "C" int fal_mgf_parse(fal_ctx* ctx, const uint8_t* text, int64_t n_bytes, int64_t n_spectra, int64_t nnz_cap,
-                             int64_t* out_indptr, double* out_mz, float* out_intensity, double* precursor_mz, int32_t* charge,
-                             int32_t* has_charge, double* retention_time, int64_t* title, int64_t* span, int32_t* status_out) {
+extern "C" int fal_mgf_parse_ex(fal_ctx* ctx, const uint8_t* text, int64_t n_bytes, int64_t n_spectra, int64_t nnz_cap,
+                                int64_t* out_indptr, double* out_mz, float* out_intensity, double* precursor_mz, int32_t* charge,
+                                int32_t* has_charge, double* retention_time, int64_t* title, int64_t* span, int32_t* status_out,
+                                int optional_keys) {
     fal::CallScope _call(ctx);
     FAL_REQUIRE(ctx && out_indptr && n_spectra >= 0 && nnz_cap >= 0, FAL_EINVAL, "fal_mgf_parse: bad argument");
+    FAL_REQUIRE((optional_keys & ~FAL_MGF_OPT_TITLE) == 0, FAL_EINVAL, "fal_mgf_parse: unknown optional_keys bits %d", optional_keys);
     const fal_ctx::TextIndex& ix = ctx->mgf;
     FAL_REQUIRE(matches(ctx, ix, SLOT_MGF, text, n_bytes, n_spectra), FAL_EINVAL,
                 "fal_mgf_parse: not the text, length and spectrum count of the last fal_mgf_index of this context");
@@ -446,10 +557,77 @@ extern "C" int fal_mgf_parse(fal_ctx* ctx, const uint8_t* text, int64_t n_bytes,
     const unsigned grid = capped_grid(ctx, n_spectra, 4);
     const MgfOut out{precursor_mz, charge, has_charge, retention_time, title, span, status_out};
     hipLaunchKernelGGL(mgf_parse_kernel, dim3(grid), dim3(256), 0, ctx->stream, text, n_bytes, start, cls, spec_begin, spec_end, n_spectra,
-                       out_indptr, nnz_cap, tmp_mz, tmp_it, out);
+                       out_indptr, nnz_cap, tmp_mz, tmp_it, out, optional_keys);
     FAL_CHECK_HIP(hipGetLastError());
     hipLaunchKernelGGL(mgf_sort_kernel, dim3(grid), dim3(256), 0, ctx->stream, out_indptr, n_spectra, nnz_cap, tmp_mz, tmp_it, out_mz,
                        out_intensity);
     FAL_CHECK_HIP(hipGetLastError());
+    return FAL_OK;
+}
+
+extern "C" int fal_mgf_parse(fal_ctx* ctx, const uint8_t* text, int64_t n_bytes, int64_t n_spectra, int64_t nnz_cap,
+                             int64_t* out_indptr, double* out_mz, float* out_intensity, double* precursor_mz, int32_t* charge,
+                             int32_t* has_charge, double* retention_time, int64_t* title, int64_t* span, int32_t* status_out) {
+    return fal_mgf_parse_ex(ctx, text, n_bytes, n_spectra, nnz_cap, out_indptr, out_mz, out_intensity, precursor_mz, charge, has_charge,
+                            retention_time, title, span, status_out, 0);
+}
+
+extern "C" int fal_mgf_headers(fal_ctx* ctx, const uint8_t* text, int64_t n_bytes, int64_t n_spectra, const uint8_t* keys,
+                               const int64_t* key_ptr, const int32_t* key_kind, int n_keys, int64_t* span_out, int64_t* value_out,
+                               int32_t* state_out) {
+    fal::CallScope _call(ctx);
+    FAL_REQUIRE(ctx && n_spectra >= 0 && keys && key_ptr && key_kind, FAL_EINVAL, "fal_mgf_headers: bad argument");
+    FAL_REQUIRE(n_keys >= 1 && n_keys <= kMgfMaxKeys, FAL_EINVAL, "fal_mgf_headers: %d keys, 1 to %d are taken", n_keys, kMgfMaxKeys);
+    MgfKeyTable table = {};
+    table.n = n_keys;
+    for (int k = 0; k < n_keys; ++k) {
+        const int64_t a = key_ptr[k], len = key_ptr[k + 1] - a;
+        FAL_REQUIRE(a >= 0 && len >= 1 && len <= kMgfMaxKeyBytes, FAL_EINVAL, "fal_mgf_headers: key %d has %lld bytes, 1 to %d are taken",
+                    k, (long long)len, kMgfMaxKeyBytes);
+        FAL_REQUIRE(key_kind[k] == FAL_MGF_KEY_SPAN || key_kind[k] == FAL_MGF_KEY_INT, FAL_EINVAL, "fal_mgf_headers: key %d: unknown kind %d",
+                    k, key_kind[k]);
+        const uint8_t* w = keys + a;
+        bool plain = !mgf_space(w[0]) && !mgf_space(w[len - 1]);
+        for (int64_t i = 0; i < len; ++i) plain = plain && w[i] >= 0x20 && w[i] <= 0x7E && w[i] != '=' && !(w[i] - 'A' < 26u);
+        FAL_REQUIRE(plain, FAL_EINVAL, "fal_mgf_headers: key %d is no stripped lower-case ASCII key", k);
+        int vlo, vhi;
+        FAL_REQUIRE(mgf_header(w, 0, (int)len, &vlo, &vhi) == MGF_KEY_OTHER, FAL_EINVAL,
+                    "fal_mgf_headers: key %d is one of fal_mgf_parse's own (title, pepmass, charge, rtinseconds)", k);
+        FAL_REQUIRE(mgf_table_key(w, (int)len, table.bytes, table.len, k) < 0, FAL_EINVAL, "fal_mgf_headers: key %d repeats an earlier key", k);
+        for (int64_t i = 0; i < len; ++i) table.bytes[k][i] = w[i];
+        table.len[k] = (int32_t)len;
+        table.kind[k] = key_kind[k];
+    }
+    const fal_ctx::TextIndex& ix = ctx->mgf;
+    FAL_REQUIRE(matches(ctx, ix, SLOT_MGF, text, n_bytes, n_spectra), FAL_EINVAL,
+                "fal_mgf_headers: not the text, length and spectrum count of the last fal_mgf_index of this context");
+    if (n_spectra == 0) return FAL_OK;
+    FAL_REQUIRE(span_out && value_out && state_out, FAL_EINVAL, "fal_mgf_headers: NULL output");
+    const int32_t* start = static_cast<const int32_t*>(ix.blocks[0]);
+    const uint8_t* cls = static_cast<const uint8_t*>(ix.blocks[1]);
+    const int32_t* spec = static_cast<const int32_t*>(ix.blocks[3]);
+    hipLaunchKernelGGL(mgf_headers_kernel, dim3(capped_grid(ctx, n_spectra, 4)), dim3(256), 0, ctx->stream, text, n_bytes, start, cls, spec,
+                       spec + ix.cap_spectra, n_spectra, table, span_out, value_out, state_out);
+    FAL_CHECK_HIP(hipGetLastError());
+    return FAL_OK;
+}
+
+extern "C" int fal_text_rows(fal_ctx* ctx, const uint8_t* text, int64_t n_bytes, const int64_t* span, int64_t stride, int64_t column,
+                             int64_t n, int width, uint8_t* rows_out, int32_t* long_out) {
+    fal::CallScope _call(ctx);
+    FAL_REQUIRE(ctx && n >= 0 && n_bytes >= 0 && stride >= 1 && column >= 0 && column < stride, FAL_EINVAL, "fal_text_rows: bad argument");
+    FAL_REQUIRE(width >= 1 && width <= FAL_TEXT_MAX_WIDTH, FAL_EINVAL, "fal_text_rows: width %d, 1 to %d are taken", width,
+                FAL_TEXT_MAX_WIDTH);
+    if (n == 0) return FAL_OK;
+    FAL_REQUIRE((text || n_bytes == 0) && span && rows_out && long_out, FAL_EINVAL, "fal_text_rows: NULL argument");
+    unsigned long long* meta = nullptr;
+    FAL_TRY(ctx->reserve(SLOT_MGF5, sizeof(unsigned long long) * META_WORDS, (void**)&meta));
+    FAL_CHECK_HIP(hipMemsetAsync(meta, 0, sizeof(unsigned long long) * META_WORDS, ctx->stream));
+    hipLaunchKernelGGL(text_rows_kernel, dim3(capped_grid(ctx, n * ((width + 3) / 4), 256)), dim3(256), 0, ctx->stream, text, n_bytes, span,
+                       stride, column, n, width, rows_out, long_out, meta);
+    FAL_CHECK_HIP(hipGetLastError());
+    const unsigned long long* h = nullptr;
+    FAL_TRY(read_meta(ctx, meta, &h));
+    FAL_REQUIRE((h[META_FLAGS] & kTextFlagRange) == 0, FAL_EINVAL, "fal_text_rows: a range lies outside the text (its row is zero)");
     return FAL_OK;
 }

@@ -362,36 +362,79 @@ class Context:
         Synchronises once.  The tables stay in the context for the `mgf_parse` of the same tensor."""
         return self._text_index("fal_mgf_index", d_text)
 
-    def mgf_parse(self, d_text, n: int, nnz: int):
-        """`fal_mgf_parse` behind `mgf_index` of the same tensor -> device tensors indptr i64[n+1], mz f64[nnz], intensity
-        f32[nnz], precursor_mz f64[n], charge i32[n], has_charge i32[n], retention_time f64[n], title i64[n, 2], span i64[n, 2],
-        status i32[n].  No sync."""
+    def mgf_parse(self, d_text, n: int, nnz: int, optional_keys: int = 0):
+        """`fal_mgf_parse` (`fal_mgf_parse_ex` with `optional_keys`, `_lib.MGF_OPT_*` bits) behind `mgf_index` of the same tensor
+        -> device tensors indptr i64[n+1], mz f64[nnz], intensity f32[nnz], precursor_mz f64[n], charge i32[n], has_charge
+        i32[n], retention_time f64[n], title i64[n, 2], span i64[n, 2], status i32[n].  No sync."""
         torch = _torch()
         m = max(n, 1)
         indptr, mz, it = self.empty((n + 1,), torch.int64), self.empty((max(nnz, 1),), torch.float64), self.empty((max(nnz, 1),), torch.float32)
         pmz, rt = self.empty((m,), torch.float64), self.empty((m,), torch.float64)
         charge, has_charge, status = (self.empty((m,), torch.int32) for _ in range(3))
         title, span = self.empty((m, 2), torch.int64), self.empty((m, 2), torch.int64)
-        check(self.lib.fal_mgf_parse(self._h, self._p(d_text) if d_text.numel() else None, d_text.numel(), n, nnz, self._p(indptr),
-                                     self._p(mz), self._p(it), self._p(pmz), self._p(charge), self._p(has_charge), self._p(rt),
-                                     self._p(title), self._p(span), self._p(status)), "fal_mgf_parse")
+        args = (self._h, self._p(d_text) if d_text.numel() else None, d_text.numel(), n, nnz, self._p(indptr), self._p(mz), self._p(it),
+                self._p(pmz), self._p(charge), self._p(has_charge), self._p(rt), self._p(title), self._p(span), self._p(status))
+        if optional_keys:
+            check(self.lib.fal_mgf_parse_ex(*args, optional_keys), "fal_mgf_parse_ex")
+        else:
+            check(self.lib.fal_mgf_parse(*args), "fal_mgf_parse")
         return indptr, mz[:nnz], it[:nnz], pmz[:n], charge[:n], has_charge[:n], rt[:n], title[:n], span[:n], status[:n]
 
-    def parse_mgf(self, text):
+    def mgf_headers(self, d_text, n: int, keys):
+        """`fal_mgf_headers` behind `mgf_index` of the same tensor.  `keys`: lower-case header keys (at most `_lib.MGF_MAX_KEYS`),
+        a sequence of names (byte ranges only) or a dict name -> `_lib.MGF_KEY_SPAN` / `_lib.MGF_KEY_INT`
+        -> device tensors span i64[n, k, 2] (the stripped value of the spectrum's last line of that key), value i64[n, k] (the
+        integer of a decided INT key), state i32[n, k] (`_lib.MGF_KEY_ABSENT` / `PRESENT` / `HOST`).  No sync."""
+        torch = _torch()
+        kinds = np.array([keys[k] for k in keys] if isinstance(keys, dict) else [0] * len(keys), np.int32)
+        raw = [str(k).encode("utf-8") for k in keys]
+        ptr = np.zeros(len(raw) + 1, np.int64)
+        np.cumsum([len(r) for r in raw], out=ptr[1:])
+        blob = np.frombuffer(b"".join(raw) + b"\0", np.uint8)
+        k, m = len(raw), max(n, 1)
+        span, value = self.empty((m, max(k, 1), 2), torch.int64), self.empty((m, max(k, 1)), torch.int64)
+        state = self.empty((m, max(k, 1)), torch.int32)
+        as_p = lambda a: a.ctypes.data_as(C.c_void_p)                             # noqa: E731
+        check(self.lib.fal_mgf_headers(self._h, self._p(d_text) if d_text.numel() else None, d_text.numel(), n, as_p(blob), as_p(ptr),
+                                       as_p(kinds) if k else None, k, self._p(span), self._p(value), self._p(state)), "fal_mgf_headers")
+        return span[:n], value[:n], state[:n]
+
+    def text_rows(self, d_text, span, column: int = 0, width: int = 256):
+        """`fal_text_rows`: the byte ranges span[:, column] (i64 device tensor [n, 2] or [n, k, 2]) of the text as rows of `width`
+        bytes, zero-padded -> device tensors rows u8[n, width], long i32[n] (1: the range is longer than the row).  Synchronises
+        once; a range outside the text raises."""
+        torch = _torch()
+        span = self.to_dev(span, torch.int64)
+        n = int(span.shape[0])
+        stride = int(span.shape[1]) if span.dim() == 3 else 1
+        rows, long = self.empty((max(n, 1), width), torch.uint8), self.empty((max(n, 1),), torch.int32)
+        check(self.lib.fal_text_rows(self._h, self._p(d_text) if d_text.numel() else None, d_text.numel(), self._p(span), stride, column,
+                                     n, width, self._p(rows), self._p(long)), "fal_text_rows")
+        return rows[:n], long[:n]
+
+    def parse_mgf(self, text, optional_title: bool = False, keys=None):
         """MGF text (bytes, uint8 array or uint8 device tensor) -> dict: `flags` (`_lib.MGF_FLAG_*`; non-zero: the text is the
         host reader's and nothing else is set), else the raw CSR on the device -- `indptr` i64[n+1], `mz` f64, `intensity` f32,
         sorted by m/z inside every spectrum as falcon._raw_csr -- and the per-spectrum host columns `precursor_mz` f64,
         `charge` i32, `has_charge` bool, `retention_time` f64 (-1 when absent), `title` / `span` i64[n, 2] (byte ranges of the
         title value and of the spectrum), `status` i32 (0, or `_lib.MGF_ST_HOST`: the host reader decides that spectrum; its
-        slot has the right size and placeholder values).  DESIGN.md "MGF on the device" states the grammar."""
+        slot has the right size and placeholder values).  `optional_title`: a spectrum without TITLE is not HOST on that
+        account (its title range is (0, 0)).  `keys` (see `mgf_headers`) adds `key_span` (device, i64[n, k, 2]) and the host
+        columns `key_value` i64[n, k], `key_state` i32[n, k], and `text`, the device tensor the ranges refer to (for
+        `text_rows`).  DESIGN.md "MGF on the device" states the grammar."""
+        from ._lib import MGF_OPT_TITLE
         d_text = self._text_to_dev(text)
         n, nnz, flags, lines = self.mgf_index(d_text)
         if flags:
             return dict(flags=flags, lines=lines)
-        indptr, mz, it, *cols = self.mgf_parse(d_text, n, nnz)
+        indptr, mz, it, *cols = self.mgf_parse(d_text, n, nnz, MGF_OPT_TITLE if optional_title else 0)
+        extra = {}
+        if keys is not None:
+            key_span, value, state = self.mgf_headers(d_text, n, keys)
+            extra = dict(key_span=key_span, key_value=value.cpu().numpy(), key_state=state.cpu().numpy(), text=d_text)
         pmz, charge, has_charge, rt, title, span, status = (c.cpu().numpy() for c in cols)
         return dict(flags=0, lines=lines, indptr=indptr, mz=mz, intensity=it, precursor_mz=pmz, charge=charge,
-                    has_charge=has_charge.astype(bool), retention_time=rt, title=title, span=span, status=status)
+                    has_charge=has_charge.astype(bool), retention_time=rt, title=title, span=span, status=status, **extra)
 
     def _write_sizes(self, entry: str, args, n: int):
         """a text writer's sizing call `entry` over the packed columns `args`, n units -> (sizes i64[n], offsets i64[n + 1] on the

@@ -222,18 +222,31 @@ def _load_library(spectra_dir: str, ctx):
     already scaled) and partitioned by charge like any input -> ({charge: arrays + `cluster` ids}, first id of a new cluster).
     Each charge's library is also left in the work directory (`library_charge_<z>.npz`): what the run matched against."""
     _, min_mz, max_mz = spectrum.get_dim(config.min_mz, config.max_mz, config.fragment_tol)
-    specs = mgf_io.read_library([os.path.abspath(fn) for fn in config.assign_to])
-    logger.info("Read %d cluster representatives from %d file(s)", len(specs), len(config.assign_to))
-    if not specs:
+    filenames = [os.path.abspath(fn) for fn in config.assign_to]
+    if config.mgf_reader == "device":                    # the text parsed on the device, the peaks left there (mgf_io.read_library_chunks)
+        chunks = mgf_io.read_library(filenames, ctx=ctx)
+        cols, read, valid, oip, omz, oit = _process_entry_chunks(ctx, chunks, min_mz, max_mz, scaling=None)
+        n_read = int(read.sum())
+        logger.debug("Representative MGFs: %d entries parsed on the device", sum(len(c) for c in chunks if c.reader == "device"))
+    else:
+        specs = mgf_io.read_library(filenames)
+        n_read = len(specs)
+    logger.info("Read %d cluster representatives from %d file(s)", n_read, len(config.assign_to))
+    if not n_read:
         return {}, 0
-    first_new = max(s["cluster"] for s in specs) + 1
-    mz, it, indptr = _raw_csr(specs)
-    pmz = np.array([s["precursor_mz"] for s in specs], np.float64)
-    charge = np.array([int(s["precursor_charge"]) if s.get("precursor_charge") else 0 for s in specs], np.int32)
-    valid, oip, omz, oit = _process(ctx, mz, it, indptr, pmz, charge, min_mz, max_mz, scaling=None)
-    logger.info("Skipped %d representatives the preprocessing rejects", int((~valid).sum()))
-    ids = np.array([s["cluster"] for s in specs], np.int64)
-    rt = np.array([s.get("retention_time", -1) for s in specs], np.float32)
+    if config.mgf_reader == "device":
+        pmz, charge, ids, rt = cols["precursor_mz"], cols["precursor_charge"], cols["cluster"], cols["retention_time"].astype(np.float32)
+        first_new = int(ids[read].max()) + 1
+        logger.info("Skipped %d representatives the preprocessing rejects", int((read & ~valid).sum()))
+    else:
+        first_new = max(s["cluster"] for s in specs) + 1
+        mz, it, indptr = _raw_csr(specs)
+        pmz = np.array([s["precursor_mz"] for s in specs], np.float64)
+        charge = np.array([int(s["precursor_charge"]) if s.get("precursor_charge") else 0 for s in specs], np.int32)
+        valid, oip, omz, oit = _process(ctx, mz, it, indptr, pmz, charge, min_mz, max_mz, scaling=None)
+        logger.info("Skipped %d representatives the preprocessing rejects", int((~valid).sum()))
+        ids = np.array([s["cluster"] for s in specs], np.int64)
+        rt = np.array([s.get("retention_time", -1) for s in specs], np.float32)
     library = {}
     for z in np.unique(charge[valid]):
         rows = np.flatnonzero(valid & (charge == z))
@@ -393,7 +406,25 @@ def _load_annotation_library(ctx):
     that survived: the peak CSR, precursor_mz f32, charge i32 (0: none) and the annotation strings"""
     _, min_mz, max_mz = spectrum.get_dim(config.min_mz, config.max_mz, config.fragment_tol)
     counts = {}
-    specs = mgf_io.read_annotation_library([os.path.abspath(fn) for fn in config.library], counts)
+    filenames = [os.path.abspath(fn) for fn in config.library]
+    if config.mgf_reader == "device":                    # the text parsed on the device, the peaks left there (mgf_io.read_annotation_chunks)
+        chunks = mgf_io.read_annotation_library(filenames, counts, ctx=ctx)
+        logger.info("Read %d library spectra from %d file(s), skipped %d entries without a usable precursor or with a malformed "
+                    "peak line", counts["entries"] - counts["skipped"], len(config.library), counts["skipped"])
+        logger.debug("Library MGFs: %d of %d entries decided by the host reader", counts["host"], counts["entries"])
+        cols, read, valid, oip, omz, oit = _process_entry_chunks(ctx, chunks, min_mz, max_mz)
+        text = {k: cols.get(k, cols["filename"]) for k in ("name", "adduct", "smiles", "inchikey", "ionmode")}       # (no chunk: all empty)
+        text.update(library_id=cols.get("identifier", cols["filename"]), library_file=np.array([os.path.basename(fn) for fn in cols["filename"]], dtype=str))
+        if not read.any():
+            return dict({k: text[k][:0] for k in ("library_id", "name", "library_file", "adduct", "smiles", "inchikey", "ionmode")}, precursor_mz=np.zeros(0, np.float32), charge=np.zeros(0, np.int32),
+                        mz=np.zeros(0, np.float32), intensity=np.zeros(0, np.float32), indptr=np.zeros(1, np.int64))
+        logger.info("Skipped %d library spectra the preprocessing rejects", int((read & ~valid).sum()))
+        rows = np.flatnonzero(valid)
+        pos, off = _take_rows(oip, rows)
+        return dict({k: text[k][rows] for k in ("library_id", "name", "library_file", "adduct", "smiles", "inchikey", "ionmode")},
+                    precursor_mz=cols["precursor_mz"][rows].astype(np.float32), charge=cols["precursor_charge"][rows],
+                    mz=omz[pos].astype(np.float32), intensity=oit[pos].astype(np.float32), indptr=off)
+    specs = mgf_io.read_annotation_library(filenames, counts)
     logger.info("Read %d library spectra from %d file(s), skipped %d entries without a usable precursor or with a malformed peak "
                 "line", len(specs), len(config.library), counts["skipped"])
     text = lambda k: np.array([str(s[k]) for s in specs], dtype=str)
@@ -692,6 +723,30 @@ def _process(ctx, mz, it, indptr, pmz, charge, min_mz, max_mz, scaling="config")
         mz, it, indptr, pmz, charge, config.min_peaks, config.min_mz_range, min_mz, max_mz,
         config.remove_precursor_tol, config.min_intensity, config.max_peaks_used, scaling)
     return valid.cpu().numpy(), oip.cpu().numpy(), omz.cpu().numpy(), oit.cpu().numpy()
+
+
+def _process_entry_chunks(ctx, chunks, min_mz, max_mz, scaling="config"):
+    """`fal_process_spectra` over every `mgf_io.EntryChunk` of a library or representative reader, the peaks of a device chunk
+    left on the device (preprocessing is per spectrum: the chunks' results side by side are one call's) -> the chunks' columns
+    side by side (plus `filename`), `read` (False: a row the reader dropped), valid (False for those too), and the out indptr,
+    mz and intensity over all rows as host arrays"""
+    names = list(chunks[0].columns) if chunks else []
+    cols = {k: np.concatenate([c.columns[k] for c in chunks]) for k in names}
+    cols["filename"] = np.concatenate([np.array([c.filename] * len(c), dtype=str) for c in chunks]) if chunks else np.zeros(0, dtype=str)
+    read = np.concatenate([~c.dropped for c in chunks]) if chunks else np.zeros(0, bool)
+    valid, sizes, mzs, its = [], [], [], []
+    for c in chunks:
+        v, oip, omz, oit = _process(ctx, c.mz, c.intensity, c.indptr, c.columns["precursor_mz"], c.columns["precursor_charge"],
+                                    min_mz, max_mz, scaling)
+        valid.append(v & ~c.dropped)
+        sizes.append(np.diff(oip))
+        mzs.append(omz[:oip[-1]])
+        its.append(oit[:oip[-1]])
+    indptr = np.zeros(len(read) + 1, np.int64)
+    if chunks:
+        np.cumsum(np.concatenate(sizes), out=indptr[1:])
+    cat = lambda parts, dt: np.concatenate(parts) if parts else np.zeros(0, dt)          # noqa: E731
+    return cols, read, cat(valid, bool), indptr, cat(mzs, np.float32), cat(its, np.float32)
 
 
 def _partition(parts, fn, ident, pmz, rt, charge, valid, oip, omz, oit) -> None:

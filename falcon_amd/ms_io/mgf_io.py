@@ -114,9 +114,13 @@ def get_library_spectra(filename: str) -> Iterator[Dict]:
             yield got[0]
 
 
-def read_library(filenames) -> list:
+def read_library(filenames, ctx=None):
     """every spectrum of the representative MGFs `filenames`, in order, each with `cluster` and `filename`; the same cluster id
-    twice (inside one file or across them) raises MgfLibraryError"""
+    twice (inside one file or across them) raises MgfLibraryError.  With `ctx` (a `device.Context`) the files are read on the
+    device (`read_library_chunks`): the same spectra and the same first error, as a list of `EntryChunk`s -- `chunk_entries`
+    makes the dicts of them."""
+    if ctx is not None:
+        return read_library_chunks(filenames, ctx)
     out, seen = [], {}
     for fn in filenames:
         for k, s in enumerate(get_library_spectra(fn)):
@@ -132,54 +136,75 @@ def read_library(filenames) -> list:
 ANNOTATION_KEYS = ("adduct", "smiles", "inchikey", "ionmode")
 
 
-def read_annotation_library(filenames, counts: Optional[dict] = None) -> list:
+LIBRARY_KEYS = ("spectrumid", "name", "compound_name") + ANNOTATION_KEYS      # the header keys the device reader asks for
+
+
+def _annotation_entry(params, mzs, its, bad, fn, entry):
+    """the per-entry rule of `read_annotation_library`: an entry's header values and peaks -> its dict, None when it is skipped"""
+    try:
+        pmz = float(params["pepmass"].split()[0])
+        charge = _parse_charge(params["charge"]) if params.get("charge") else 0
+    except (ValueError, KeyError, IndexError):
+        bad = True
+    if bad or not pmz > 0.0 or not np.isfinite(pmz):
+        return None
+    spec = {"identifier": params.get("spectrumid") or params.get("title") or f"{os.path.basename(fn)}:{entry}",
+            "precursor_mz": pmz, "precursor_charge": charge,
+            "retention_time": -1.0, "mz": np.asarray(mzs, np.float64), "intensity": np.asarray(its, np.float32),
+            "name": params.get("name") or params.get("compound_name") or "", "filename": fn}
+    spec.update({k: params.get(k, "") for k in ANNOTATION_KEYS})
+    return spec
+
+
+def _annotation_entries(lines, fn, entry: int = 0):
+    """the entries of library text `lines` (a file, or one entry's own text) of file `fn` -> (entry number, dict or None for a
+    skipped entry), numbered from `entry` + 1"""
+    params, mzs, its, inside, bad = {}, [], [], False, False
+    for line in lines:
+        line = line.strip()
+        if not line or line[0] in "#;!/":
+            continue
+        if line == "BEGIN IONS":
+            params, mzs, its, inside, bad = {}, [], [], True, False
+        elif line == "END IONS":
+            if not inside:
+                continue
+            inside = False
+            entry += 1
+            yield entry, _annotation_entry(params, mzs, its, bad, fn, entry)
+        elif inside:
+            if "=" in line and not (line[0].isdigit() or line[0] == "."):
+                k, v = line.split("=", 1)
+                params[k.strip().lower()] = v.strip()
+            else:
+                tok = line.split()
+                try:
+                    mzs.append(float(tok[0]))
+                    its.append(float(tok[1]) if len(tok) > 1 else 0.0)
+                except ValueError:
+                    bad = True
+
+
+def read_annotation_library(filenames, counts: Optional[dict] = None, ctx=None):
     """The entries of reference spectral library MGFs (`--library`; GNPS style), in order: `get_spectra`'s dicts --
     `precursor_charge` 0 for an entry without CHARGE= or with CHARGE=0 -- plus `name` (NAME=, else COMPOUND_NAME=, else ""),
     `filename`, and `adduct`, `smiles`, `inchikey`, `ionmode` as strings ("" when absent).  `identifier` is SPECTRUMID=, else
     TITLE=, else `<file name>:<entry number>` (the file's base name; entries count from 1, skipped ones included).  An entry
     with no usable precursor (PEPMASS missing, unparsable or <= 0) or with a malformed peak line is skipped; `counts` (a dict)
-    receives `entries` and `skipped`.  A host reader: libraries are small next to the inputs."""
+    receives `entries` and `skipped`.  Without `ctx` a host reader; with `ctx` (a `device.Context`) the files are read on the
+    device (`read_annotation_chunks`): the same entries and counts, as a list of `EntryChunk`s -- `chunk_entries` makes the
+    dicts of them."""
+    if ctx is not None:
+        return read_annotation_chunks(filenames, ctx, counts)
     out, n_entries, n_skipped = [], 0, 0
     for fn in filenames:
         entry = 0
         with open(fn, "r") as f:
-            params, mzs, its, inside, bad = {}, [], [], False, False
-            for line in f:
-                line = line.strip()
-                if not line or line[0] in "#;!/":
-                    continue
-                if line == "BEGIN IONS":
-                    params, mzs, its, inside, bad = {}, [], [], True, False
-                elif line == "END IONS":
-                    if not inside:
-                        continue
-                    inside = False
-                    entry += 1
-                    try:
-                        pmz = float(params["pepmass"].split()[0])
-                        charge = _parse_charge(params["charge"]) if params.get("charge") else 0
-                    except (ValueError, KeyError, IndexError):
-                        bad = True
-                    if bad or not pmz > 0.0 or not np.isfinite(pmz):
-                        n_skipped += 1
-                        continue
-                    spec = {"identifier": params.get("spectrumid") or params.get("title") or f"{os.path.basename(fn)}:{entry}",
-                            "precursor_mz": pmz, "precursor_charge": charge,
-                            "retention_time": -1.0, "mz": np.asarray(mzs, np.float64), "intensity": np.asarray(its, np.float32),
-                            "name": params.get("name") or params.get("compound_name") or "", "filename": fn}
-                    spec.update({k: params.get(k, "") for k in ANNOTATION_KEYS})
+            for entry, spec in _annotation_entries(f, fn):
+                if spec is None:
+                    n_skipped += 1
+                else:
                     out.append(spec)
-                elif inside:
-                    if "=" in line and not (line[0].isdigit() or line[0] == "."):
-                        k, v = line.split("=", 1)
-                        params[k.strip().lower()] = v.strip()
-                    else:
-                        tok = line.split()
-                        try:
-                            mzs.append(float(tok[0]))
-                            its.append(float(tok[1]) if len(tok) > 1 else 0.0)
-                        except ValueError:
-                            bad = True
         n_entries += entry
     if counts is not None:
         counts.update(entries=n_entries, skipped=n_skipped)
@@ -295,19 +320,24 @@ def _device_chunk(ctx, buf, res) -> MgfChunk:
             ident[i], pmz[i], rt[i] = str(s["identifier"]), s["precursor_mz"], s["retention_time"]
             charge[i] = int(s["precursor_charge"]) if s["precursor_charge"] else 0
         ident = np.array(list(ident), dtype=str) if n else np.zeros(0, dtype=str)
-        if pos and sum(len(p) for p in pos):
-            at = torch.from_numpy(np.concatenate(pos)).to(res["mz"].device)
-            res["mz"][at] = torch.from_numpy(np.concatenate(mzs)).to(res["mz"].device)
-            res["intensity"][at] = torch.from_numpy(np.concatenate(its)).to(res["mz"].device)
+        _patch_peaks(res, pos, mzs, its)
     return MgfChunk(res["indptr"], res["mz"], res["intensity"], ident, pmz, charge, rt, dropped, len(host), "device")
 
 
-def read_chunks(filename: str, ctx, max_bytes: int = DEFAULT_CHUNK_BYTES) -> Iterator[MgfChunk]:
-    """The device reader: the file as bytes, cut directly behind END IONS lines into stretches of about `max_bytes` (a
-    stretch grows when one spectrum is larger), each parsed by `ctx.parse_mgf`; spectra with status HOST are read again by
-    `get_spectra`.  A stretch outside the device grammar (a byte the device does not take) ends the device
-    path: the rest of the file is read by `get_spectra` through the same text layer as `open(filename)`, exceptions included.
-    The spectra of all chunks together are `get_spectra(filename)`'s."""
+def _patch_peaks(res, pos, mzs, its) -> None:
+    """the host reader's peaks of re-read spectra (sorted by m/z) into their slots `pos` of a parsed stretch's device CSR"""
+    import torch
+    if pos and sum(len(p) for p in pos):
+        at = torch.from_numpy(np.concatenate(pos)).to(res["mz"].device)
+        res["mz"][at] = torch.from_numpy(np.concatenate(mzs)).to(res["mz"].device)
+        res["intensity"][at] = torch.from_numpy(np.concatenate(its)).to(res["mz"].device)
+
+
+def _stretches(filename: str, ctx, max_bytes: int, **parse):
+    """The file as bytes, cut directly behind END IONS lines into stretches of about `max_bytes` (a stretch grows when one
+    spectrum is larger), each parsed by `ctx.parse_mgf(stretch, **parse)` -> (stretch bytes, result) for every stretch with
+    spectra.  A stretch outside the device grammar ends it with (None, the rest of the file -- that stretch included --
+    behind the same text layer as `open(filename)`)."""
     with open(filename, "rb") as f:
         buf = bytearray()
         final = False
@@ -321,14 +351,267 @@ def read_chunks(filename: str, ctx, max_bytes: int = DEFAULT_CHUNK_BYTES) -> Ite
             if cut == 0:
                 continue                           # one spectrum larger than the stretch: read on
             head = buf[:cut]
-            res = ctx.parse_mgf(head)
+            res = ctx.parse_mgf(head, **parse)
             if res["flags"]:
-                rest = io.BytesIO(bytes(buf) + f.read())
-                yield _host_chunk(list(get_spectra(io.TextIOWrapper(rest))))
+                yield None, io.TextIOWrapper(io.BytesIO(bytes(buf) + f.read()))
                 return
             if len(res["status"]):
-                yield _device_chunk(ctx, head, res)
+                yield head, res
             del buf[:cut]
+
+
+def read_chunks(filename: str, ctx, max_bytes: int = DEFAULT_CHUNK_BYTES) -> Iterator[MgfChunk]:
+    """The device reader: the file's stretches (`_stretches`), each parsed by `ctx.parse_mgf`; spectra with status HOST are
+    read again by `get_spectra`.  A stretch outside the device grammar (a byte the device does not take) ends
+    the device path: the rest of the file is read by `get_spectra` through the same text layer as `open(filename)`,
+    exceptions included.  The spectra of all chunks together are `get_spectra(filename)`'s."""
+    for head, res in _stretches(filename, ctx, max_bytes):
+        if head is None:
+            yield _host_chunk(list(get_spectra(res)))
+            return
+        yield _device_chunk(ctx, head, res)
+
+
+class EntryChunk:
+    """The entries of one stretch of a library or representative MGF, in file order: the raw CSR `indptr` / `mz` / `intensity`
+    (device tensors from the device reader, host arrays where the host rule read the stretch), `filename`, and `columns`, a
+    dict of host arrays by entry -- `identifier` (str), `precursor_mz` f64, `precursor_charge` i32 (0: none),
+    `retention_time` f64, and the reader's own (`name`, `adduct`, `smiles`, `inchikey`, `ionmode`; or `cluster`
+    i64).  `dropped`: entries the host rule skips (their rows stay, so that the CSR is the device's).  `n_host`:
+    entries the host rule decided; `reader`: "device", or "host" for a stretch outside the device grammar."""
+
+    def __init__(self, indptr, mz, intensity, columns, dropped, n_host, reader, filename):
+        self.indptr, self.mz, self.intensity, self.columns = indptr, mz, intensity, columns
+        self.dropped, self.n_host, self.reader, self.filename = dropped, n_host, reader, filename
+
+    def __len__(self):
+        return len(self.dropped)
+
+
+def chunk_entries(chunks) -> list:
+    """`EntryChunk`s -> the dicts the host readers return for the same files, entry by entry (dropped ones left out), with
+    the peaks of every entry sorted by m/z as `raw_csr` sorts them"""
+    out = []
+    for c in chunks:
+        host = [np.asarray(a.cpu() if hasattr(a, "cpu") else a) for a in (c.indptr, c.mz, c.intensity)]
+        indptr, mz, it = host
+        for i in np.flatnonzero(~c.dropped):
+            s = {k: v[i].item() for k, v in c.columns.items()}
+            s.update(mz=mz[indptr[i]:indptr[i + 1]], intensity=it[indptr[i]:indptr[i + 1]], filename=c.filename)
+            out.append(s)
+    return out
+
+
+def _text_column(ctx, buf, d_text, span, column: int = 0) -> np.ndarray:
+    """the byte ranges span[:, column] (device i64[n, k, 2] or host i64[n, 2]) of a stretch -> str array: `ctx.text_rows` rows of
+    the longest range's width, at most `_TITLE_WIDTH`; the few longer ones are taken from the host's copy `buf` one by one"""
+    n = len(span)
+    if n == 0:
+        return np.zeros(0, dtype=str)
+    span = ctx.to_dev(span)
+    view = span[:, column] if span.dim() == 3 else span
+    w = int(min(max(int((view[:, 1] - view[:, 0]).max().item()), 1), _TITLE_WIDTH))
+    rows, long = ctx.text_rows(d_text, span, column, w)
+    out = np.ascontiguousarray(rows.cpu().numpy()).view(f"S{w}").reshape(n).astype(f"U{w}")
+    at = long.nonzero().reshape(-1)
+    if len(at):
+        out = out.astype(object)
+        for i, (a, b) in zip(at.cpu().numpy(), view[at].cpu().numpy()):
+            out[i] = bytes(buf[a:b]).decode("ascii")
+        out = np.array(list(out), dtype=str)
+    return out
+
+
+def _host_entry_chunk(specs, extra, fn) -> EntryChunk:
+    """the dicts of entries the host rule read -> an EntryChunk of host arrays; `extra`: (column, dtype) of the reader's own"""
+    mz, it, indptr = raw_csr(specs)
+    cols = dict(identifier=np.array([str(s["identifier"]) for s in specs], dtype=str),
+                precursor_mz=np.array([s["precursor_mz"] for s in specs], np.float64),
+                precursor_charge=np.array([int(s["precursor_charge"]) if s.get("precursor_charge") else 0 for s in specs], np.int32),
+                retention_time=np.array([s["retention_time"] for s in specs], np.float64))
+    cols.update({k: np.array([s[k] for s in specs], dtype=dt) for k, dt in extra})
+    return EntryChunk(indptr, mz, it, cols, np.zeros(len(specs), bool), len(specs), "host", fn)
+
+
+_ANNOTATION_COLUMNS = tuple((k, str) for k in ("name",) + ANNOTATION_KEYS)
+
+
+def read_annotation_chunks(filenames, ctx, counts: Optional[dict] = None, max_bytes: int = DEFAULT_CHUNK_BYTES) -> list:
+    """`read_annotation_library` on the device: every file's stretches (`_stretches`) through `ctx.parse_mgf` with the title
+    optional and `LIBRARY_KEYS`, the string columns through `ctx.text_rows`, the skip and fall-through rules of
+    `_annotation_entry` applied to whole columns.  An entry with status HOST or a HOST key is read again from its own bytes by
+    `_annotation_entries`; a stretch outside the device grammar hands the rest of its file to that rule, the entry number
+    carried over.  -> EntryChunks, the peaks left on the device; `counts` as the host reader's, plus `host`: the entries the
+    host rule read."""
+    from .._lib import MGF_KEY_HOST, MGF_ST_HOST
+    chunks, n_entries, n_skipped, n_host = [], 0, 0, 0
+    for fn in filenames:
+        entry = 0
+        for head, res in _stretches(fn, ctx, max_bytes, optional_title=True, keys=LIBRARY_KEYS):
+            if head is None:
+                specs = []
+                for entry, spec in _annotation_entries(res, fn, entry):
+                    n_host += 1
+                    if spec is None:
+                        n_skipped += 1
+                    else:
+                        specs.append(spec)
+                if specs:
+                    chunks.append(_host_entry_chunk(specs, _ANNOTATION_COLUMNS, fn))
+                break
+            n = len(res["status"])
+            number = entry + 1 + np.arange(n)
+            entry += n
+            state = res["key_state"]
+            text = {k: _text_column(ctx, head, res["text"], res["key_span"], j) for j, k in enumerate(LIBRARY_KEYS)}
+            title = _text_column(ctx, head, res["text"], res["title"])
+            # `a or b or c` of the host rule, on columns (an absent key has the range (0, 0): the empty string)
+            ident = np.where(text["spectrumid"] != "", text["spectrumid"], title)
+            cols = dict(identifier=ident, precursor_mz=res["precursor_mz"].copy(),
+                        precursor_charge=np.where(res["has_charge"], res["charge"], 0).astype(np.int32),
+                        retention_time=np.full(n, -1.0), name=np.where(text["name"] != "", text["name"], text["compound_name"]),
+                        **{k: text[k] for k in ANNOTATION_KEYS})
+            dropped = ~(cols["precursor_mz"] > 0.0)          # (a decided PEPMASS is finite)
+            host = np.flatnonzero((res["status"] == MGF_ST_HOST) | (state == MGF_KEY_HOST).any(axis=1))
+            unnamed = np.flatnonzero(ident == "")
+            if len(host) or len(unnamed):                    # (strings of any length are patched in: object columns meanwhile)
+                for k in ("identifier", "name") + ANNOTATION_KEYS:
+                    cols[k] = cols[k].astype(object)
+                for i in unnamed:
+                    cols["identifier"][i] = f"{os.path.basename(fn)}:{number[i]}"
+            if len(host):
+                indptr = res["indptr"].cpu().numpy()
+                pos, mzs, its = [], [], []
+                for i in host:
+                    a, b = res["span"][i]
+                    (_, s), = _annotation_entries(io.StringIO(bytes(head[a:b]).decode("ascii")), fn, int(number[i]) - 1)
+                    dropped[i] = s is None
+                    if s is None:
+                        continue
+                    size = int(indptr[i + 1] - indptr[i])
+                    if len(s["mz"]) != size:
+                        raise RuntimeError(f"MGF entry at bytes {a}-{b}: {size} peak lines on the device, {len(s['mz'])} on the host")
+                    order = np.argsort(s["mz"], kind="stable")
+                    pos.append(np.arange(indptr[i], indptr[i + 1]))
+                    mzs.append(s["mz"][order])
+                    its.append(s["intensity"][order])
+                    for k in cols:
+                        cols[k][i] = s[k]
+                _patch_peaks(res, pos, mzs, its)
+            for k in ("identifier", "name") + ANNOTATION_KEYS:
+                cols[k][dropped] = ""
+                if cols[k].dtype == object:
+                    cols[k] = np.array(list(cols[k]), dtype=str)
+            cols["precursor_mz"][dropped], cols["precursor_charge"][dropped] = 0.0, 0
+            n_skipped, n_host = n_skipped + int(dropped.sum()), n_host + len(host)
+            chunks.append(EntryChunk(res["indptr"], res["mz"], res["intensity"], cols, dropped, len(host), "device", fn))
+        n_entries += entry
+    if counts is not None:
+        counts.update(entries=n_entries, skipped=n_skipped, host=n_host)
+    return chunks
+
+
+def _host_library_entries(lines, fn, entry: int):
+    """`get_library_spectra`'s rule over the text `lines` of file `fn` without its errors -> (entry number, `get_spectra`'s dict
+    with `cluster`: the stripped value of the last CLUSTER= line or None; None for an entry `get_spectra` rejects)"""
+    block, inside = [], False
+    for line in lines:
+        t = line.strip()
+        if t == "BEGIN IONS":
+            block, inside = [line], True
+            continue
+        if not inside:
+            continue
+        block.append(line)
+        if t != "END IONS":
+            continue
+        inside = False
+        entry += 1
+        got = list(get_spectra(io.StringIO("".join(block))))
+        if len(got) != 1:
+            yield entry, None
+            continue
+        value = None
+        for l in block[1:-1]:
+            l = l.strip()
+            if l and l[0] not in "#;!/" and "=" in l and not (l[0].isdigit() or l[0] == "."):
+                k, v = l.split("=", 1)
+                if k.strip().lower() == "cluster":
+                    value = v.strip()
+        got[0]["cluster"] = value
+        yield entry, got[0]
+
+
+def read_library_chunks(filenames, ctx, counts: Optional[dict] = None, max_bytes: int = DEFAULT_CHUNK_BYTES) -> list:
+    """`read_library` on the device: every file's stretches (`_stretches`) through `ctx.parse_mgf` (title required, as
+    `get_spectra`) with the key `cluster` as an integer; spectra with status HOST are read again by `get_spectra`
+    (`_device_chunk`), a CLUSTER= value outside the integer fast form goes to `int()`.  The problems -- an accepted entry
+    without CLUSTER=, with a value that is no integer, or with an id an earlier entry holds -- are found on whole columns; the
+    first one in file order raises MgfLibraryError with the host reader's message.  A stretch outside the device grammar
+    hands the rest of its file to the host rule, the entry number carried over.  -> EntryChunks with the column `cluster`
+    (`precursor_charge` 0: none); `counts` receives `entries` and `host`, the entries the host rule read."""
+    from .._lib import MGF_KEY_ABSENT, MGF_KEY_INT, MGF_KEY_PRESENT
+    chunks, n_host, n_entries = [], 0, 0
+    seen_ids, seen_where = np.zeros(0, np.int64), []          # every id so far; per stretch (file, its first id's place, identifiers)
+    for fn in filenames:
+        entry = accepted = 0
+        for head, res in _stretches(fn, ctx, max_bytes, keys={"cluster": MGF_KEY_INT}):
+            if head is None:
+                got = list(_host_library_entries(res, fn, entry))
+                entry = got[-1][0] if got else entry
+                got = [(e, s) for e, s in got if s is not None]
+                specs = [s for _, s in got]
+                chunk = _host_entry_chunk(specs, (), fn)
+                number, ids = np.array([e for e, _ in got], np.int64), np.zeros(len(got), np.int64)
+                values = {i: s["cluster"] for i, s in enumerate(specs)}           # every value through int(); None: no CLUSTER= line
+            else:
+                n = len(res["status"])
+                number = entry + 1 + np.arange(n)
+                entry += n
+                c = _device_chunk(ctx, head, res)
+                chunk = EntryChunk(c.indptr, c.mz, c.intensity, dict(identifier=c.identifier, precursor_mz=c.precursor_mz,
+                                                                    precursor_charge=c.precursor_charge, retention_time=c.retention_time),
+                                   c.dropped, c.n_host, "device", fn)
+                state, span, ids = res["key_state"][:, 0], res["key_span"].cpu().numpy()[:, 0], res["key_value"][:, 0].copy()
+                decided = (state == MGF_KEY_PRESENT) & (span[:, 1] > span[:, 0])
+                values = {int(i): None if state[i] == MGF_KEY_ABSENT else bytes(head[span[i, 0]:span[i, 1]]).decode("ascii")
+                          for i in np.flatnonzero(~decided & ~c.dropped)}
+            n_host += chunk.n_host
+            ident, rows = chunk.columns["identifier"], np.flatnonzero(~chunk.dropped)
+            problem = None                                                        # (row, message): the first one in file order
+            for i in sorted(values):
+                where = f"{fn}: entry {number[i]} (TITLE={ident[i]})"
+                if values[i] is None:
+                    problem = (i, f"{where} has no CLUSTER= line: not a file of cluster representatives")
+                    break
+                try:
+                    ids[i] = int(values[i])
+                except ValueError:
+                    problem = (i, f"{where}: CLUSTER={values[i]} is not an integer")
+                    break
+            good = rows if problem is None else rows[rows < problem[0]]
+            both = np.concatenate([seen_ids, ids[good]])
+            _, first, inverse = np.unique(both, return_index=True, return_inverse=True)
+            repeat = np.flatnonzero(first[inverse] != np.arange(len(both)))
+            if len(repeat):
+                i, holder = int(good[repeat[0] - len(seen_ids)]), int(first[inverse[repeat[0]]])
+                if holder >= len(seen_ids):
+                    held = f"{fn} (TITLE={ident[good[holder - len(seen_ids)]]})"
+                else:
+                    held = next(f"{f} (TITLE={names[holder - at]})" for f, at, names in reversed(seen_where) if at <= holder)
+                k = accepted + int(np.searchsorted(rows, i))
+                problem = (i, f"{fn}: spectrum {k + 1} (TITLE={ident[i]}) repeats CLUSTER={ids[i]} of {held}")
+            if problem is not None:
+                raise MgfLibraryError(problem[1])
+            seen_where.append((fn, len(seen_ids), ident[rows]))
+            seen_ids, accepted = both, accepted + len(rows)
+            chunk.columns["cluster"] = np.where(chunk.dropped, 0, ids)
+            if len(chunk):
+                chunks.append(chunk)
+        n_entries += entry
+    if counts is not None:
+        counts.update(entries=n_entries, host=n_host)
+    return chunks
 
 
 def write_spectra(filename: str, spectra: Iterable[Dict]) -> None:

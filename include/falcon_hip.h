@@ -487,6 +487,49 @@ int fal_mgf_parse(fal_ctx* ctx, const uint8_t* text, int64_t n_bytes, int64_t n_
                   int64_t* out_indptr, double* out_mz, float* out_intensity, double* precursor_mz, int32_t* charge,
                   int32_t* has_charge, double* retention_time, int64_t* title, int64_t* span, int32_t* status_out);
 
+/* ---- MGF header values by a key table, and byte ranges as fixed-width rows (the library and representative readers; DESIGN.md
+ *          "MGF on the device" states the key rule; falcon_amd/ms_io/mgf_io.py holds the host readers they mirror).
+ * fal_mgf_parse_ex: fal_mgf_parse with optional_keys, a set of FAL_MGF_OPT_* bits (any other bit: FAL_EINVAL).  FAL_MGF_OPT_TITLE:
+ *          a spectrum without TITLE is not HOST on that account, its title range is (0, 0).  fal_mgf_parse is the call with 0.
+ * fal_mgf_headers: a third consumer of the index fal_mgf_index left in the context, with fal_mgf_parse's handle check (FAL_EINVAL
+ *          for another text, length or spectrum count, and after fal_ctx_trim); it may run before or after fal_mgf_parse.
+ *          The table (host): keys u8 back to back with key_ptr i64[n_keys + 1], key k = keys[key_ptr[k], key_ptr[k + 1]); key_kind
+ *          i32[n_keys]: FAL_MGF_KEY_SPAN or FAL_MGF_KEY_INT.  1 <= n_keys <= FAL_MGF_MAX_KEYS; a key has 1 to FAL_MGF_MAX_KEY_BYTES
+ *          bytes of stripped lower-case printable ASCII without '=', is none of title / pepmass / charge / rtinseconds and
+ *          appears once; anything else: FAL_EINVAL, nothing written.
+ *          For every spectrum s of the index and every key k, from the spectrum's LAST header line whose key -- what stands before
+ *          the first '=', stripped, compared without case -- equals the table's ("SMILES=C=O" has the value "C=O", "NAMES=" is
+ *          not "name", "1=2" is a peak line):
+ * -> span_out i64[n][n_keys][2]: the stripped value's byte range [from, to) in the text, (0, 0) when absent; value_out
+ *    i64[n][n_keys]: for a decided FAL_MGF_KEY_INT key the integer of the fast form [+-]?D{1,18}, else 0; state_out
+ *    i32[n][n_keys]: FAL_MGF_KEY_ABSENT, FAL_MGF_KEY_PRESENT (an empty value is present with from == to and the value 0), or
+ *    FAL_MGF_KEY_HOST -- the host reads the value from its range: that line is longer than 4096 bytes, or the key is an INT key
+ *    and its non-empty value is outside the fast form ("1_0", "1 2", 19 digits, "0x5": Python's int() decides, never a guess).
+ *          No synchronisation.  Malformed text never makes the call fail or write outside n * n_keys entries.
+ * fal_text_rows: rows_out u8[n][width] (device) = the bytes of range k = span[(k * stride + column) * 2 + {0, 1}] (device, i64:
+ *          [from, to) in text u8[n_bytes], which needs no alignment), zero-padded to width, 1 <= width <= FAL_TEXT_MAX_WIDTH;
+ *          long_out i32[n] = 1 where the range is longer than width (the row then holds its first width bytes).  A range
+ *          outside [0, n_bytes] or with to < from gives a zero row and, behind the launch, FAL_EINVAL; nothing is read outside
+ *          the text.  One stream synchronisation.  No host work per line or per row. ----------------------------------- [dev] */
+#define FAL_MGF_OPT_TITLE     1
+#define FAL_MGF_MAX_KEYS      16
+#define FAL_MGF_MAX_KEY_BYTES 32
+#define FAL_MGF_KEY_SPAN      0
+#define FAL_MGF_KEY_INT       1
+#define FAL_MGF_KEY_ABSENT    0
+#define FAL_MGF_KEY_PRESENT   1
+#define FAL_MGF_KEY_HOST      2
+#define FAL_TEXT_MAX_WIDTH    256
+int fal_mgf_parse_ex(fal_ctx* ctx, const uint8_t* text, int64_t n_bytes, int64_t n_spectra, int64_t nnz_cap,
+                     int64_t* out_indptr, double* out_mz, float* out_intensity, double* precursor_mz, int32_t* charge,
+                     int32_t* has_charge, double* retention_time, int64_t* title, int64_t* span, int32_t* status_out,
+                     int optional_keys);
+int fal_mgf_headers(fal_ctx* ctx, const uint8_t* text, int64_t n_bytes, int64_t n_spectra, const uint8_t* keys,
+                    const int64_t* key_ptr, const int32_t* key_kind, int n_keys, int64_t* span_out, int64_t* value_out,
+                    int32_t* state_out);
+int fal_text_rows(fal_ctx* ctx, const uint8_t* text, int64_t n_bytes, const int64_t* span, int64_t stride, int64_t column,
+                  int64_t n, int width, uint8_t* rows_out, int32_t* long_out);
+
 /* ---- peak CSR + per-entry columns -> MGF text (the device writer; DESIGN.md "MGF out of the device" states the layout and the
  *          number form; falcon_amd/ms_io/mgf_io.write_spectra is the writer it mirrors: for the same entries the bytes are equal).
  * mz / intensity f32[nnz], indptr i64[n_rows + 1]: the peaks; rows i32[n]: the CSR row whose peaks entry k carries (any order,
