@@ -491,14 +491,16 @@ int launch_assign16(fal_ctx* ctx, int stage, const void* X16, const float* X, co
                     int64_t merge_rows) {
     if (n_single + n_merge <= 0) return FAL_OK;
     // work lists of the exact kernels: a row enters at most one of them once per pass, so n_rows entries never overflow
-    int32_t* amb = nullptr;
     const int amb_cap = (int)std::max<int64_t>(n_rows, 1);
-    FAL_TRY(ctx->reserve(SLOT_FUSED, sizeof(int32_t) * (size_t)(9 * (size_t)amb_cap + 16), (void**)&amb));
+    ScratchLayout L;
+    const auto amb = L.array<int32_t>(16);                 // the count, in front
+    const auto amb_list = L.array<int32_t>(5 * (int64_t)amb_cap), pair_list = L.array<int32_t>(4 * (int64_t)amb_cap);
+    FAL_TRY(L.reserve(ctx, SLOT_FUSED));
     FAL_CHECK_HIP(hipMemsetAsync(amb, 0, sizeof(int32_t) * 16, ctx->stream));
     Assign16Args a{};
     a.X16 = reinterpret_cast<const __half*>(X16); a.C16 = reinterpret_cast<const __half*>(C16);
-    a.jobs = jobs; a.n_jobs = n_single; a.assign = assign; a.amb_list = amb + 16; a.amb_count = amb; a.amb_cap = amb_cap;
-    a.pair_list = amb + 16 + 5 * (size_t)amb_cap; a.ckeys = ckeys; a.ckeys_stride = ckeys_stride; a.n = std::max<int64_t>(merge_rows, 1);
+    a.jobs = jobs; a.n_jobs = n_single; a.assign = assign; a.amb_list = amb_list; a.amb_count = amb; a.amb_cap = amb_cap;
+    a.pair_list = pair_list; a.ckeys = ckeys; a.ckeys_stride = ckeys_stride; a.n = std::max<int64_t>(merge_rows, 1);
     a.sp_cols = sp_cols; a.sp_vals = sp_vals;
     StageScope ts(ctx, stage);
     const dim3 block(256);
@@ -523,14 +525,16 @@ int launch_assign16(fal_ctx* ctx, int stage, const void* X16, const float* X, co
     };
     if (n_single > 0) FAL_TRY(run(false));
     if (n_merge > 0) {
-        float* part = nullptr;
         const size_t n_sub = 4 * (size_t)std::max(1, (merge_max_lists + kAssignGroup - 1) / kAssignGroup);      // four per group job, whole groups
         FAL_REQUIRE(merge_max_lists <= kAssignMergeLists, FAL_EINTERNAL, "assign16: a merge job with %d lists", merge_max_lists);
         // (sized by the rows of the MERGE buckets -- AssignJob::part0 --, not by the partition's: one 2,048-list bucket among 10 M
         // rows asked for 7.7 GB)
         const size_t n_part = (size_t)a.n;
-        FAL_TRY(ctx->reserve(SLOT_PROBE_SIM, sizeof(float) * 3 * n_sub * n_part, (void**)&part));
-        a.part_b = part; a.part_s = part + n_sub * n_part; a.part_id = reinterpret_cast<int32_t*>(part + 2 * n_sub * n_part);
+        ScratchLayout LP;
+        const auto part_b = LP.array<float>((int64_t)(n_sub * n_part)), part_s = LP.array<float>((int64_t)(n_sub * n_part));
+        const auto part_id = LP.array<int32_t>((int64_t)(n_sub * n_part));
+        FAL_TRY(LP.reserve(ctx, SLOT_PROBE_SIM));
+        a.part_b = part_b; a.part_s = part_s; a.part_id = part_id;
         a.jobs = jobs + n_single + n_merge; a.n_jobs = n_group;
         FAL_TRY(run(true));
         a.mjobs = jobs + n_single; a.n_mjobs = n_merge;

@@ -180,14 +180,12 @@ extern "C" int fal_assign_nearest(fal_ctx* ctx, const float* q_mz, const float* 
     FAL_REQUIRE(!(rt_tol >= 0.0) || nl == 0 || (q_rt && l_rt), FAL_EINVAL,
                 "fal_assign_nearest: a retention-time tolerance needs the retention times of both sides");
     hipStream_t st = ctx->stream;
-    // one block: keys u64[nq] | q_order i64[nq] | l_order i64[nl] | q_pmz f32[nq] | l_pmz f32[nl]
-    unsigned char* blk = nullptr;
-    FAL_TRY(ctx->reserve(SLOT_ASSIGN, (size_t)(2 * nq + nl) * 8 + (size_t)(nq + nl) * 4 + 64, (void**)&blk));
-    unsigned long long* keys = reinterpret_cast<unsigned long long*>(blk);
-    int64_t* q_order = reinterpret_cast<int64_t*>(keys + nq);
-    int64_t* l_order = q_order + nq;
-    float* q_pmzs = reinterpret_cast<float*>(l_order + nl);
-    float* l_pmzs = q_pmzs + nq;
+    ScratchLayout L;
+    const auto keys = L.array<unsigned long long>(nq);
+    const auto q_order = L.array<int64_t>(nq), l_order = L.array<int64_t>(nl);
+    const auto q_pmzs = L.array<float>(nq), l_pmzs = L.array<float>(nl);
+    L.pad(64);
+    FAL_TRY(L.reserve(ctx, SLOT_ASSIGN));
     int32_t* misc = nullptr;                                     // [0] error word, [2..3] fallback pairs
     FAL_TRY(ctx->reserve(SLOT_EXACT5, 64, (void**)&misc));
     unsigned long long* d_fb = reinterpret_cast<unsigned long long*>(misc + 2);

@@ -744,17 +744,20 @@ __global__ void tile_job_c16_kernel(const DenseJob* __restrict__ jobs, int n_job
 int launch_coarse16(fal_ctx* ctx, const Coarse16Args& a_in) {
     if (a_in.n_tiles <= 0) return FAL_OK;
     Coarse16Args a = a_in;
-    int32_t* tj = nullptr;
     ctx->release(SLOT_TILEJOB);        // a launcher-local table: the previous launcher's pointer is dead
-    FAL_TRY(ctx->reserve(SLOT_TILEJOB, sizeof(int32_t) * (size_t)(std::max<int64_t>(a.n_tiles, 1 << 16) + 32 * a.n_tiles + 64), (void**)&tj));
+    ScratchLayout L;
+    const auto tj = L.array<int32_t>(std::max<int64_t>(a.n_tiles, 1 << 16));
+    // the queries the wave-level kernel hands over (count in front), behind the tile table
+    const auto ovf_count = L.array<int32_t>(16), ovf_list = L.array<int32_t>(32 * a.n_tiles);
+    L.pad(192);
+    FAL_TRY(L.reserve(ctx, SLOT_TILEJOB));
     StageScope ts(ctx, ST_COARSE);
     hipLaunchKernelGGL(tile_job_c16_kernel, dim3((unsigned)ceil_div(a.n_tiles, 256)), dim3(256), 0, ctx->stream, a.jobs, a.n_jobs,
                        a.n_tiles, tj);
     a.tile_job = tj;
     FAL_REQUIRE(a.n_tiles * 4 < (int64_t)INT32_MAX, FAL_EUNSUPPORTED, "too many queries in one coarse launch");
-    // the queries the wave-level kernel hands over (count in front), behind the tile table
-    a.ovf_count = tj + std::max<int64_t>(a.n_tiles, 1 << 16);
-    a.ovf_list = a.ovf_count + 16;
+    a.ovf_count = ovf_count;
+    a.ovf_list = ovf_list;
     a.ovf_cap = (int)std::min<int64_t>(32 * a.n_tiles, INT32_MAX);
     FAL_CHECK_HIP(hipMemsetAsync(a.ovf_count, 0, sizeof(int32_t), ctx->stream));
     const unsigned list_grid = (unsigned)std::min<int64_t>(a.n_tiles * 4, (int64_t)ctx->num_cus * 16);

@@ -7,6 +7,7 @@
 #include <string>
 #include <vector>
 #include "../../include/falcon_hip.h"
+#include "scratch.h"
 
 namespace fal {
 

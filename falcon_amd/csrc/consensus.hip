@@ -306,27 +306,17 @@ extern "C" int fal_consensus_spectra(fal_ctx* ctx, const float* mz, const float*
     const int64_t n1 = std::max<int64_t>(n, 1), nc = n_clusters;
 
     // ---- rows by (label, row); the pool offset of every member and cluster ---------------------------------------------------
-    uint32_t *key_in = nullptr, *key = nullptr;
-    int32_t *row_in = nullptr, *row = nullptr, *mcount = nullptr, *kept_count = nullptr;
-    int64_t *pool_off = nullptr, *cstart = nullptr, *cpool = nullptr, *big_size = nullptr, *big_off = nullptr, *out_count = nullptr;
-    {
-        unsigned char* a = nullptr;
-        FAL_TRY(ctx->reserve(SLOT_TAIL, (size_t)n1 * 20 + 64, (void**)&a));
-        key_in = (uint32_t*)a;
-        key = key_in + n1;
-        row_in = (int32_t*)(key + n1);
-        row = row_in + n1;
-        mcount = row + n1;
-        FAL_TRY(ctx->reserve(SLOT_TAIL2, sizeof(int64_t) * (size_t)(n + 2), (void**)&pool_off));
-        int64_t* b = nullptr;
-        FAL_TRY(ctx->reserve(SLOT_TAIL3, sizeof(int64_t) * (size_t)(5 * (nc + 1)) + sizeof(int32_t) * (size_t)nc, (void**)&b));
-        cstart = b;
-        cpool = cstart + nc + 1;
-        big_size = cpool + nc + 1;
-        big_off = big_size + nc + 1;
-        out_count = big_off + nc + 1;
-        kept_count = (int32_t*)(out_count + nc + 1);
-    }
+    ScratchLayout LA, LB, LP;
+    const auto key_in = LA.array<uint32_t>(n1), key = LA.array<uint32_t>(n1);
+    const auto row_in = LA.array<int32_t>(n1), row = LA.array<int32_t>(n1), mcount = LA.array<int32_t>(n1);
+    LA.pad(64);
+    FAL_TRY(LA.reserve(ctx, SLOT_TAIL));
+    int64_t* pool_off = nullptr;
+    FAL_TRY(ctx->reserve(SLOT_TAIL2, sizeof(int64_t) * (size_t)(n + 2), (void**)&pool_off));
+    const auto cstart = LB.array<int64_t>(nc + 1), cpool = LB.array<int64_t>(nc + 1), big_size = LB.array<int64_t>(nc + 1);
+    const auto big_off = LB.array<int64_t>(nc + 1), out_count = LB.array<int64_t>(nc + 1);
+    const auto kept_count = LB.array<int32_t>(nc);
+    FAL_TRY(LB.reserve(ctx, SLOT_TAIL3));
     if (n > 0) {
         hipLaunchKernelGGL(cons_label_keys_kernel, grid_for(n), dim3(kConsBlock), 0, s, labels, n, key_in, row_in);
         FAL_CHECK_HIP(hipGetLastError());
@@ -356,20 +346,13 @@ extern "C" int fal_consensus_spectra(fal_ctx* ctx, const float* mz, const float*
                 (long long)nnz);
 
     // ---- pool, sort every cluster's pool, groups --------------------------------------------------------------------------------
-    int32_t *pool_peak = nullptr, *pool_cluster = nullptr;
-    float *smz = nullptr, *sint = nullptr, *gmz = nullptr;
-    double* graw = nullptr;
-    uint8_t* kept = nullptr;
+    const auto graw = LP.array<double>(pooled);
+    const auto pool_peak = LP.array<int32_t>(pooled), pool_cluster = LP.array<int32_t>(pooled);
+    const auto smz = LP.array<float>(pooled), sint = LP.array<float>(pooled), gmz = LP.array<float>(pooled);
+    const auto kept = LP.array<uint8_t>(pooled);
+    LP.pad(64);
     if (pooled > 0) {
-        unsigned char* a = nullptr;
-        FAL_TRY(ctx->reserve(SLOT_DB, (size_t)pooled * 29 + 64, (void**)&a));
-        graw = (double*)a;
-        pool_peak = (int32_t*)(graw + pooled);
-        pool_cluster = pool_peak + pooled;
-        smz = (float*)(pool_cluster + pooled);
-        sint = smz + pooled;
-        gmz = sint + pooled;
-        kept = (uint8_t*)(gmz + pooled);
+        FAL_TRY(LP.reserve(ctx, SLOT_DB));
         hipLaunchKernelGGL(cons_pool_kernel, grid_for(pooled), dim3(kConsBlock), 0, s, pool_off, key, row, n, pooled, indptr, pool_peak,
                            pool_cluster);
         FAL_CHECK_HIP(hipGetLastError());
@@ -377,10 +360,10 @@ extern "C" int fal_consensus_spectra(fal_ctx* ctx, const float* mz, const float*
         hipLaunchKernelGGL(cons_sort_lds_kernel, dim3(wgs), dim3(kConsBlock), 0, s, cstart, cpool, nc, pool_peak, mz, intensity, smz, sint);
         FAL_CHECK_HIP(hipGetLastError());
         if (n_big > 0) {
-            uint32_t* k0 = nullptr;
-            FAL_TRY(ctx->reserve(SLOT_DB2, sizeof(uint32_t) * 4 * (size_t)n_big, (void**)&k0));
-            uint32_t* k1 = k0 + n_big;
-            int32_t *v0 = (int32_t*)(k1 + n_big), *v1 = v0 + n_big;
+            ScratchLayout LK;
+            const auto k0 = LK.array<uint32_t>(n_big), k1 = LK.array<uint32_t>(n_big);
+            const auto v0 = LK.array<int32_t>(n_big), v1 = LK.array<int32_t>(n_big);
+            FAL_TRY(LK.reserve(ctx, SLOT_DB2));
             hipLaunchKernelGGL(cons_big_keys_kernel, grid_for(n_big), dim3(kConsBlock), 0, s, big_off, cpool, nc, n_big, pool_peak, mz, k0, v0);
             FAL_CHECK_HIP(hipGetLastError());
             ctx->release(SLOT_SORT);

@@ -155,11 +155,13 @@ extern "C" int fal_csv_order(fal_ctx* ctx, const int32_t* file_rank, const uint8
     const CsvRowLess less{file_rank, id, id_ptr, n};
     size_t sort_bytes = 0;
     FAL_CHECK_HIP(rocprim::merge_sort<CsvSortConfig>(nullptr, sort_bytes, (int32_t*)nullptr, order_out, (size_t)n, less, ctx->stream));
-    const size_t iota_at = 256, sort_at = iota_at + (((size_t)n * sizeof(int32_t) + 255) & ~(size_t)255);
-    unsigned char* scratch = nullptr;
-    FAL_TRY(ctx->reserve(SLOT_CSVW, sort_at + sort_bytes, (void**)&scratch));
-    unsigned long long* meta = (unsigned long long*)scratch;
-    int32_t* iota = (int32_t*)(scratch + iota_at);
+    ScratchLayout L;                                        // every part on a 256-byte step
+    const auto meta = L.array<unsigned long long>(8);
+    L.align(256);
+    const auto iota = L.array<int32_t>(n);
+    L.align(256);
+    const auto sort_tmp = L.array<unsigned char>((int64_t)sort_bytes);
+    FAL_TRY(L.reserve(ctx, SLOT_CSVW));
     FAL_CHECK_HIP(hipMemsetAsync(meta, 0, 64, ctx->stream));
     hipLaunchKernelGGL(csv_check_ids_kernel, dim3(capped_grid(ctx, n, 256)), dim3(256), 0, ctx->stream, id, id_ptr, id_bytes, n, iota, meta);
     FAL_CHECK_HIP(hipGetLastError());
@@ -167,7 +169,7 @@ extern "C" int fal_csv_order(fal_ctx* ctx, const int32_t* file_rank, const uint8
     FAL_TRY(read_meta(ctx, meta, &h));
     FAL_REQUIRE(!(h[META_FLAGS] & TW_BAD_INPUT), FAL_EINVAL, "fal_csv_order: id_ptr not ascending inside the id blob");
     *max_digit_run_out = (int64_t)h[META_DIGITS];
-    FAL_CHECK_HIP(rocprim::merge_sort<CsvSortConfig>(scratch + sort_at, sort_bytes, iota, order_out, (size_t)n, less, ctx->stream));
+    FAL_CHECK_HIP(rocprim::merge_sort<CsvSortConfig>(sort_tmp, sort_bytes, iota.get(), order_out, (size_t)n, less, ctx->stream));
     return FAL_OK;
 }
 

@@ -182,12 +182,11 @@ int exact_medoids_dev(fal_ctx* ctx, const ExactPeaks& pk, const int32_t* labels_
                       unsigned long long* best) {
     hipStream_t st = ctx->stream;
     const int64_t cmax = n + 1;
-    int64_t* off = nullptr;
-    FAL_TRY(ctx->reserve(SLOT_EXACT6, sizeof(int64_t) * (size_t)(cmax + 1) + sizeof(int32_t) * (size_t)(cmax + 2 * n + 8),
-                         (void**)&off));
-    int32_t* cursor = reinterpret_cast<int32_t*>(off + cmax + 1);
-    int32_t* mem = cursor + cmax;
-    int32_t* sorted = mem + n;
+    ScratchLayout L;
+    const auto off = L.array<int64_t>(cmax + 1);
+    const auto cursor = L.array<int32_t>(cmax), mem = L.array<int32_t>(n), sorted = L.array<int32_t>(n);
+    L.pad(32);
+    FAL_TRY(L.reserve(ctx, SLOT_EXACT6));
     const int grid = (int)std::min<int64_t>(ceil_div(n, 256), (int64_t)ctx->num_cus * 16);
     FAL_CHECK_HIP(hipMemsetAsync(cursor, 0, sizeof(int32_t) * (size_t)cmax, st));
     FAL_TRY(device_scan_i32(ctx, size, cmax, off, SLOT_TAIL3));
@@ -240,10 +239,12 @@ static int exact_edges_dev(fal_ctx* ctx, const ExactPeaks& pk_in, int64_t n, con
     pk.err = out->d_err;
     const int64_t cap0 = std::max<int64_t>(1, std::min<int64_t>(total, kExEdgeBudget));
     auto reserve_edges = [&](int64_t cap) -> int {
-        void* p = nullptr;
-        FAL_TRY(ctx->reserve(SLOT_EXACT, (sizeof(uint64_t) + sizeof(double)) * 2 * (size_t)cap, &p));
-        out->keys = static_cast<uint64_t*>(p);
-        out->vals = reinterpret_cast<double*>(out->keys + 2 * cap);
+        ScratchLayout L;
+        const auto keys = L.array<uint64_t>(2 * cap);
+        const auto vals = L.array<double>(2 * cap);
+        FAL_TRY(L.reserve(ctx, SLOT_EXACT));
+        out->keys = keys;
+        out->vals = vals;
         out->cap = cap;
         return FAL_OK;
     };
@@ -307,14 +308,13 @@ static int read_err(fal_ctx* ctx, const int32_t* d_err, const char* what) {
 static int exact_csr_dev(fal_ctx* ctx, const ExEdges& ed, int64_t n, int64_t** ptr_out, int32_t** idx_out, double** dist_out) {
     hipStream_t st = ctx->stream;
     const int64_t m = 2 * ed.cap;
-    unsigned char* buf = nullptr;
-    FAL_TRY(ctx->reserve(SLOT_EXACT4, sizeof(int64_t) * (size_t)(n + 1) + sizeof(int32_t) * (size_t)(2 * n) +
-                                          (sizeof(int32_t) + sizeof(double)) * (size_t)m + 64, (void**)&buf));
-    int64_t* ptr = reinterpret_cast<int64_t*>(buf);
-    double* dist = reinterpret_cast<double*>(ptr + n + 1);
-    int32_t* deg = reinterpret_cast<int32_t*>(dist + m);
-    int32_t* cursor = deg + n;
-    int32_t* idx = cursor + n;
+    ScratchLayout L;
+    const auto ptr = L.array<int64_t>(n + 1);
+    const auto dist = L.array<double>(m);
+    const auto deg = L.array<int32_t>(n), cursor = L.array<int32_t>(n);      // one memset clears both
+    const auto idx = L.array<int32_t>(m);
+    L.pad(64);
+    FAL_TRY(L.reserve(ctx, SLOT_EXACT4));
     FAL_CHECK_HIP(hipMemsetAsync(deg, 0, sizeof(int32_t) * (size_t)(2 * n), st));
     const int egrid = (int)std::min<int64_t>(ceil_div(m, 256), (int64_t)ctx->num_cus * 32);
     hipLaunchKernelGGL(ex_degree_kernel, dim3(egrid), dim3(256), 0, st, ed.keys, ed.d_count, ed.cap, deg);
@@ -389,11 +389,12 @@ int fal_exact_edges(fal_ctx* ctx, const float* mz, const float* intensity, const
     FAL_REQUIRE(m == 0 || (csr_idx && csr_dist), FAL_EINVAL, "fal_exact_edges: NULL csr_idx / csr_dist");
     hipStream_t st = ctx->stream;
     // deterministic order: (row, col) keys are unique, a radix sort puts them in place
-    unsigned char* sb = nullptr;
-    FAL_TRY(ctx->reserve(SLOT_EXACT4, (sizeof(uint64_t) + sizeof(double)) * (size_t)m + sizeof(int32_t) * (size_t)n + 64, (void**)&sb));
-    uint64_t* kout = reinterpret_cast<uint64_t*>(sb);
-    double* vout = reinterpret_cast<double*>(kout + m);
-    int32_t* deg = reinterpret_cast<int32_t*>(vout + m);
+    ScratchLayout L;
+    const auto kout = L.array<uint64_t>(m);
+    const auto vout = L.array<double>(m);
+    const auto deg = L.array<int32_t>(n);
+    L.pad(64);
+    FAL_TRY(L.reserve(ctx, SLOT_EXACT4));
     if (m > 0) FAL_TRY(sort_pairs_u64_f64(ctx, ed.keys, kout, ed.vals, vout, m, SLOT_EXACT6));
     const int egrid = (int)std::min<int64_t>(ceil_div(std::max<int64_t>(m, 1), 256), (int64_t)ctx->num_cus * 32);
     FAL_CHECK_HIP(hipMemsetAsync(deg, 0, sizeof(int32_t) * (size_t)n, st));

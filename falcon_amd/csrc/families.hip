@@ -144,25 +144,21 @@ extern "C" int fal_network_families(fal_ctx* ctx, const int32_t* edge_u, const i
         return FAL_OK;
     }
     hipStream_t st = ctx->stream;
-    // SLOT_FAM: misc 64 B | rank i64[n + 1] | parent, root, size, flag i32[n] | lo u32[n] | round i32[m]
-    unsigned char* blk = nullptr;
-    FAL_TRY(ctx->reserve(SLOT_FAM, 64 + 8 * (size_t)(n + 1) + 20 * (size_t)n + 4 * (size_t)m, (void**)&blk));
-    int32_t* misc = reinterpret_cast<int32_t*>(blk);
-    unsigned long long* d_cut = reinterpret_cast<unsigned long long*>(blk + 8);
-    int64_t* rank = reinterpret_cast<int64_t*>(blk + 64);
-    int32_t* parent = reinterpret_cast<int32_t*>(rank + n + 1);
-    int32_t* root = parent + n;
-    int32_t* size = root + n;
-    int32_t* flag = size + n;
-    uint32_t* lo = reinterpret_cast<uint32_t*>(flag + n);
-    int32_t* round = reinterpret_cast<int32_t*>(lo + n);
+    fal::ScratchLayout L;
+    const auto misc = L.array<int32_t>(16);             // 64 B of meta words; the 64-bit cut lives in words 2 and 3
+    const auto rank = L.array<int64_t>(n + 1);
+    const auto parent = L.array<int32_t>(n), root = L.array<int32_t>(n), size = L.array<int32_t>(n), flag = L.array<int32_t>(n);
+    const auto lo = L.array<uint32_t>(n);
+    const auto round = L.array<int32_t>(m);
+    FAL_TRY(L.reserve(ctx, SLOT_FAM));
+    unsigned long long* d_cut = reinterpret_cast<unsigned long long*>(misc + 2);
     unsigned char* pin = nullptr;
     FAL_TRY(ctx->pinned_reserve(64, (void**)&pin));
     int32_t* h_misc = reinterpret_cast<int32_t*>(pin);
     unsigned long long* h_cut = reinterpret_cast<unsigned long long*>(pin + 8);
     int64_t* h_fam = reinterpret_cast<int64_t*>(pin + 16);
     const unsigned ngrid = capped_grid(ctx, n, kFamBlock), egrid = capped_grid(ctx, m, kFamBlock);
-    FAL_CHECK_HIP(hipMemsetAsync(blk, 0, 64, st));
+    FAL_CHECK_HIP(hipMemsetAsync(misc, 0, 64, st));
     if (m > 0) hipLaunchKernelGGL(fam_check_kernel, dim3(egrid), dim3(kFamBlock), 0, st, edge_u, edge_v, edge_sim, m, n, round, misc);
     int64_t rounds = 0;
     for (;;) {

@@ -874,23 +874,24 @@ int fused_prepare(fal_ctx* ctx, FusedArgs* ap, int64_t n_rows) {
     a.tol_f = float_le_bound(a.tol, a.is_da ? 1.0 : 1e6);
     a.rt_f = float_le_bound(a.rt_tol, 1.0);
     // hand-off buffers, indexed by sorted row
-    unsigned char* hand = nullptr;
-    const size_t per_row = sizeof(QThr) + (size_t)FAL_FUSED_MEM * 8 + (size_t)FAL_FUSED_KEEP * 8 + 8;
-    FAL_TRY(ctx->reserve(SLOT_FUSED3, per_row * (size_t)n_rows + 256, (void**)&hand));
-    a.thr = reinterpret_cast<QThr*>(hand);
-    a.gmem_v = reinterpret_cast<float*>(a.thr + n_rows);
-    a.gmem_id = reinterpret_cast<uint32_t*>(a.gmem_v + n_rows * FAL_FUSED_MEM);
-    a.gkept_u = a.gmem_id + n_rows * FAL_FUSED_MEM;
-    a.gkept_id = a.gkept_u + n_rows * FAL_FUSED_KEEP;
-    a.gkcnt = reinterpret_cast<int32_t*>(a.gkept_id + n_rows * FAL_FUSED_KEEP);
+    ScratchLayout LH, LF;
+    const auto thr = LH.array<QThr>(n_rows);
+    const auto gmem_v = LH.array<float>(n_rows * FAL_FUSED_MEM);
+    const auto gmem_id = LH.array<uint32_t>(n_rows * FAL_FUSED_MEM);
+    const auto gkept_u = LH.array<uint32_t>(n_rows * FAL_FUSED_KEEP), gkept_id = LH.array<uint32_t>(n_rows * FAL_FUSED_KEEP);
+    const auto gkcnt = LH.array<int32_t>(2 * n_rows);
+    LH.pad(256);
+    FAL_TRY(LH.reserve(ctx, SLOT_FUSED3));
+    a.thr = thr;          a.gmem_v = gmem_v;      a.gmem_id = gmem_id;
+    a.gkept_u = gkept_u;  a.gkept_id = gkept_id;  a.gkcnt = gkcnt;
     // fallback list: resolve_kernel pushes a query at most once, so n_rows entries can never overflow
-    int32_t* fb = nullptr;
     const int fb_cap = (int)std::max<int64_t>(n_rows, 1);
-    FAL_TRY(ctx->reserve(SLOT_FUSED, sizeof(int32_t) * (size_t)(2 * fb_cap + 16), (void**)&fb));
-    a.fb_count = fb;
-    a.fb_list = fb + 16;
+    const auto fb_count = LF.array<int32_t>(16), fb_list = LF.array<int32_t>(2 * (int64_t)fb_cap);
+    FAL_TRY(LF.reserve(ctx, SLOT_FUSED));
+    a.fb_count = fb_count;
+    a.fb_list = fb_list;
     a.fb_cap = fb_cap;
-    FAL_CHECK_HIP(hipMemsetAsync(fb, 0, sizeof(int32_t) * 16, ctx->stream));
+    FAL_CHECK_HIP(hipMemsetAsync(fb_count, 0, sizeof(int32_t) * 16, ctx->stream));
     return FAL_OK;
 }
 

@@ -301,11 +301,13 @@ int fal_neighbors_to_csr_mapped(fal_ctx* ctx, const int32_t* nb_idx, const float
 // a9 with the cluster count left on the device at *d_count_out (no host synchronisation)
 int fal::dbscan_dev(fal_ctx* ctx, const int32_t* nb_idx, const float* nb_dist, int64_t n, int k, float eps,
                     int32_t* labels, int64_t** d_count_out, const int32_t** extent_out, const int32_t* nb_count) {
-    int32_t* buf = nullptr;
     int64_t* rank = nullptr;
-    FAL_TRY(ctx->reserve(SLOT_DB, sizeof(int32_t) * (size_t)n * 5, (void**)&buf));
+    ScratchLayout L;
+    const auto core = L.array<int32_t>(n), parent = L.array<int32_t>(n), border = L.array<int32_t>(n), is_root = L.array<int32_t>(n);
+    const auto own_extent = L.array<int32_t>(n);
+    FAL_TRY(L.reserve(ctx, SLOT_DB));
     FAL_TRY(ctx->reserve(SLOT_DB2, sizeof(int64_t) * (size_t)(n + 1), (void**)&rank));
-    int32_t *core = buf, *parent = buf + n, *border = buf + 2 * n, *is_root = buf + 3 * n, *extent = buf + 4 * n;
+    int32_t* extent = own_extent;
     const int grid = (int)std::min<int64_t>(ceil_div(n, 256), (int64_t)ctx->num_cus * 16);
     const unsigned wgrid = (unsigned)std::min<int64_t>(ceil_div(n, 4), (int64_t)ctx->num_cus * 64);      // a wave per row
     ctx->stage_reset(ST_DBSCAN);

@@ -583,9 +583,10 @@ int fal_ivf_build_x16(fal_ctx* ctx, const float* X, const void* X16, int64_t n, 
         // such rows the build and the searches of this index use the exact float32 kernels (same results, slower).
         uint16_t* sp_cols = nullptr;
         float* sp_vals = nullptr;
-        uint32_t *key_in = nullptr, *key_out = nullptr;
-        int32_t* iota = nullptr;
-        int64_t *boff_dev = nullptr, *lbase_dev = nullptr;
+        ScratchLayout LS, LB;
+        const auto key_in = LS.array<uint32_t>(n), key_out = LS.array<uint32_t>(n);
+        const auto iota = LS.array<int32_t>(n);
+        const auto boff_dev = LB.array<int64_t>(n_buckets + 1), lbase_dev = LB.array<int64_t>(n_buckets + 1);   // `tab`, uploaded whole
         int end_bit = 1;
         while (end_bit < 32 && (1ll << end_bit) < total) ++end_bit;
         {
@@ -595,15 +596,14 @@ int fal_ivf_build_x16(fal_ctx* ctx, const float* X, const void* X16, int64_t n, 
                 tab[b] = bucket_off[b];
                 tab[n_buckets + 1 + b] = ivf->list_base[b];
             }
-            int64_t* seg_dev = nullptr;
-            void* sortbuf = nullptr;
-            B_TRY(ctx->reserve(SLOT_MISC, sizeof(int64_t) * (seg_off.size() + 2), (void**)&seg_dev));
+            ScratchLayout LM;
+            const auto seg_dev = LM.array<int64_t>((int64_t)seg_off.size());
+            const auto neg_dev = LM.array<int32_t>(4);
+            B_TRY(LM.reserve(ctx, SLOT_MISC));
             B_TRY(ctx->upload(seg_dev, seg_off.data(), sizeof(int64_t) * seg_off.size()));
-            int32_t* neg_dev = reinterpret_cast<int32_t*>(seg_dev + seg_off.size());
             B_HIP(hipMemsetAsync(neg_dev, 0, 2 * sizeof(int64_t), st));
-            B_TRY(ctx->reserve(SLOT_MISC2, sizeof(int64_t) * tab.size(), (void**)&boff_dev));
+            B_TRY(LB.reserve(ctx, SLOT_MISC2));
             B_TRY(ctx->upload(boff_dev, tab.data(), sizeof(int64_t) * tab.size()));
-            lbase_dev = boff_dev + n_buckets + 1;
             B_TRY(ctx->pool_alloc(sizeof(uint16_t) * (size_t)n * kSparseW, (void**)&ivf->sp_cols));
             B_TRY(ctx->pool_alloc(sizeof(float) * (size_t)n * kSparseW, (void**)&ivf->sp_vals));
             sp_cols = ivf->sp_cols;
@@ -611,10 +611,7 @@ int fal_ivf_build_x16(fal_ctx* ctx, const float* X, const void* X16, int64_t n, 
             // (with float16 rows at hand the searches may run the float16 list scan: its queries arrive as 256-byte sparse records)
             // (rows of up to 400 columns: at 800 the dense gather is the faster form, list16s.hip)
             if (X16 != nullptr && low_dim <= 400) B_TRY(ctx->pool_alloc(sizeof(uint16_t) * (size_t)n * 2 * kSparseW, (void**)&ivf->sq16));
-            B_TRY(ctx->reserve(SLOT_SORT2, 3 * sizeof(uint32_t) * (size_t)n, &sortbuf));
-            key_in = (uint32_t*)sortbuf;
-            key_out = key_in + n;
-            iota = (int32_t*)(key_out + n);
+            B_TRY(LS.reserve(ctx, SLOT_SORT2));
             {
                 StageScope ts(ctx, ST_BUILD);
                 hipLaunchKernelGGL(sparsify_rows_kernel, dim3((unsigned)seg_off.back()), dim3(256), 0, st, X, low_dim, bkd, seg_dev,

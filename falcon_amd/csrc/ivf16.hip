@@ -670,13 +670,16 @@ int launch_select16(fal_ctx* ctx, const Select16Args& a_in, int64_t n_tiles) {
     Select16Args a = a_in;
     a.n_tiles = n_tiles;
     // tile -> job table, then the list of queries with more than 2,048 keys (count in front)
-    int32_t* tj = nullptr;
     ctx->release(SLOT_TILEJOB);        // a launcher-local table: the previous launcher's pointer is dead
-    FAL_TRY(ctx->reserve(SLOT_TILEJOB, sizeof(int32_t) * (size_t)(std::max<int64_t>(n_tiles, 1 << 16) + 35 * n_tiles + 64 + 4), (void**)&tj));
-    a.big_count = tj + std::max<int64_t>(n_tiles, 1 << 16);
-    a.big_list = a.big_count + 16;
-    int32_t* tp0 = a.big_list + 32 * n_tiles;
-    int64_t* tl0 = reinterpret_cast<int64_t*>(tj + ((std::max<int64_t>(n_tiles, 1 << 16) + 33 * n_tiles + 16 + 1) & ~(int64_t)1));      // (8-byte aligned)
+    ScratchLayout L;
+    const auto tj = L.array<int32_t>(std::max<int64_t>(n_tiles, 1 << 16));
+    const auto big_count = L.array<int32_t>(16), big_list = L.array<int32_t>(32 * n_tiles);
+    const auto tp0 = L.array<int32_t>(n_tiles);
+    const auto tl0 = L.array<int64_t>(n_tiles);
+    L.pad(208);
+    FAL_TRY(L.reserve(ctx, SLOT_TILEJOB));
+    a.big_count = big_count;
+    a.big_list = big_list;
     a.big_cap = (int)std::min<int64_t>(32 * n_tiles, INT32_MAX);
     FAL_REQUIRE(n_tiles * 8 < (int64_t)INT32_MAX, FAL_EUNSUPPORTED, "too many queries in one select launch");
     StageScope ts(ctx, ST_SELECT);

@@ -126,24 +126,17 @@ extern "C" int fal_library_search(fal_ctx* ctx, const float* q_mz, const float* 
     const NetCall call{"fal_library_search", "in scope", 14, SLOT_LIB2, SLOT_LIB3, SLOT_LIB4, SLOT_LIB6, SLOT_LIB7};
     hipStream_t st = ctx->stream;
     const int64_t n_tiles = ceil_div(nq, kExTile);
-    // SLOT_LIB: misc 64 B | q_order, q_crow i64[nq] | l_order, l_crow i64[nl] | toff i64[n_tiles + 1] | q_pmzs f32[nq] | l_pmzs
-    // f32[nl] | q_node i32[nq] | l_node i32[nl] | chunks, first, end i32[n_tiles]
-    unsigned char* blk = nullptr;
-    FAL_TRY(ctx->reserve(SLOT_LIB, 64 + 24 * (size_t)(nq + nl) + 20 * (size_t)(n_tiles + 1), (void**)&blk));
-    NetWords w(blk);
-    int64_t* q_order = reinterpret_cast<int64_t*>(blk + 64);
-    int64_t* q_crow = q_order + nq;
-    int64_t* l_order = q_crow + nq;
-    int64_t* l_crow = l_order + nl;
-    int64_t* toff = l_crow + nl;
-    float* q_pmzs = reinterpret_cast<float*>(toff + n_tiles + 1);
-    float* l_pmzs = q_pmzs + nq;
-    int32_t* q_node = reinterpret_cast<int32_t*>(l_pmzs + nl);
-    int32_t* l_node = q_node + nq;
-    int32_t* chunks = l_node + nl;
-    int32_t* first = chunks + n_tiles;
-    int32_t* end = first + n_tiles;
-    FAL_CHECK_HIP(hipMemsetAsync(blk, 0, 64, st));
+    ScratchLayout L;
+    const auto words = L.array<unsigned char>(64);          // the call's words (NetWords)
+    const auto q_order = L.array<int64_t>(nq), q_crow = L.array<int64_t>(nq), l_order = L.array<int64_t>(nl), l_crow = L.array<int64_t>(nl);
+    const auto toff = L.array<int64_t>(n_tiles + 1);
+    const auto q_pmzs = L.array<float>(nq), l_pmzs = L.array<float>(nl);
+    const auto q_node = L.array<int32_t>(nq), l_node = L.array<int32_t>(nl);
+    const auto chunks = L.array<int32_t>(n_tiles), first = L.array<int32_t>(n_tiles), end = L.array<int32_t>(n_tiles);
+    L.pad(12);
+    FAL_TRY(L.reserve(ctx, SLOT_LIB));
+    NetWords w(words);
+    FAL_CHECK_HIP(hipMemsetAsync(words, 0, 64, st));
     FAL_TRY(fal_sort_by_precursor(ctx, q_precursor_mz, nq, q_order, q_pmzs));
     ctx->release(SLOT_SORT);                                     // (the second sort may grow them: the first one's work is enqueued)
     ctx->release(SLOT_SORT2);
@@ -167,17 +160,17 @@ extern "C" int fal_library_search(fal_ctx* ctx, const float* q_mz, const float* 
                        lib_greedy_kernel<kNetSmall>, lib_greedy_kernel<kNetMaxPeaks>, &ht, &m, q, l, rule));
     if (m == 0) return FAL_OK;
     // SLOT_LIB4: the hits in (query, library) order, s.flag = keep; the second, stable pass by (query, sim descending) keeps equal
-    // similarities in that order.  SLOT_LIB5: rkey in / out u64[m] | rhit in / out u64[m]
+    // similarities in that order.
     NetSorted s;
-    uint64_t* rkey = nullptr;
-    FAL_TRY(ctx->reserve(SLOT_LIB5, 32 * (size_t)m, (void**)&rkey));
-    uint64_t* rhit = rkey + 2 * m;
+    ScratchLayout L5;
+    const auto rkey = L5.array<uint64_t>(2 * m), rhit = L5.array<uint64_t>(2 * m);           // the sort's in and out, m each
+    FAL_TRY(L5.reserve(ctx, SLOT_LIB5));
     FAL_TRY(net_sort_records(ctx, call, ht, m, &s));
     const unsigned hgrid = capped_grid(ctx, m, kNetBlock);
     hipLaunchKernelGGL(lib_rank_entries_kernel, dim3(hgrid), dim3(kNetBlock), 0, st, s.keys, s.vals, m, rkey, rhit);
     ctx->release(SLOT_LIB7);                           // (the hit sort is enqueued: its block is retired, not freed, if this one grows)
     // (the hit numbers travel through the sort as the bit patterns of doubles)
-    FAL_TRY(sort_pairs_u64_f64(ctx, rkey, rkey + m, reinterpret_cast<double*>(rhit), reinterpret_cast<double*>(rhit + m), m, SLOT_LIB7));
+    FAL_TRY(sort_pairs_u64_f64(ctx, rkey, rkey + m, reinterpret_cast<double*>(rhit.get()), reinterpret_cast<double*>(rhit + m), m, SLOT_LIB7));
     int64_t kept = m;
     if (top_n > 0) {
         hipLaunchKernelGGL(lib_rank_mark_kernel, dim3(hgrid), dim3(kNetBlock), 0, st, rkey + m, m, top_n, s.flag);

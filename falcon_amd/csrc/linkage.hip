@@ -473,11 +473,11 @@ int linkage_dev_src(fal_ctx* ctx, const LinkageSource& src, int64_t n, double t,
     const float* nb_dist = src.nb_dist;
     const int k = src.csr_ptr || src.exact_fill ? 0 : src.k;
     hipStream_t st = ctx->stream;
-    int32_t* buf = nullptr;
     int64_t* rank = nullptr;
-    FAL_TRY(ctx->reserve(SLOT_DB, sizeof(int32_t) * (size_t)n * 4, (void**)&buf));
+    ScratchLayout L;
+    const auto parent = L.array<int32_t>(n), count = L.array<int32_t>(n), rep = L.array<int32_t>(n), flag = L.array<int32_t>(n);
+    FAL_TRY(L.reserve(ctx, SLOT_DB));
     FAL_TRY(ctx->reserve(SLOT_DB2, sizeof(int64_t) * (size_t)(n + 1), (void**)&rank));
-    int32_t *parent = buf, *count = buf + n, *rep = buf + 2 * n, *flag = buf + 3 * n;
     const int grid = (int)std::min<int64_t>(ceil_div(n, 256), (int64_t)ctx->num_cus * 16);
     const int egrid = (int)std::min<int64_t>(ceil_div(n * src.k, 256), (int64_t)ctx->num_cus * 32);
     ctx->stage_reset(ST_DBSCAN);
@@ -491,14 +491,13 @@ int linkage_dev_src(fal_ctx* ctx, const LinkageSource& src, int64_t n, double t,
     if (method == 0) {
         hipLaunchKernelGGL(lk_single_kernel, dim3(grid), dim3(256), 0, st, parent, count, n, rep);
     } else {
-        int64_t *msz = nullptr, *moff = nullptr, *qoff = nullptr, *crank = nullptr;
-        FAL_TRY(ctx->reserve(SLOT_TAIL, sizeof(int64_t) * (size_t)(4 * (n + 1)), (void**)&msz));
-        int64_t* msq = msz + (n + 1);
-        moff = msq + (n + 1);
-        qoff = moff + (n + 1);
+        ScratchLayout LT, LT2;
+        const auto msz = LT.array<int64_t>(n + 1), msq = LT.array<int64_t>(n + 1), moff = LT.array<int64_t>(n + 1), qoff = LT.array<int64_t>(n + 1);
+        FAL_TRY(LT.reserve(ctx, SLOT_TAIL));
         const int64_t big_cap = n / kLinkageWaveMax + 2;    // components of more than kLinkageWaveMax rows: at most n / that many
-        FAL_TRY(ctx->reserve(SLOT_TAIL2, sizeof(int64_t) * (size_t)(n + 1) + sizeof(int32_t) * (size_t)(big_cap + 2), (void**)&crank));
-        int32_t* big = reinterpret_cast<int32_t*>(crank + n + 1);           // (behind the n + 1 words of the scan)
+        const auto crank = LT2.array<int64_t>(n + 1);       // (the n + 1 words of the scan)
+        const auto big = LT2.array<int32_t>(big_cap + 2);
+        FAL_TRY(LT2.reserve(ctx, SLOT_TAIL2));
         FAL_CHECK_HIP(hipMemsetAsync(big, 0, sizeof(int32_t), st));
         hipLaunchKernelGGL(lk_comp_kernel, dim3(grid), dim3(256), 0, st, parent, count, n, flag, msz, msq, big);
         FAL_TRY(device_scan_i32(ctx, flag, n, crank, SLOT_DB3));
@@ -513,20 +512,21 @@ int linkage_dev_src(fal_ctx* ctx, const LinkageSource& src, int64_t n, double t,
         FAL_CHECK_HIP(hipStreamSynchronize(st));
         const int64_t n_comp = tot[0], n_mem = tot[1], n_sq = tot[2];
         if (n_comp > 0) {
-            int32_t* ibuf = nullptr;
-            double* D = nullptr;
-            FAL_TRY(ctx->reserve(SLOT_TAIL3, sizeof(int32_t) * (size_t)(7 * n_mem + 2 * n + n_comp + 16), (void**)&ibuf));
-            const int rc = ctx->reserve(SLOT_TAIL4, sizeof(double) * (size_t)(n_sq + n_mem + 16), (void**)&D);
+            ScratchLayout LT3, LT4;
+            const auto mem = LT3.array<int32_t>(n_mem), mem_sorted = LT3.array<int32_t>(n_mem), act = LT3.array<int32_t>(n_mem);
+            const auto sz = LT3.array<int32_t>(n_mem), cl = LT3.array<int32_t>(n_mem), nni = LT3.array<int32_t>(n_mem), todo = LT3.array<int32_t>(n_mem);
+            const auto lidx = LT3.array<int32_t>(n), cursor = LT3.array<int32_t>(n), comp_root = LT3.array<int32_t>(n_comp);
+            LT3.pad(64);
+            FAL_TRY(LT3.reserve(ctx, SLOT_TAIL3));
+            const auto D = LT4.array<double>(n_sq), nnv = LT4.array<double>(n_mem);
+            LT4.pad(128);
+            const int rc = LT4.reserve(ctx, SLOT_TAIL4);
             if (rc != FAL_OK) {
                 set_error("hierarchical clustering (complete / average): the connected groups within the distance threshold need "
                           "%.1f GB of pair distances (sum of squared group sizes %lld); single linkage or DBSCAN take the same graph",
                           8e-9 * (double)n_sq, (long long)n_sq);
                 return rc;
             }
-            int32_t *mem = ibuf, *mem_sorted = mem + n_mem, *act = mem_sorted + n_mem, *sz = act + n_mem, *cl = sz + n_mem;
-            int32_t *nni = cl + n_mem, *todo = nni + n_mem;
-            int32_t *lidx = todo + n_mem, *cursor = lidx + n, *comp_root = cursor + n;
-            double* nnv = D + n_sq;
             FAL_CHECK_HIP(hipMemsetAsync(cursor, 0, sizeof(int32_t) * (size_t)n, st));
             const unsigned qgrid = (unsigned)std::min<int64_t>(ceil_div(n_sq, 256), (int64_t)ctx->num_cus * 32);
             hipLaunchKernelGGL(lk_scatter_kernel, dim3(grid), dim3(256), 0, st, parent, count, n, moff, cursor, mem, crank, comp_root);

@@ -236,19 +236,17 @@ __global__ __launch_bounds__(kMsBlock) void ms_summary_kernel(const int64_t* __r
 }
 
 // the members in (label, row) order: key u32[n] (the label), row i32[n]; with cstart_out, the first member of every cluster.
-// One block of SLOT_MSCORE: misc 64 B | cstart i64[n_clusters + 1] | key_in, key u32[n] | row_in, row i32[n]
+// One block of SLOT_MSCORE.
 int ms_order(fal_ctx* ctx, const int32_t* labels, int64_t n, int64_t n_clusters, int32_t** misc_out, const uint32_t** key_out,
              const int32_t** row_out, const int64_t** cstart_out) {
     hipStream_t st = ctx->stream;
-    unsigned char* blk = nullptr;
     const int64_t n1 = std::max<int64_t>(n, 1);
-    FAL_TRY(ctx->reserve(SLOT_MSCORE, 64 + sizeof(int64_t) * (size_t)(n_clusters + 1) + (size_t)n1 * 16, (void**)&blk));
-    int32_t* misc = reinterpret_cast<int32_t*>(blk);
-    int64_t* cstart = reinterpret_cast<int64_t*>(blk + 64);
-    uint32_t* key_in = reinterpret_cast<uint32_t*>(cstart + n_clusters + 1);
-    uint32_t* key = key_in + n1;
-    int32_t* row_in = reinterpret_cast<int32_t*>(key + n1);
-    int32_t* row = row_in + n1;
+    ScratchLayout L;
+    const auto misc = L.array<int32_t>(16);                // 64 B of meta words
+    const auto cstart = L.array<int64_t>(n_clusters + 1);
+    const auto key_in = L.array<uint32_t>(n1), key = L.array<uint32_t>(n1);
+    const auto row_in = L.array<int32_t>(n1), row = L.array<int32_t>(n1);
+    FAL_TRY(L.reserve(ctx, SLOT_MSCORE));
     FAL_CHECK_HIP(hipMemsetAsync(misc, 0, 64, st));
     if (n > 0) {
         hipLaunchKernelGGL(ms_label_keys_kernel, dim3(capped_grid(ctx, n, kMsBlock)), dim3(kMsBlock), 0, st, labels, n, key_in, row_in);

@@ -480,20 +480,19 @@ extern "C" int fal_mgf_index(fal_ctx* ctx, const uint8_t* text, int64_t n_bytes,
     }
     const int64_t n_tiles = ceil_div(n_bytes, kTileBytes);
     const int64_t cap_lines = n_bytes / 4 + 2, cap_spectra = n_bytes / 20 + 2, cap_blocks = ceil_div(cap_lines, kBlockLines);
-    int32_t *start = nullptr, *spec = nullptr, *block_nl = nullptr;
-    uint8_t *cls = nullptr, *small = nullptr;
+    int32_t* start = nullptr;
+    uint8_t* cls = nullptr;
     FAL_TRY(ctx->reserve(SLOT_MGF, sizeof(int32_t) * (size_t)(cap_lines + 1), (void**)&start));
     FAL_TRY(ctx->reserve(SLOT_MGF2, (size_t)cap_lines, (void**)&cls));
-    // meta words, block summaries and carries, newline counts and their scan
-    const size_t small_bytes = 64 + 2 * sizeof(int4) * (size_t)cap_blocks + (sizeof(int32_t) + sizeof(int64_t)) * (size_t)(n_tiles + 2) + 64;
-    FAL_TRY(ctx->reserve(SLOT_MGF3, small_bytes, (void**)&small));
-    FAL_TRY(ctx->reserve(SLOT_MGF4, 3 * sizeof(int32_t) * (size_t)cap_spectra, (void**)&spec));
-    unsigned long long* meta = reinterpret_cast<unsigned long long*>(small);
-    int4* summary = reinterpret_cast<int4*>(small + 64);
-    int4* carry = summary + cap_blocks;
-    int64_t* block_base = reinterpret_cast<int64_t*>(carry + cap_blocks);
-    block_nl = reinterpret_cast<int32_t*>(block_base + n_tiles + 1);
-    int32_t *spec_begin = spec, *spec_end = spec + cap_spectra, *spec_count = spec + 2 * cap_spectra;
+    ScratchLayout L3, L4;
+    const auto meta = L3.array<unsigned long long>(8);                              // 64 B of meta words
+    const auto summary = L3.array<int4>(cap_blocks), carry = L3.array<int4>(cap_blocks);
+    const auto block_base = L3.array<int64_t>(n_tiles + 1);                         // the scan of the newline counts
+    const auto block_nl = L3.array<int32_t>(n_tiles + 2);
+    L3.pad(72);
+    FAL_TRY(L3.reserve(ctx, SLOT_MGF3));
+    const auto spec_begin = L4.array<int32_t>(cap_spectra), spec_end = L4.array<int32_t>(cap_spectra), spec_count = L4.array<int32_t>(cap_spectra);
+    FAL_TRY(L4.reserve(ctx, SLOT_MGF4));
     FAL_CHECK_HIP(hipMemsetAsync(meta, 0, 64, ctx->stream));
     hipLaunchKernelGGL(mgf_newlines_kernel, dim3((unsigned)n_tiles), dim3(256), 0, ctx->stream, text, n_bytes, block_nl, meta);
     FAL_CHECK_HIP(hipGetLastError());
@@ -521,7 +520,7 @@ extern "C" int fal_mgf_index(fal_ctx* ctx, const uint8_t* text, int64_t n_bytes,
     counts_out[1] = overflow ? 0 : (int64_t)h[META_PEAKS];
     counts_out[2] = flags;
     counts_out[3] = (int64_t)h[META_LINES];
-    store_index(ctx->mgf, text, n_bytes, counts_out[0], counts_out[1], cap_lines, cap_spectra, start, cls, small, spec);
+    store_index(ctx->mgf, text, n_bytes, counts_out[0], counts_out[1], cap_lines, cap_spectra, start, cls, meta, spec_begin);
     return FAL_OK;
 }
 
@@ -548,11 +547,11 @@ extern "C" int fal_mgf_parse_ex(fal_ctx* ctx, const uint8_t* text, int64_t n_byt
     const uint8_t* cls = static_cast<const uint8_t*>(ix.blocks[1]);
     const int32_t* spec = static_cast<const int32_t*>(ix.blocks[3]);
     const int32_t *spec_begin = spec, *spec_end = spec + ix.cap_spectra, *spec_count = spec + 2 * ix.cap_spectra;
-    uint8_t* tmp = nullptr;
-    const size_t mz_bytes = sizeof(double) * (size_t)ix.extra;
-    FAL_TRY(ctx->reserve(SLOT_MGF5, mz_bytes + sizeof(float) * (size_t)ix.extra + 64, (void**)&tmp));
-    double* tmp_mz = reinterpret_cast<double*>(tmp);
-    float* tmp_it = reinterpret_cast<float*>(tmp + mz_bytes);
+    ScratchLayout L;
+    const auto tmp_mz = L.array<double>(ix.extra);
+    const auto tmp_it = L.array<float>(ix.extra);
+    L.pad(64);
+    FAL_TRY(L.reserve(ctx, SLOT_MGF5));
     FAL_TRY(device_scan_i32(ctx, spec_count, n_spectra, out_indptr, SLOT_SORT));
     const unsigned grid = capped_grid(ctx, n_spectra, 4);
     const MgfOut out{precursor_mz, charge, has_charge, retention_time, title, span, status_out};

@@ -248,22 +248,20 @@ extern "C" int fal_mzml_index(fal_ctx* ctx, const uint8_t* text, int64_t n_bytes
     if (n_bytes == 0) return FAL_OK;
     const int64_t n_tiles = ceil_div(n_bytes, kTileBytes);
     const int64_t cap_tags = n_bytes / 4 + 2, cap_spectra = n_bytes / 21 + 2, cap_blocks = ceil_div(cap_tags, kBlockTags);
-    int32_t *tag_pos = nullptr, *spec = nullptr;
+    int32_t* tag_pos = nullptr;
     MzTag* recs = nullptr;
-    uint8_t* small = nullptr;
     FAL_TRY(ctx->reserve(SLOT_MZML, sizeof(int32_t) * (size_t)(cap_tags + 1), (void**)&tag_pos));
     FAL_TRY(ctx->reserve(SLOT_MZML2, sizeof(MzTag) * (size_t)cap_tags, (void**)&recs));
-    // meta words; marker counts per tag block and their scan; '<' counts per tile and their scan
-    const size_t small_bytes = 64 + sizeof(int64_t) * (size_t)(2 * cap_blocks + 1) + (sizeof(int64_t) + sizeof(int32_t)) * (size_t)(n_tiles + 2) + 64;
-    FAL_TRY(ctx->reserve(SLOT_MZML3, small_bytes, (void**)&small));
-    FAL_TRY(ctx->reserve(SLOT_MZML4, 2 * sizeof(int32_t) * (size_t)cap_spectra, (void**)&spec));
-    unsigned long long* meta = reinterpret_cast<unsigned long long*>(small);
-    int64_t* block_cnt = reinterpret_cast<int64_t*>(small + 64);
-    int64_t* block_base = block_cnt + cap_blocks;
-    int64_t* tile_base = block_base + cap_blocks + 1;
-    int32_t* tile_cnt = reinterpret_cast<int32_t*>(tile_base + n_tiles + 1);
-    int32_t *spec_open = spec, *spec_close = spec + cap_spectra;
-    FAL_CHECK_HIP(hipMemsetAsync(small, 0, 64 + sizeof(int64_t) * (size_t)cap_blocks, ctx->stream));      // meta and block_cnt
+    ScratchLayout L3, L4;
+    const auto meta = L3.array<unsigned long long>(8);                              // 64 B of meta words
+    const auto block_cnt = L3.array<int64_t>(cap_blocks), block_base = L3.array<int64_t>(cap_blocks + 1);   // marker counts per tag block, their scan
+    const auto tile_base = L3.array<int64_t>(n_tiles + 1);                          // the scan of the '<' counts per tile
+    const auto tile_cnt = L3.array<int32_t>(n_tiles + 2);
+    L3.pad(72);
+    FAL_TRY(L3.reserve(ctx, SLOT_MZML3));
+    const auto spec_open = L4.array<int32_t>(cap_spectra), spec_close = L4.array<int32_t>(cap_spectra);
+    FAL_TRY(L4.reserve(ctx, SLOT_MZML4));
+    FAL_CHECK_HIP(hipMemsetAsync(meta, 0, 64 + sizeof(int64_t) * (size_t)cap_blocks, ctx->stream));       // meta and block_cnt behind it
     hipLaunchKernelGGL(mzml_count_kernel, dim3((unsigned)n_tiles), dim3(256), 0, ctx->stream, text, n_bytes, tile_cnt);
     FAL_CHECK_HIP(hipGetLastError());
     FAL_TRY(device_scan_i32(ctx, tile_cnt, n_tiles, tile_base, SLOT_SORT));
@@ -286,7 +284,7 @@ extern "C" int fal_mzml_index(fal_ctx* ctx, const uint8_t* text, int64_t n_bytes
     counts_out[1] = flags ? 0 : (int64_t)h[META_INSIDE];
     counts_out[2] = flags;
     counts_out[3] = (int64_t)h[META_TAGS];
-    store_index(ctx->mzml, text, n_bytes, counts_out[0], 0, cap_tags, cap_spectra, tag_pos, recs, small, spec);
+    store_index(ctx->mzml, text, n_bytes, counts_out[0], 0, cap_tags, cap_spectra, tag_pos, recs, meta, spec_open);
     return FAL_OK;
 }
 
@@ -306,13 +304,12 @@ extern "C" int fal_mzml_parse(fal_ctx* ctx, const uint8_t* text, int64_t n_bytes
     const MzTag* recs = static_cast<const MzTag*>(ix.blocks[1]);
     const int32_t* spec = static_cast<const int32_t*>(ix.blocks[3]);
     const int32_t *spec_open = spec, *spec_close = spec + ix.cap_spectra;
-    uint8_t* tmp = nullptr;
-    // text ranges (4 i32 a spectrum), rounded lengths (i32) and their scan (i64)
-    const size_t src_bytes = sizeof(int32_t) * 4 * (size_t)n_spectra, len_bytes = (sizeof(int32_t) * (size_t)n_spectra + 7) & ~(size_t)7;
-    FAL_TRY(ctx->reserve(SLOT_MZML5, src_bytes + len_bytes + sizeof(int64_t) * (size_t)(n_spectra + 1) + 64, (void**)&tmp));
-    int32_t* src = reinterpret_cast<int32_t*>(tmp);
-    int32_t* rlen = reinterpret_cast<int32_t*>(tmp + src_bytes);
-    int64_t* offs = reinterpret_cast<int64_t*>(tmp + src_bytes + len_bytes);
+    ScratchLayout L;
+    const auto src = L.array<int32_t>(4 * n_spectra);      // text ranges, four words a spectrum
+    const auto rlen = L.array<int32_t>(n_spectra);         // rounded lengths
+    const auto offs = L.array<int64_t>(n_spectra + 1);     // and their scan
+    L.pad(64);
+    FAL_TRY(L.reserve(ctx, SLOT_MZML5));
     const MzmlOut out{status_out, id, span, precursor_mz, charge, retention_time, arrays};
     hipLaunchKernelGGL(mzml_walk_kernel, dim3((unsigned)ceil_div(n_spectra, 64)), dim3(64), 0, ctx->stream, text, recs, tag_pos, spec_open,
                        spec_close, n_spectra, src, rlen, out);

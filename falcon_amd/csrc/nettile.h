@@ -324,12 +324,12 @@ inline int net_settle(fal_ctx* ctx, const NetCall& call, const NetWords& w, cons
     ctx->stage_reset(ST_TAIL);
     for (int run = 0;; ++run) {
         FAL_REQUIRE(run < 3, FAL_EINTERNAL, "%s: the lists did not settle", call.name);
-        int2* small = nullptr;
-        FAL_TRY(ctx->reserve(call.slot_lists, sizeof(int2) * (size_t)(small_cap + large_cap), (void**)&small));
-        uint64_t* keys = nullptr;
-        FAL_TRY(ctx->reserve(call.slot_out, 2 * sizeof(uint64_t) * (size_t)out_cap, (void**)&keys));
-        *out = NetOut{keys, keys + out_cap, out_cap, w.d_counts};
-        int2* large = small + small_cap;
+        ScratchLayout LL, LO;
+        const auto small = LL.array<int2>(small_cap), large = LL.array<int2>(large_cap);
+        FAL_TRY(LL.reserve(ctx, call.slot_lists));
+        const auto keys = LO.array<uint64_t>(out_cap), vals = LO.array<uint64_t>(out_cap);
+        FAL_TRY(LO.reserve(ctx, call.slot_out));
+        *out = NetOut{keys, vals, out_cap, w.d_counts};
         FAL_CHECK_HIP(hipMemsetAsync(w.d_counts, 0, 3 * sizeof(unsigned long long), st));
         if (wgs > 0) {
             StageScope ts(ctx, ST_KERNEL);
@@ -363,13 +363,16 @@ inline int net_settle(fal_ctx* ctx, const NetCall& call, const NetWords& w, cons
 }
 
 // the m records in the order of their keys (unique: a radix sort puts them in place; the order of arrival decides nothing), in
-// slot_sorted: keys, vals u64[m] | place i64[m + 1] | flag i32[m].  (The sort is exact.hip's: the 8-byte values travel as the
-// bit patterns of doubles.)
+// slot_sorted.  (The sort is exact.hip's: the 8-byte values travel as the bit patterns of doubles.)
 struct NetSorted { uint64_t *keys, *vals; int64_t* place; int32_t* flag; };
 inline int net_sort_records(fal_ctx* ctx, const NetCall& call, const NetOut& out, int64_t m, NetSorted* s) {
-    unsigned char* sb = nullptr;
-    FAL_TRY(ctx->reserve(call.slot_sorted, 28 * (size_t)m + 64, (void**)&sb));
-    *s = NetSorted{(uint64_t*)sb, (uint64_t*)sb + m, (int64_t*)sb + 2 * m, (int32_t*)((int64_t*)sb + 3 * m + 1)};
+    ScratchLayout L;
+    const auto keys = L.array<uint64_t>(m), vals = L.array<uint64_t>(m);
+    const auto place = L.array<int64_t>(m + 1);
+    const auto flag = L.array<int32_t>(m);
+    L.pad(56);
+    FAL_TRY(L.reserve(ctx, call.slot_sorted));
+    *s = NetSorted{keys, vals, place, flag};
     return sort_pairs_u64_f64(ctx, out.keys, s->keys, reinterpret_cast<double*>(out.vals), reinterpret_cast<double*>(s->vals), m,
                               call.slot_sort);
 }

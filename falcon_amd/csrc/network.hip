@@ -111,17 +111,15 @@ extern "C" int fal_network_edges(fal_ctx* ctx, const float* mz, const float* int
     hipStream_t st = ctx->stream;
     ctx->counters[12] = 0;
     const int64_t n_tiles = ceil_div(n, kExTile);
-    // SLOT_NET: misc 64 B | order, crow i64[n] | toff i64[n_tiles + 1] | pmzs f32[n] | node i32[n] | chunks i32[n_tiles]
-    unsigned char* blk = nullptr;
-    FAL_TRY(ctx->reserve(SLOT_NET, 64 + 24 * (size_t)n + 12 * (size_t)(n_tiles + 1), (void**)&blk));
-    NetWords w(blk);
-    int64_t* order = reinterpret_cast<int64_t*>(blk + 64);
-    int64_t* crow = order + n;
-    int64_t* toff = crow + n;
-    float* pmzs = reinterpret_cast<float*>(toff + n_tiles + 1);
-    int32_t* node = reinterpret_cast<int32_t*>(pmzs + n);
-    int32_t* chunks = node + n;
-    FAL_CHECK_HIP(hipMemsetAsync(blk, 0, 64, st));
+    ScratchLayout L;
+    const auto words = L.array<unsigned char>(64);          // the call's words (NetWords)
+    const auto order = L.array<int64_t>(n), crow = L.array<int64_t>(n), toff = L.array<int64_t>(n_tiles + 1);
+    const auto pmzs = L.array<float>(n);
+    const auto node = L.array<int32_t>(n), chunks = L.array<int32_t>(n_tiles);
+    L.pad(4);
+    FAL_TRY(L.reserve(ctx, SLOT_NET));
+    NetWords w(words);
+    FAL_CHECK_HIP(hipMemsetAsync(words, 0, 64, st));
     FAL_TRY(fal_sort_by_precursor(ctx, precursor_mz, n, order, pmzs));
     const NetSide sd = net_side(ctx, net_prepare_kernel, mz, intensity, indptr, n_csr_rows, rows, n, order, crow, pmzs, node, fragment_tol,
                                 min_matched, w.d_err);
@@ -137,19 +135,19 @@ extern "C" int fal_network_edges(fal_ctx* ctx, const float* mz, const float* int
     FAL_TRY(net_settle(ctx, call, w, toff, n_tiles, mz && intensity, net_tile_kernel, net_greedy_kernel<kNetSmall>,
                        net_greedy_kernel<kNetMaxPeaks>, &ed, &m, sd, NetRule{fragment_tol, max_shift, min_cosine, min_matched}));
     if (m == 0) return FAL_OK;
-    // SLOT_NET4: the edges in (u, v) order, s.flag = drop;  SLOT_NET5: rkey in / out u64[2 m] | redge in / out u64[2 m]
+    // SLOT_NET4: the edges in (u, v) order, s.flag = drop
     NetSorted s;
     FAL_TRY(net_sort_records(ctx, call, ed, m, &s));
     const unsigned egrid = capped_grid(ctx, m, kNetBlock);
     int64_t kept = m;
     if (top_k > 0) {
-        uint64_t* rkey = nullptr;
-        FAL_TRY(ctx->reserve(SLOT_NET5, 64 * (size_t)m, (void**)&rkey));
-        uint64_t* redge = rkey + 4 * m;
+        ScratchLayout L5;
+        const auto rkey = L5.array<uint64_t>(4 * m), redge = L5.array<uint64_t>(4 * m);      // the sort's in and out, 2 m each
+        FAL_TRY(L5.reserve(ctx, SLOT_NET5));
         hipLaunchKernelGGL(net_rank_entries_kernel, dim3(egrid), dim3(kNetBlock), 0, st, s.keys, s.vals, m, rkey, redge, s.flag);
         ctx->release(SLOT_NET7);                       // (the edge sort is enqueued: its block is retired, not freed, if this one grows)
         // (the edge numbers travel through the sort as the bit patterns of doubles)
-        FAL_TRY(sort_pairs_u64_f64(ctx, rkey, rkey + 2 * m, reinterpret_cast<double*>(redge), reinterpret_cast<double*>(redge + 2 * m), 2 * m,
+        FAL_TRY(sort_pairs_u64_f64(ctx, rkey, rkey + 2 * m, reinterpret_cast<double*>(redge.get()), reinterpret_cast<double*>(redge + 2 * m), 2 * m,
                                    SLOT_NET7));
         hipLaunchKernelGGL(net_rank_mark_kernel, dim3(capped_grid(ctx, 2 * m, kNetBlock)), dim3(kNetBlock), 0, st, rkey + 2 * m,
                            redge + 2 * m, 2 * m, top_k, s.flag);

@@ -133,22 +133,19 @@ extern "C" int fal_network_propagate(fal_ctx* ctx, const int32_t* edge_u, const 
         return FAL_OK;
     }
     hipStream_t st = ctx->stream;
-    // SLOT_PROP: misc 64 B | key u64[n] | hops, source, parent i32[n] | score f32[n]
-    unsigned char* blk = nullptr;
-    FAL_TRY(ctx->reserve(SLOT_PROP, 64 + 24 * (size_t)n, (void**)&blk));
-    int32_t* misc = reinterpret_cast<int32_t*>(blk);
-    unsigned long long* d_reached = reinterpret_cast<unsigned long long*>(blk + 16);
-    unsigned long long* key = reinterpret_cast<unsigned long long*>(blk + 64);
-    int32_t* hops = reinterpret_cast<int32_t*>(key + n);
-    int32_t* source = hops + n;
-    int32_t* parent = source + n;
-    float* score = reinterpret_cast<float*>(parent + n);
+    ScratchLayout L;
+    const auto misc = L.array<int32_t>(16);                // 64 B of meta words; the 64-bit count of reached nodes lives in words 4 and 5
+    const auto key = L.array<unsigned long long>(n);
+    const auto hops = L.array<int32_t>(n), source = L.array<int32_t>(n), parent = L.array<int32_t>(n);
+    const auto score = L.array<float>(n);
+    FAL_TRY(L.reserve(ctx, SLOT_PROP));
+    unsigned long long* d_reached = reinterpret_cast<unsigned long long*>(misc + 4);
     unsigned char* pin = nullptr;
     FAL_TRY(ctx->pinned_reserve(64, (void**)&pin));
     const int32_t* h_misc = reinterpret_cast<const int32_t*>(pin);
     const unsigned long long* h_reached = reinterpret_cast<const unsigned long long*>(pin + 16);
     const unsigned ngrid = capped_grid(ctx, n, kPropBlock), egrid = capped_grid(ctx, m, kPropBlock);
-    FAL_CHECK_HIP(hipMemsetAsync(blk, 0, 64, st));
+    FAL_CHECK_HIP(hipMemsetAsync(misc, 0, 64, st));
     if (m > 0) hipLaunchKernelGGL(prop_check_kernel, dim3(egrid), dim3(kPropBlock), 0, st, edge_u, edge_v, edge_sim, m, n, misc);
     hipLaunchKernelGGL(prop_init_kernel, dim3(ngrid), dim3(kPropBlock), 0, st, node_seed, n, hops, source, parent, score, key, misc);
     for (int32_t d = 1; m > 0 && d <= (int32_t)max_hops; ++d) {
@@ -160,7 +157,7 @@ extern "C" int fal_network_propagate(fal_ctx* ctx, const int32_t* edge_u, const 
                        node_parent, node_score);
     FAL_CHECK_HIP(hipGetLastError());
     // the call's one wait: the error word, the last level that reached a node and the nodes reached
-    FAL_CHECK_HIP(hipMemcpyAsync(pin, blk, 64, hipMemcpyDeviceToHost, st));
+    FAL_CHECK_HIP(hipMemcpyAsync(pin, misc, 64, hipMemcpyDeviceToHost, st));
     FAL_CHECK_HIP(hipStreamSynchronize(st));
     FAL_REQUIRE(h_misc[PROP_ERR] == 0, FAL_EINVAL,
                 "fal_network_propagate: a link with an end outside the %lld nodes, with both ends the same, or with a sim that is negative "

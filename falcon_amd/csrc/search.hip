@@ -618,18 +618,19 @@ static int search_impl(fal_ctx* ctx, const fal_ivf* ivf, int n_probe, int k_ann,
     // ---- inverted probe table (list -> queries probing it) ------------------------------------
     const int64_t TL = ivf->total_lists;
     const int64_t n_pairs_max = ivf->n * (int64_t)np;
-    int32_t *cnt = nullptr, *inv_q = nullptr;
-    int64_t *inv_off = nullptr, *inv_dest = nullptr;
-    FAL_TRY(ctx->reserve(SLOT_INVCNT, sizeof(int32_t) * (size_t)(3 * TL + 3) + sizeof(int64_t) * (size_t)(2 * TL + 4), (void**)&inv_off));
-    int64_t* ltile_off = inv_off + (TL + 2);
-    cnt = reinterpret_cast<int32_t*>(ltile_off + (TL + 2));
-    int32_t* cursor = cnt + (TL + 1);
-    int32_t* ltiles = cursor + (TL + 1);
+    ScratchLayout LC, LI;
+    const auto inv_off = LC.array<int64_t>(TL + 2), ltile_off = LC.array<int64_t>(TL + 2);
+    const auto cnt = LC.array<int32_t>(TL + 1), cursor = LC.array<int32_t>(TL + 1), ltiles = LC.array<int32_t>(TL + 1);
+    FAL_TRY(LC.reserve(ctx, SLOT_INVCNT));
     // (the probe table by sorted row as well when the f16 list scan may follow: ordered table + float16 rows attached)
     const bool want_rows = nf && ivf->X16pre && ivf->pos_of_row && max_n_list <= 16384;
-    FAL_TRY(ctx->reserve(SLOT_INV, (sizeof(int64_t) + (want_rows ? 2 : 1) * sizeof(int32_t)) * (size_t)n_pairs_max + 1024, (void**)&inv_dest));   // (slack: list16_kernel reads whole chunks of row ids)
-    inv_q = reinterpret_cast<int32_t*>(inv_dest + n_pairs_max);
-    int32_t* inv_row = want_rows ? inv_q + n_pairs_max + 64 : nullptr;
+    const auto inv_dest = LI.array<int64_t>(n_pairs_max);
+    const auto inv_q = LI.array<int32_t>(n_pairs_max);
+    LI.pad(want_rows ? 256 : 0);                            // inv_row begins 64 words behind inv_q
+    const auto own_inv_row = LI.array<int32_t>(want_rows ? n_pairs_max : 0);
+    LI.pad(want_rows ? 768 : 1024);                         // (slack, 1024 bytes in all: list16_kernel reads whole chunks of row ids)
+    FAL_TRY(LI.reserve(ctx, SLOT_INV));
+    int32_t* inv_row = want_rows ? own_inv_row.get() : nullptr;
     FAL_CHECK_HIP(hipMemsetAsync(cnt, 0, sizeof(int32_t) * (size_t)(2 * TL + 2), st));     // cnt, cursor
     {
         StageScope ts(ctx, ST_COARSE);
@@ -725,12 +726,13 @@ static int search_impl(fal_ctx* ctx, const fal_ivf* ivf, int n_probe, int k_ann,
             j32[j] = {cj.q_row0, cj.c_row0, 0, 0, cj.nq, cj.nq, xt32[x]};
             xt32[x] += ceil_div(cj.nq, 32);
         }
-        DenseJob* jd = nullptr;
         const int64_t tiles32 = *std::max_element(xt32, xt32 + 8);
-        const size_t jd_bytes = (sizeof(DenseJob) * j32.size() + 15) & ~(size_t)15;
-        FAL_TRY(ctx->reserve(SLOT_JOBS3, jd_bytes + sizeof(int32_t) * (size_t)(8 * tiles32), (void**)&jd));
+        ScratchLayout LJ;
+        const auto jd = LJ.array<DenseJob>((int64_t)j32.size());
+        LJ.align(16);
+        const auto tj32 = LJ.array<int32_t>(8 * tiles32);
+        FAL_TRY(LJ.reserve(ctx, SLOT_JOBS3));
         FAL_TRY(ctx->upload(jd, j32.data(), sizeof(DenseJob) * j32.size()));
-        int32_t* tj32 = reinterpret_cast<int32_t*>(reinterpret_cast<unsigned char*>(jd) + jd_bytes);
         FAL_TRY(launch_tile_job32(ctx, jd, (int)j32.size(), tiles32, tj32));
         FusedArgs fa{};
         fa.X = ivf->X; fa.jobs32 = jd; fa.n_jobs32 = (int)j32.size(); fa.tile_job32 = tj32;
@@ -741,11 +743,11 @@ static int search_impl(fal_ctx* ctx, const fal_ivf* ivf, int n_probe, int k_ann,
         fa.sp_cols = ivf->sp_cols; fa.sp_vals = ivf->sp_vals; fa.rows_f16 = ivf->rows_f16;
         FAL_TRY(fused_prepare(ctx, &fa, ivf->n));
         // the exact part: only the (query, candidate) pairs that can matter (pairs16.hip)
-        int2* gsel = nullptr;
-        float* pmz_l = nullptr;
         fa.ivf = 2;
-        FAL_TRY(ctx->reserve(SLOT_WIN, (sizeof(int2) + sizeof(float)) * (size_t)ivf->n, (void**)&gsel));
-        pmz_l = reinterpret_cast<float*>(gsel + ivf->n);
+        ScratchLayout LW;
+        const auto gsel = LW.array<int2>(ivf->n);
+        const auto pmz_l = LW.array<float>(ivf->n);
+        FAL_TRY(LW.reserve(ctx, SLOT_WIN));
         FAL_TRY(launch_gather_pmz(ctx, nf->pmz, ivf->perm, ivf->n, pmz_l));
         uint16_t* keys = nullptr;
         // (list16_kernel addresses a batch's keys by 32-bit byte offsets from the buffer's base)

@@ -102,10 +102,9 @@ static int device_scan_t(fal_ctx* ctx, const T* in, int64_t n, int64_t* out, int
         return FAL_OK;
     }
     const int64_t nb = ceil_div(n, kScanBlock);
-    int64_t* tmp = nullptr;
-    FAL_TRY(ctx->reserve(scratch_slot, sizeof(int64_t) * (size_t)(2 * nb + 2), (void**)&tmp));
-    int64_t* sums = tmp;
-    int64_t* offs = tmp + nb + 1;
+    ScratchLayout L;
+    const auto sums = L.array<int64_t>(nb + 1), offs = L.array<int64_t>(nb + 1);
+    FAL_TRY(L.reserve(ctx, scratch_slot));
     hipLaunchKernelGGL(scan_block_sums_kernel<T>, dim3((unsigned)nb), dim3(kScanBlock), 0, ctx->stream, in, n, sums);
     if (nb <= 4096) {
         hipLaunchKernelGGL(scan_apply_fused_kernel<T>, dim3((unsigned)nb), dim3(kScanBlock), 0, ctx->stream, in, n, sums, out);
@@ -394,10 +393,10 @@ int fal_precursor_splits(fal_ctx* ctx, const float* mz, int64_t n, double tol, i
     std::vector<int32_t> gap_flag;
     if (n > 1) {
         FAL_REQUIRE(mz, FAL_EINVAL, "fal_precursor_splits: NULL mz");
-        int32_t *flag = nullptr, *nz = nullptr, *cflag = nullptr;
-        int64_t *pos = nullptr, *cidx = nullptr;
-        FAL_TRY(ctx->reserve(SLOT_MISC, sizeof(int32_t) * (size_t)n * 2, (void**)&flag));
-        nz = flag + n;
+        int64_t* pos = nullptr;
+        ScratchLayout LF, LC;
+        const auto flag = LF.array<int32_t>(n), nz = LF.array<int32_t>(n);
+        FAL_TRY(LF.reserve(ctx, SLOT_MISC));
         FAL_TRY(ctx->reserve(SLOT_MISC2, sizeof(int64_t) * (size_t)(n + 1), (void**)&pos));
         const int grid = (int)std::min<int64_t>(ceil_div(n, 256), 4096);
         hipLaunchKernelGGL(split_flags_kernel, dim3(grid), dim3(256), 0, ctx->stream, mz, n, tol, tol_is_da, mz_interval, flag);
@@ -405,8 +404,9 @@ int fal_precursor_splits(fal_ctx* ctx, const float* mz, int64_t n, double tol, i
         FAL_TRY(device_scan_i32(ctx, nz, n, pos, SLOT_SORT));
         // compact on the device right away, then ONE synchronisation: the count and the first K entries
         // come back through a pinned buffer (a second readback only if there are more than K gaps)
-        FAL_TRY(ctx->reserve(SLOT_SORT2, (sizeof(int64_t) + sizeof(int32_t)) * (size_t)n, (void**)&cidx));
-        cflag = reinterpret_cast<int32_t*>(cidx + n);
+        const auto cidx = LC.array<int64_t>(n);
+        const auto cflag = LC.array<int32_t>(n);
+        FAL_TRY(LC.reserve(ctx, SLOT_SORT2));
         hipLaunchKernelGGL(compact_flags_kernel, dim3(grid), dim3(256), 0, ctx->stream, flag, pos, n, cidx, cflag);
         const int64_t K = std::min<int64_t>(n, 65536);
         unsigned char* pin = nullptr;

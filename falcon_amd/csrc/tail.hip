@@ -835,23 +835,24 @@ struct RefineArrays {
 };
 static int refine_arrays(fal_ctx* ctx, int64_t n, RefineArrays* A) {
     const int64_t cmax = n + 1;
-    unsigned char* slab = nullptr;
-    FAL_TRY(ctx->reserve(SLOT_TAIL, sizeof(int32_t) * (size_t)(3 * cmax + 2 * n) + 64, (void**)&A->counts));
-    A->cursor = A->counts + cmax;
-    A->n_sub = A->cursor + cmax;
-    A->rows = A->n_sub + cmax;
-    A->sub = A->rows + n;
-    FAL_TRY(ctx->reserve(SLOT_TAIL2, sizeof(int64_t) * (size_t)(2 * (cmax + 2)), (void**)&A->seg));
-    A->base = A->seg + (cmax + 2);
-    const size_t per = 4 * 11 + 8;   // 11 4-byte arrays + 1 double array
-    FAL_TRY(ctx->reserve(SLOT_TAIL4, per * (size_t)n + 256, (void**)&slab));
+    ScratchLayout L, L2, L4;
+    const auto counts = L.array<int32_t>(cmax), cursor = L.array<int32_t>(cmax), n_sub = L.array<int32_t>(cmax);
+    const auto rows = L.array<int32_t>(n), sub = L.array<int32_t>(n);
+    L.pad(64);
+    FAL_TRY(L.reserve(ctx, SLOT_TAIL));
+    const auto seg = L2.array<int64_t>(cmax + 2), base = L2.array<int64_t>(cmax + 2);
+    FAL_TRY(L2.reserve(ctx, SLOT_TAIL2));
+    const auto zmd = L4.array<double>(n);
+    const auto val = L4.array<float>(n), smin = L4.array<float>(n), smax = L4.array<float>(n);
+    const auto ord = L4.array<int32_t>(n), sid = L4.array<int32_t>(n), zl = L4.array<int32_t>(n), zr = L4.array<int32_t>(n);
+    const auto t_a = L4.array<int32_t>(n), t_b = L4.array<int32_t>(n), stack = L4.array<int32_t>(n), visit = L4.array<int32_t>(n);
+    L4.pad(256);
+    FAL_TRY(L4.reserve(ctx, SLOT_TAIL4));
+    *A = RefineArrays{counts, cursor, n_sub, rows, sub, seg, base, RefineScratch{}};
     RefineScratch& S = A->S;
-    S.zmd = reinterpret_cast<double*>(slab);
-    float* f = reinterpret_cast<float*>(slab + 8 * (size_t)n);
-    S.val = f;            S.smin = f + n;       S.smax = f + 2 * n;
-    int32_t* q = reinterpret_cast<int32_t*>(f + 3 * n);
-    S.ord = q;            S.sid = q + n;        S.zl = q + 2 * n;     S.zr = q + 3 * n;
-    S.t_a = q + 4 * n;    S.t_b = q + 5 * n;    S.stack = q + 6 * n;  S.visit = q + 7 * n;
+    S.zmd = zmd;      S.val = val;      S.smin = smin;    S.smax = smax;
+    S.ord = ord;      S.sid = sid;      S.zl = zl;        S.zr = zr;
+    S.t_a = t_a;      S.t_b = t_b;      S.stack = stack;  S.visit = visit;
     return FAL_OK;
 }
 
@@ -890,11 +891,11 @@ int fal::finalize_dev(fal_ctx* ctx, const int32_t* labels_sorted, int64_t n, con
                       const ExactPeaks* exact) {
     hipStream_t st = ctx->stream;
     const int64_t cmax = n + 1;               // fal_finalize accepts any n_clusters <= n (single-member clusters included)
-    int32_t *size = nullptr, *noise = nullptr;
     unsigned long long* best = nullptr;
     int64_t* rank = nullptr;
-    FAL_TRY(ctx->reserve(SLOT_FIN, sizeof(int32_t) * (size_t)(n + cmax + 2), (void**)&size));
-    noise = size + cmax + 1;
+    ScratchLayout L;
+    const auto size = L.array<int32_t>(cmax + 1), noise = L.array<int32_t>(n + 1);
+    FAL_TRY(L.reserve(ctx, SLOT_FIN));
     FAL_TRY(ctx->reserve(SLOT_FIN2, sizeof(unsigned long long) * (size_t)(cmax + 1), (void**)&best));
     FAL_TRY(ctx->reserve(SLOT_FIN3, sizeof(int64_t) * (size_t)(n + 1), (void**)&rank));
     FAL_CHECK_HIP(hipMemsetAsync(size, 0, sizeof(int32_t) * (size_t)(cmax + 1), st));
@@ -1053,13 +1054,13 @@ int fal_cluster_graph_tiled(fal_ctx* ctx, const int32_t* nb_idx, const float* nb
     hipStream_t st = ctx->stream;
     const int nt = (int)tile_row.size() - 1;
     int32_t* labels = labels_sorted_scratch;
-    // tile tables: tile_row[nt + 1] | cnt[4][nt] | base[4][nt + 1] | kept[nt] | fbase[nt + 1], then the int64 totals
-    int32_t* tt = nullptr;
-    const size_t words = (size_t)(nt + 1) + 4 * (size_t)nt + 4 * (size_t)(nt + 1) + (size_t)nt + (size_t)(nt + 1);
-    FAL_TRY(ctx->reserve(SLOT_TILES, sizeof(int32_t) * (words + 2) + sizeof(int64_t) * 5, (void**)&tt));
-    int32_t *d_tile_row = tt, *cnt = d_tile_row + (nt + 1), *base = cnt + 4 * (size_t)nt, *kept = base + 4 * (size_t)(nt + 1),
-            *fbase = kept + nt;
-    int64_t* totals = reinterpret_cast<int64_t*>(tt + ((words + 1) & ~(size_t)1));     // [0] DBSCAN clusters, [1] members, [2] error, [3] overflowed lists, [4] clusters kept
+    ScratchLayout LT;                                        // the tile tables
+    const auto d_tile_row = LT.array<int32_t>(nt + 1);
+    const auto cnt = LT.array<int32_t>(4 * (int64_t)nt), base = LT.array<int32_t>(4 * (int64_t)(nt + 1));   // [4][nt], [4][nt + 1]
+    const auto kept = LT.array<int32_t>(nt), fbase = LT.array<int32_t>(nt + 1);
+    const auto totals = LT.array<int64_t>(5);                // [0] DBSCAN clusters, [1] members, [2] error, [3] overflowed lists, [4] clusters kept
+    LT.pad(8);
+    FAL_TRY(LT.reserve(ctx, SLOT_TILES));
     FAL_TRY(ctx->upload(d_tile_row, tile_row.data(), sizeof(int32_t) * (size_t)(nt + 1)));
     // a10's arrays (refine_dev's) and a11's
     const int64_t cmax = n + 1;
