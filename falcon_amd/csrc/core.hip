@@ -301,8 +301,7 @@ int fal_ctx_plan(fal_ctx* c, int64_t n, int low_dim, int k_ann, int n_probe, int
     // the flat scan's hand-off: one [32, ceil32(n_b)] block per query tile, batches of at most the cap (search.hip); a bucket holds
     // at most batch_size rows -- the whole job's need is bounded by n * min(n, batch_size) floats, the cap (2 GiB) usually binds
     {
-        const char* e = getenv("FALCON_SIMS_MB");
-        size_t cap = (e ? (size_t)atoll(e) : 2048) * 1024 * 1024;
+        size_t cap = sims_mb_env() * 1024 * 1024;            // (as given: the search's 16 MB floor is not applied here)
         const double need = 4.0 * (double)nn * (double)std::min<int64_t>(n, std::min<int64_t>(batch_size, 4096));
         if (need < (double)cap) cap = (size_t)need;
         FAL_TRY(c->reserve(SLOT_SIMS, cap + sizeof(float) * kSimsSlack, &p));

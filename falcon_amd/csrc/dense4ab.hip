@@ -178,15 +178,7 @@ int launch_dense4ab(fal_ctx* ctx, const float* X, int d, const DenseJob* jobs, c
                     int64_t sims_base) {
     if (n_jobs <= 0) return FAL_OK;
     FAL_REQUIRE(dense4ab_supports(d), FAL_EUNSUPPORTED, "dense4ab: low_dim %d has no instantiation (400)", d);
-    std::vector<int32_t> table(16, 0);
-    for (int x = 0; x < 8; ++x) {
-        for (int j = x; j < n_jobs; j += 8)
-            for (int g = 0; g < (jobs_host[j].nq + 127) / 128; ++g) {
-                table.push_back(j);
-                table.push_back(g);
-            }
-        table[x + 1] = (int32_t)((table.size() - 16) / 2);
-    }
+    const std::vector<int32_t> table = dense4_items(jobs_host, n_jobs);
     const int64_t n_items = table[8];
     int32_t* table_dev = nullptr;
     FAL_TRY(ctx->reserve(SLOT_ITEMS, sizeof(int32_t) * table.size(), (void**)&table_dev));

@@ -11,6 +11,9 @@ enum { MODE_DENSE = 0, MODE_IVF = 1 };
 // every sims buffer is allocated with this many floats of slack after its last row: the select kernel
 // reads whole 64*R-key rounds without bounds checks, the f16 scan parks idle waves' stores there
 constexpr size_t kSimsSlack = 2048;
+// FALCON_SIMS_MB as given (default 2048), read at every call (search.hip).  The search keeps its first reading for the process
+// and applies a floor (searchplan.h: sims_cap_floats); fal_ctx_plan sizes the slot from the value as it stands.
+size_t sims_mb_env();
 
 struct SelectArgs {
     const float* sims;       // sims buffer of the current batch

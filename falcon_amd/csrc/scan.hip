@@ -484,16 +484,7 @@ int launch_dense4(fal_ctx* ctx, const float* X, int d, const DenseJob* jobs, con
     const bool split = d > 512;
     const int dv = split ? d / 2 : d;                        // columns one pass sees
     const int dh4 = dv / 8;
-    // the item table: 9 offsets (in items), then the (job, 128-row group) pairs of XCD list 0, 1, ... from word 16
-    std::vector<int32_t> table(16, 0);
-    for (int x = 0; x < 8; ++x) {
-        for (int j = x; j < n_jobs; j += 8)
-            for (int g = 0; g < (jobs_host[j].nq + 127) / 128; ++g) {
-                table.push_back(j);
-                table.push_back(g);
-            }
-        table[x + 1] = (int32_t)((table.size() - 16) / 2);
-    }
+    const std::vector<int32_t> table = dense4_items(jobs_host, n_jobs);
     const int64_t n_items = table[8];
     int32_t* table_dev = nullptr;
     FAL_TRY(ctx->reserve(SLOT_ITEMS, sizeof(int32_t) * table.size(), (void**)&table_dev));

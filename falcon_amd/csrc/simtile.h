@@ -11,6 +11,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "searchplan.h"
 
 namespace fal {
 
@@ -183,20 +184,7 @@ __device__ __forceinline__ float sortable_f32(uint32_t u) {
     return __uint_as_float(b);
 }
 
-// One unit of dense work: the queries [q_row0, q_row0+nq) of array Q against the candidates
-// [c_row0, c_row0+nc) of array C.  Tiles of 32 queries; tile0 = index of the job's first tile
-// in the launch; obase = where the job's sims start (float index): one [32, ceil32(nc)] block per tile.
-struct DenseJob {
-    int64_t q_row0;
-    int64_t c_row0;
-    int64_t obase;
-    int64_t tile0;
-    int32_t nq;
-    int32_t nc;
-    int64_t xtile0;   // XCD-list mode: tiles of earlier jobs of the same XCD list (jobs j, j+8, j+16 ...)
-};
-
-// binary search: last job whose tile0 <= t
+// binary search: last job (searchplan.h: DenseJob) whose tile0 <= t
 __device__ __forceinline__ int find_job(const DenseJob* __restrict__ jobs, int n_jobs, int64_t t) {
     int lo = 0, hi = n_jobs - 1;
     while (lo < hi) {

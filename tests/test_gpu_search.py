@@ -1,4 +1,8 @@
 """GPU parity: a6 (IVF build) and a7 (n_probe search + top-k) vs the oracle."""
+import os
+import subprocess
+import sys
+
 import numpy as np
 import pytest
 
@@ -6,6 +10,7 @@ from oracle import falcon_oracle as fo
 from tests.util import assert_topk_close, assert_topk_exact
 
 pytestmark = pytest.mark.gpu
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 @pytest.fixture(scope="module")
@@ -90,18 +95,15 @@ def test_small_flat_buckets_beyond_low_dim_512_are_exact(ctx):
             assert np.array_equal(np.isfinite(sim[a:e]), fin) and np.abs(sim[a:e][fin] - rs[fin]).max() <= 2e-6
 
 
-def test_flat_many_small_batches(ctx, monkeypatch):
-    """forces several scan/select batches through a tiny sims buffer."""
-    import torch
-    sizes = [300] * 12
-    off = np.concatenate([[0], np.cumsum(sizes)])
-    X = unit_vectors(off[-1], 400, 5)
-    idxr = ctx.ivf_build(torch.from_numpy(X).to(ctx.tdev), off, np.ones(len(sizes), np.int32))
-    sim, idx = idxr.search(16, 32)
-    sim, idx = sim.cpu().numpy(), idx.cpu().numpy()
-    for a, b in zip(off[:-1], off[1:]):
-        rs, ri = fo.exhaustive_topk(X[a:b], 32, base=a)
-        assert_topk_exact(sim[a:b], idx[a:b], rs, ri)
+def test_flat_many_small_batches():
+    """forces several scan/select batches through a tiny sims buffer: FALCON_SIMS_MB is read once per process, so a fresh child
+    (tests/search_batches_worker.py) runs with 16 MB -- flat buckets in three batches (exact top-k per bucket), two indexed
+    buckets whose fine scan takes two batches on the staged path (exact top-k) and on the float16 key path (neighbour lists bit
+    for bit the staged path's); `fal_ctx_counter(2)` must report the batch counts tests/test_searchplan_cpu.py derives"""
+    env = dict(os.environ, FALCON_SIMS_MB="16", PYTHONPATH=ROOT + os.pathsep + os.environ.get("PYTHONPATH", ""))
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "search_batches_worker.py")], env=env, cwd=ROOT,
+                       capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0 and "batches ok" in r.stdout, r.stdout[-2000:] + r.stderr[-3000:]
 
 
 @pytest.mark.parametrize("sizes,nlists,d", [
