@@ -4,6 +4,7 @@
 #include "common.h"
 
 namespace fal {
+struct BucketDev;                            // buildplan.h
 // the sparse form of a row (fal_ivf::sp_cols / sp_vals)
 constexpr int kSparseW = 64;                 // entries per row (one per lane)
 constexpr uint16_t kColPad = 0xFFFF;         // unused entry
@@ -81,5 +82,5 @@ struct fal_ivf {
     int rows_many = 0;
     int64_t* list_off = nullptr;     // [total_lists + 1] list-order positions
     int64_t* counts = nullptr;       // [total_lists + 1] list sizes (flat buckets)
-    void* bk_dev = nullptr;          // BucketDev[n_ivf_buckets]
+    fal::BucketDev* bk_dev = nullptr;   // [n_ivf_buckets] the indexed buckets
 };

@@ -6,6 +6,7 @@
 // ivf_search).  Everything is batched over ALL buckets of a charge partition: one launch per
 // step, never one launch per bucket.
 #include <algorithm>
+#include <memory>
 #include <hip/hip_fp16.h>
 #include <math.h>
 #include <stdlib.h>
@@ -20,14 +21,6 @@ namespace fal {
 // ------------------------------------------------------------------------------------------
 // small kernels
 // ------------------------------------------------------------------------------------------
-struct BucketDev {       // one per IVF (n_list > 1) bucket
-    int64_t row0;        // first sorted row
-    int64_t list0;       // global id of its list 0
-    int32_t n;           // rows
-    int32_t n_list;
-    int64_t wave0;       // index of its first (bucket, list) wave in per-list launches
-};
-
 __device__ __forceinline__ int find_bucket(const BucketDev* __restrict__ b, int nb, int64_t w) {
     int lo = 0, hi = nb - 1;
     while (lo < hi) {
@@ -158,8 +151,6 @@ __global__ void list_bounds_kernel(const uint32_t* __restrict__ keys_sorted, int
 // offsets follow from a wave scan, and the rows are placed chunk by chunk IN ORDER: lanes with the same list find each other
 // with one ballot per list-id bit, rank = earlier peers in the chunk, base = the list's running cursor in LDS.  Identical output
 // (perm, list_off of the bucket's lists); flat buckets keep what the first, global sort of the build wrote.
-constexpr int kBucketSortMaxLists = 2048;
-
 __global__ __launch_bounds__(64) void bucket_list_sort_kernel(const int32_t* __restrict__ assign, const BucketDev* __restrict__ bk, int nb,
                                                               int32_t* __restrict__ perm, int64_t* __restrict__ list_off) {
     __shared__ uint32_t cur[kBucketSortMaxLists];
@@ -402,6 +393,277 @@ __global__ void rows_sign16_kernel(const uint4* __restrict__ x, int64_t n8, int3
 }  // namespace fal
 FAL_WARM_KERNEL(fal::kmeans_init_kernel);      // (fal_ctx_plan: this unit's code object is loaded up front)
 
+// ------------------------------------------------------------------------------------------
+// build: fal_ivf_build_x16 step by step; the host arithmetic of every step is buildplan.h
+// ------------------------------------------------------------------------------------------
+namespace {
+struct IvfDestroy {
+    void operator()(fal_ivf* ivf) const { fal_ivf_destroy(ivf); }
+};
+using IvfOwner = std::unique_ptr<fal_ivf, IvfDestroy>;      // the one owner of a half-built index: every error path frees through it
+
+struct Build {                   // one call: what every step reads
+    fal_ctx* ctx;
+    fal_ivf* ivf;
+    const float* X;
+    const void* X16;             // float16 rows for the prefiltered assignment, or nullptr
+    const int64_t* bucket_off;
+    const int32_t* n_list;
+    int64_t n_buckets;
+    int kmeans_iters;
+    size_t ckeys_budget;         // bytes the coarse keys may take
+    std::vector<BucketDev> bk;   // the indexed buckets (host copy of ivf->bk_dev)
+    // sparsify_rows -> sort_lists
+    uint32_t *key_in = nullptr, *key_out = nullptr;
+    int32_t* iota = nullptr;
+    int64_t *boff_dev = nullptr, *lbase_dev = nullptr;      // bucket_off and list_base on the device
+    bool sorted_once = false;
+    // upload_jobs -> assign_pass, update_centroids
+    AssignPlan plan;
+    AssignJob *wide_dev = nullptr, *half_dev = nullptr;
+    DenseJob* dense_dev = nullptr;
+    unsigned long long* keys = nullptr;                     // launch_assign's scratch
+    void* C16 = nullptr;                                    // the centroids' float16 copy
+};
+
+// the arguments checked, the handle with its host tables, the list table (-> bk: the indexed buckets)
+int new_index(fal_ctx* ctx, const float* X, int64_t n, int low_dim, const int64_t* bucket_off, int64_t n_buckets,
+              const int32_t* n_list, int kmeans_iters, IvfOwner& owner, std::vector<BucketDev>& bk) {
+    FAL_REQUIRE(n >= 0 && n < (int64_t)INT32_MAX, FAL_EUNSUPPORTED, "fal_ivf_build: n must be < 2^31 per partition");
+    FAL_REQUIRE(low_dim >= 8 && low_dim <= FAL_MAX_LOW_DIM && low_dim % 8 == 0, FAL_EUNSUPPORTED,
+                "fal_ivf_build: low_dim must be a multiple of 8 in [8, %d]", FAL_MAX_LOW_DIM);
+    FAL_REQUIRE(n_buckets >= 0 && (n_buckets == 0 || (bucket_off && n_list)), FAL_EINVAL, "fal_ivf_build: NULL bucket arrays");
+    FAL_REQUIRE(kmeans_iters >= 0, FAL_EINVAL, "fal_ivf_build: kmeans_iters < 0");
+    FAL_REQUIRE(n == 0 || X || all_flat(n_list, n_buckets), FAL_EINVAL, "fal_ivf_build: X may only be NULL when every bucket is flat");
+    if (n_buckets > 0) {
+        FAL_REQUIRE(bucket_off[0] == 0 && bucket_off[n_buckets] == n, FAL_EINVAL,
+                    "fal_ivf_build: bucket_off must start at 0 and end at n");
+    } else {
+        FAL_REQUIRE(n == 0, FAL_EINVAL, "fal_ivf_build: no buckets but n > 0");
+    }
+    ctx->counters[6] = 0;      // bit 0: rows of an indexed bucket, bit 1: rows handed to the flat prefilter have negative / non-finite
+                               // components -> this index runs without float16 prefilters (fal_ctx_counter 6)
+    owner.reset(new fal_ivf());
+    fal_ivf* ivf = owner.get();
+    ivf->ctx = ctx;
+    ivf->n = n;
+    ivf->d = low_dim;
+    ivf->X = X;
+    ivf->bucket_off.assign(bucket_off, bucket_off + n_buckets + 1 * (n_buckets > 0));
+    if (n_buckets == 0) ivf->bucket_off.assign(1, 0);
+    ivf->n_list.assign(n_list, n_list + n_buckets);
+    ListTable t;
+    const int64_t bad = plan_lists(bucket_off, n_list, n_buckets, FAL_MAX_N_LIST, t);
+    FAL_REQUIRE(bad < 0, FAL_EINVAL, "fal_ivf_build: bucket %lld: size %lld, n_list %d invalid", (long long)bad,
+                (long long)(bucket_off[bad + 1] - bucket_off[bad]), n_list[bad]);
+    ivf->list_base = std::move(t.list_base);
+    ivf->total_lists = t.total_lists;
+    ivf->n_ivf_buckets = (int)t.bk.size();
+    ivf->ivf_waves = t.ivf_waves;
+    bk = std::move(t.bk);
+    return FAL_OK;
+}
+
+// the index's arrays; counts, assign = 0, perm = identity; the indexed buckets' table and their first centroids
+int alloc_index(Build& b) {
+    fal_ctx* ctx = b.ctx;
+    fal_ivf* ivf = b.ivf;
+    hipStream_t st = ctx->stream;
+    const int64_t n = ivf->n, total = ivf->total_lists;
+    FAL_TRY(ctx->pool_alloc(sizeof(int32_t) * (size_t)n, (void**)&ivf->perm));
+    FAL_TRY(ctx->pool_alloc(sizeof(int32_t) * (size_t)n, (void**)&ivf->assign));
+    FAL_TRY(ctx->pool_alloc(sizeof(int64_t) * (size_t)(total + 1), (void**)&ivf->list_off));
+    FAL_TRY(ctx->pool_alloc(sizeof(int64_t) * (size_t)(total + 1), (void**)&ivf->counts));
+    FAL_TRY(ctx->pool_alloc(sizeof(float) * (size_t)total * ivf->d, (void**)&ivf->centroids));
+    ctx->stage_reset(ST_BUILD);
+    const std::vector<int64_t> cnt = initial_counts(b.bucket_off, b.n_list, ivf->list_base.data(), b.n_buckets);
+    FAL_TRY(ctx->upload(ivf->counts, cnt.data(), sizeof(int64_t) * cnt.size()));
+    FAL_CHECK_HIP(hipMemsetAsync(ivf->assign, 0, sizeof(int32_t) * (size_t)n, st));
+    FAL_CHECK_HIP(hipMemsetAsync(ivf->centroids, 0, sizeof(float) * (size_t)total * ivf->d, st));
+    if (n > 0) {
+        hipLaunchKernelGGL(iota_i32_kernel, dim3((unsigned)std::min<int64_t>(ceil_div(n, 256), 4096)), dim3(256), 0, st,
+                           ivf->perm, n);
+        FAL_CHECK_HIP(hipGetLastError());
+    }
+    if (b.bk.empty()) return FAL_OK;
+    FAL_TRY(ctx->pool_alloc(sizeof(BucketDev) * b.bk.size(), (void**)&ivf->bk_dev));
+    FAL_TRY(ctx->upload(ivf->bk_dev, b.bk.data(), sizeof(BucketDev) * b.bk.size()));
+    StageScope ts(ctx, ST_BUILD);
+    hipLaunchKernelGGL(kmeans_init_kernel, dim3((unsigned)ivf->ivf_waves), dim3(64), 0, st, b.X, ivf->d, ivf->bk_dev,
+                       ivf->n_ivf_buckets, ivf->centroids);
+    FAL_CHECK_HIP(hipGetLastError());
+    return FAL_OK;
+}
+
+// The rows' sparse form (k-means update: centroid_update_kernel; exact chains of the kept pairs: pairs16.hip), made before
+// anything else because the same pass over the float32 rows tells whether any component is negative (or not finite):
+// the float16 prefilters' error bound |f16-MFMA - exact| <= 1.3e-3 v + 2e-6 holds for NON-NEGATIVE rows only, so with
+// such rows the build and the searches of this index use the exact float32 kernels (same results, slower).
+// Also: the list sort's scratch and the bucket / list tables on the device.
+int sparsify_rows(Build& b) {
+    fal_ctx* ctx = b.ctx;
+    fal_ivf* ivf = b.ivf;
+    hipStream_t st = ctx->stream;
+    const int64_t n = ivf->n, n_buckets = b.n_buckets;
+    ScratchLayout LS, LB, LM;
+    const auto key_in = LS.array<uint32_t>(n), key_out = LS.array<uint32_t>(n);
+    const auto iota = LS.array<int32_t>(n);
+    const auto boff_dev = LB.array<int64_t>(n_buckets + 1), lbase_dev = LB.array<int64_t>(n_buckets + 1);   // `tab`, uploaded whole
+    const std::vector<int64_t> seg_off = sparsify_segments(b.bk.data(), b.bk.size());
+    std::vector<int64_t> tab(2 * (size_t)(n_buckets + 1));
+    for (int64_t i = 0; i <= n_buckets; ++i) {
+        tab[i] = b.bucket_off[i];
+        tab[n_buckets + 1 + i] = ivf->list_base[i];
+    }
+    const auto seg_dev = LM.array<int64_t>((int64_t)seg_off.size());
+    const auto neg_dev = LM.array<int32_t>(4);
+    FAL_TRY(LM.reserve(ctx, SLOT_MISC));
+    FAL_TRY(ctx->upload(seg_dev, seg_off.data(), sizeof(int64_t) * seg_off.size()));
+    FAL_CHECK_HIP(hipMemsetAsync(neg_dev, 0, 2 * sizeof(int64_t), st));
+    FAL_TRY(LB.reserve(ctx, SLOT_MISC2));
+    FAL_TRY(ctx->upload(boff_dev, tab.data(), sizeof(int64_t) * tab.size()));
+    FAL_TRY(ctx->pool_alloc(sizeof(uint16_t) * (size_t)n * kSparseW, (void**)&ivf->sp_cols));
+    FAL_TRY(ctx->pool_alloc(sizeof(float) * (size_t)n * kSparseW, (void**)&ivf->sp_vals));
+    // (with float16 rows at hand the searches may run the float16 list scan: its queries arrive as 256-byte sparse records)
+    // (rows of up to 400 columns: at 800 the dense gather is the faster form, list16s.hip)
+    if (b.X16 != nullptr && ivf->d <= 400) FAL_TRY(ctx->pool_alloc(sizeof(uint16_t) * (size_t)n * 2 * kSparseW, (void**)&ivf->sq16));
+    FAL_TRY(LS.reserve(ctx, SLOT_SORT2));
+    b.key_in = key_in; b.key_out = key_out; b.iota = iota; b.boff_dev = boff_dev; b.lbase_dev = lbase_dev;
+    {
+        StageScope ts(ctx, ST_BUILD);
+        hipLaunchKernelGGL(sparsify_rows_kernel, dim3((unsigned)seg_off.back()), dim3(256), 0, st, b.X, ivf->d, ivf->bk_dev, seg_dev,
+                           ivf->n_ivf_buckets, ivf->sp_cols, ivf->sp_vals, ivf->sq16, neg_dev);
+        FAL_CHECK_HIP(hipGetLastError());
+        hipLaunchKernelGGL(iota_i32_kernel, dim3((unsigned)std::min<int64_t>(ceil_div(n, 256), 4096)), dim3(256), 0, st, b.iota, n);
+        FAL_CHECK_HIP(hipGetLastError());
+    }
+    // the one synchronisation of the build (only when float16 rows were handed in: ~20 us of an empty queue against the
+    // tens of ms of the k-means passes that follow)
+    if (b.X16 != nullptr) {
+        FAL_CHECK_HIP(hipMemcpyAsync(ctx->fb_host + 6, neg_dev, 3 * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+        FAL_CHECK_HIP(hipStreamSynchronize(st));
+        ivf->rows_signed = ctx->fb_host[6] != 0 ? 1 : 0;
+        ivf->rows_f16 = ctx->fb_host[7] == 0 ? 1 : 0;
+        ivf->rows_many = ctx->fb_host[8] != 0 ? 1 : 0;
+        ctx->counters[6] |= ivf->rows_signed;
+    } else {
+        ivf->rows_signed = -1;        // not known on the host yet: fal_ivf_attach_prefilter_ex reads it if it needs it
+        FAL_TRY(ctx->pool_alloc(sizeof(int32_t) * 2, (void**)&ivf->neg_dev));
+        FAL_CHECK_HIP(hipMemcpyAsync(ivf->neg_dev, neg_dev, 2 * sizeof(int32_t), hipMemcpyDeviceToDevice, st));
+    }
+    return FAL_OK;
+}
+
+// the job tables of the assignment kernels (plan_assign) and those kernels' scratch
+int upload_jobs(Build& b) {
+    fal_ctx* ctx = b.ctx;
+    const fal_ivf* ivf = b.ivf;
+    // float16 rows at hand: the prefiltered assignment (assign16.hip; identical results)
+    const bool use16 = b.X16 != nullptr && assign16_supports(ivf->d) && ivf->rows_signed == 0;
+    b.plan = plan_assign(b.bk.data(), b.bk.size(), ctx->num_cus, use16);
+    const AssignPlan& p = b.plan;
+    if (!p.wide.empty()) {
+        FAL_TRY(ctx->reserve(SLOT_JOBS2, sizeof(AssignJob) * p.wide.size(), (void**)&b.wide_dev));
+        FAL_TRY(ctx->upload(b.wide_dev, p.wide.data(), sizeof(AssignJob) * p.wide.size()));
+        FAL_TRY(ctx->reserve(SLOT_SIMS, sizeof(unsigned long long) * (size_t)ivf->n, (void**)&b.keys));
+    }
+    if (!p.dense.empty()) {
+        FAL_TRY(ctx->reserve(SLOT_JOBS, sizeof(DenseJob) * p.dense.size(), (void**)&b.dense_dev));
+        FAL_TRY(ctx->upload(b.dense_dev, p.dense.data(), sizeof(DenseJob) * p.dense.size()));
+    }
+    if (!p.half.empty()) {
+        FAL_TRY(ctx->reserve(SLOT_INV, sizeof(AssignJob) * p.half.size(), (void**)&b.half_dev));
+        FAL_TRY(ctx->upload(b.half_dev, p.half.data(), sizeof(AssignJob) * p.half.size()));
+        FAL_TRY(ctx->reserve(SLOT_INVCNT, sizeof(uint16_t) * (size_t)ivf->total_lists * ivf->d + 64, &b.C16));
+    }
+    return FAL_OK;
+}
+
+// k-means pass `it`: every row of an indexed bucket to its best centroid
+int assign_pass(Build& b, int it) {
+    fal_ctx* ctx = b.ctx;
+    fal_ivf* ivf = b.ivf;
+    const AssignPlan& p = b.plan;
+    const bool last = it == b.kmeans_iters;
+    if (!p.half.empty()) {
+        if (it == 0) {                   // (later passes: centroid_update_kernel writes the float16 copy of what it changes)
+            StageScope ts(ctx, ST_BUILD);
+            FAL_TRY(launch_cvt_f16(ctx, ivf->centroids, b.C16, ivf->total_lists * ivf->d));
+        }
+        // the final pass leaves its approximate similarities behind for the coarse quantiser (coarse16.hip)
+        if (last && p.dense.empty() && p.wide.empty()) {
+            ivf->ckeys_stride = ckeys_stride_of(p.max_n_list);
+            // n x stride keys: ONE 2,048-list bucket sizes them for every row of the partition (41 GB at 10 M rows).  Beyond
+            // a budget (FALCON_CKEYS_MB, default 32 GB), or when the allocation fails, the index is built without them and the
+            // coarse quantiser scans in float32 (search.hip `from_keys`: the same probes, slower).
+            if (!ckeys_fit(ivf->n, ivf->ckeys_stride, b.ckeys_budget) ||
+                ctx->pool_alloc(ckeys_bytes(ivf->n, ivf->ckeys_stride), (void**)&ivf->ckeys) != FAL_OK) {
+                ivf->ckeys = nullptr;
+                (void)hipGetLastError();
+            }
+        }
+        FAL_TRY(launch_assign16(ctx, ST_BUILD, b.X16, b.X, b.C16, ivf->centroids, ivf->d, b.half_dev, p.n_single, p.n_merge, p.n_group,
+                                ivf->n, ivf->assign, last ? ivf->ckeys : nullptr, ivf->ckeys_stride, ivf->sp_cols, ivf->sp_vals,
+                                p.merge_max_lists, p.merge_rows));
+    }
+    if (!p.dense.empty())
+        FAL_TRY(launch_dense(ctx, ST_BUILD, EPI_ARGMAX, b.X, ivf->centroids, ivf->d, b.dense_dev, (int)p.dense.size(), 0, p.dtiles,
+                             nullptr, 0, ivf->assign));
+    if (p.n_wide + p.n_wave > 0)
+        FAL_TRY(launch_assign(ctx, ST_BUILD, b.X, ivf->centroids, ivf->d, b.wide_dev, p.n_wide, p.n_wave, ivf->n, b.keys, ivf->assign));
+    return FAL_OK;
+}
+
+// stable sort of the rows by (global) list: perm = rows in list order, list_off = the lists' boundaries
+int sort_by_list(Build& b) {
+    fal_ctx* ctx = b.ctx;
+    fal_ivf* ivf = b.ivf;
+    hipStream_t st = ctx->stream;
+    const int64_t n = ivf->n, total = ivf->total_lists;
+    hipLaunchKernelGGL(list_key_kernel, dim3((unsigned)std::min<int64_t>(ceil_div(n, 256), 8192)), dim3(256), 0, st, ivf->assign,
+                       b.boff_dev, b.lbase_dev, (int)b.n_buckets, n, b.key_in);
+    FAL_CHECK_HIP(hipGetLastError());
+    FAL_TRY(sort_pairs_u32_i32(ctx, b.key_in, b.key_out, b.iota, ivf->perm, n, list_sort_end_bit(total), SLOT_SORT));
+    hipLaunchKernelGGL(list_bounds_kernel, dim3((unsigned)std::min<int64_t>(ceil_div(total + 1, 256), 4096)), dim3(256), 0, st,
+                       b.key_out, n, total, ivf->list_off);
+    FAL_CHECK_HIP(hipGetLastError());
+    return FAL_OK;
+}
+
+// the members of every list in row order: after the first (global) sort every later one only re-orders the rows inside the
+// indexed buckets, one wave per bucket
+int sort_lists(Build& b) {
+    if (!b.sorted_once || !bucket_sort_serves(b.plan.max_n_list)) {
+        b.sorted_once = true;
+        return sort_by_list(b);
+    }
+    const fal_ivf* ivf = b.ivf;
+    hipLaunchKernelGGL(bucket_list_sort_kernel, dim3((unsigned)ivf->n_ivf_buckets), dim3(64), 0, b.ctx->stream, ivf->assign,
+                       ivf->bk_dev, ivf->n_ivf_buckets, ivf->perm, ivf->list_off);
+    FAL_CHECK_HIP(hipGetLastError());
+    return FAL_OK;
+}
+
+int update_centroids(Build& b) {
+    const fal_ivf* ivf = b.ivf;
+    hipLaunchKernelGGL(centroid_update_kernel, dim3((unsigned)ivf->ivf_waves), dim3(64), 0, b.ctx->stream, ivf->sp_cols, ivf->sp_vals,
+                       b.X, ivf->d, ivf->perm, ivf->list_off, ivf->bk_dev, ivf->n_ivf_buckets, ivf->centroids,
+                       reinterpret_cast<__half*>(b.C16));
+    FAL_CHECK_HIP(hipGetLastError());
+    return FAL_OK;
+}
+
+// every bucket is flat: the list offsets ARE the bucket offsets -- known on the host, uploaded, no kernel (a one-workgroup
+// scan here sat 585 us in the two-stream trace of the headline, waiting for a CU behind the other partition's matrix kernel)
+int finish_flat(Build& b) {
+    fal_ivf* ivf = b.ivf;
+    const std::vector<int64_t> off = flat_list_off(b.bucket_off, ivf->list_base.data(), b.n_buckets);
+    FAL_TRY(b.ctx->upload(ivf->list_off, off.data(), sizeof(int64_t) * off.size()));
+    ivf->Xl = b.X;
+    return FAL_OK;
+}
+}  // namespace
+
 extern "C" {
 
 int fal_ivf_destroy(fal_ivf* ivf) {
@@ -489,308 +751,31 @@ int fal_ivf_build_x16(fal_ctx* ctx, const float* X, const void* X16, int64_t n, 
     fal::CallScope _call(ctx);
     FAL_REQUIRE(ctx && out, FAL_EINVAL, "fal_ivf_build: NULL ctx/out");
     *out = nullptr;
-    FAL_REQUIRE(n >= 0 && n < (int64_t)INT32_MAX, FAL_EUNSUPPORTED, "fal_ivf_build: n must be < 2^31 per partition");
-    FAL_REQUIRE(low_dim >= 8 && low_dim <= FAL_MAX_LOW_DIM && low_dim % 8 == 0, FAL_EUNSUPPORTED,
-                "fal_ivf_build: low_dim must be a multiple of 8 in [8, %d]", FAL_MAX_LOW_DIM);
-    FAL_REQUIRE(n_buckets >= 0 && (n_buckets == 0 || (bucket_off && n_list)), FAL_EINVAL, "fal_ivf_build: NULL bucket arrays");
-    FAL_REQUIRE(kmeans_iters >= 0, FAL_EINVAL, "fal_ivf_build: kmeans_iters < 0");
-    {
-        bool any_ivf = false;
-        for (int64_t b = 0; b < n_buckets; ++b) any_ivf |= n_list[b] > 1;
-        FAL_REQUIRE(n == 0 || X || !any_ivf, FAL_EINVAL, "fal_ivf_build: X may only be NULL when every bucket is flat");
-    }
-    if (n_buckets > 0) {
-        FAL_REQUIRE(bucket_off[0] == 0 && bucket_off[n_buckets] == n, FAL_EINVAL,
-                    "fal_ivf_build: bucket_off must start at 0 and end at n");
-    } else {
-        FAL_REQUIRE(n == 0, FAL_EINVAL, "fal_ivf_build: no buckets but n > 0");
-    }
-    ctx->counters[6] = 0;      // bit 0: rows of an indexed bucket, bit 1: rows handed to the flat prefilter have negative / non-finite
-                               // components -> this index runs without float16 prefilters (fal_ctx_counter 6)
-    fal_ivf* ivf = new fal_ivf();
-    ivf->ctx = ctx;
-    ivf->n = n;
-    ivf->d = low_dim;
-    ivf->X = X;
-    ivf->bucket_off.assign(bucket_off, bucket_off + n_buckets + 1 * (n_buckets > 0));
-    if (n_buckets == 0) ivf->bucket_off.assign(1, 0);
-    ivf->n_list.assign(n_list, n_list + n_buckets);
-    ivf->list_base.resize(n_buckets + 1);
-    std::vector<BucketDev> bk;
-    int64_t total = 0, waves = 0;
-    for (int64_t b = 0; b < n_buckets; ++b) {
-        const int64_t nb = bucket_off[b + 1] - bucket_off[b];
-        if (nb < 0 || n_list[b] < 1 || n_list[b] > FAL_MAX_N_LIST || (nb > 0 && n_list[b] > nb) || nb > INT32_MAX) {
-            set_error("fal_ivf_build: bucket %lld: size %lld, n_list %d invalid", (long long)b, (long long)nb, n_list[b]);
-            delete ivf;
-            return FAL_EINVAL;
-        }
-        ivf->list_base[b] = total;
-        if (n_list[b] > 1) {
-            bk.push_back({bucket_off[b], total, (int32_t)nb, n_list[b], waves});
-            waves += n_list[b];
-        }
-        total += n_list[b];
-    }
-    ivf->list_base[n_buckets] = total;
-    ivf->total_lists = total;
-    ivf->n_ivf_buckets = (int)bk.size();
-    ivf->ivf_waves = waves;
-    hipStream_t st = ctx->stream;
-    int rc = FAL_OK;
-    auto fail = [&](int code) {
-        fal_ivf_destroy(ivf);
-        return code;
-    };
-#define B_TRY(e) do { rc = (e); if (rc != FAL_OK) return fail(rc); } while (0)
-#define B_HIP(e) do { hipError_t _e = (e); if (_e != hipSuccess) { set_error("%s:%d %s: %s", __FILE__, __LINE__, #e, hipGetErrorString(_e)); return fail(_e == hipErrorOutOfMemory ? FAL_ENOMEM : FAL_EHIP); } } while (0)
-
-    B_TRY(ctx->pool_alloc(sizeof(int32_t) * (size_t)n, (void**)&ivf->perm));
-    B_TRY(ctx->pool_alloc(sizeof(int32_t) * (size_t)n, (void**)&ivf->assign));
-    B_TRY(ctx->pool_alloc(sizeof(int64_t) * (size_t)(total + 1), (void**)&ivf->list_off));
-    B_TRY(ctx->pool_alloc(sizeof(int64_t) * (size_t)(total + 1), (void**)&ivf->counts));
-    B_TRY(ctx->pool_alloc(sizeof(float) * (size_t)total * low_dim, (void**)&ivf->centroids));
-    ctx->stage_reset(ST_BUILD);
-
-    // counts: flat buckets hold all their rows in their single list
-    {
-        std::vector<int64_t> cnt_host(total + 1, 0), qlb;
-        for (int64_t b = 0; b < n_buckets; ++b)
-            if (n_list[b] == 1) cnt_host[ivf->list_base[b]] = bucket_off[b + 1] - bucket_off[b];
-        B_TRY(ctx->upload(ivf->counts, cnt_host.data(), sizeof(int64_t) * (total + 1)));
-    }
-    B_HIP(hipMemsetAsync(ivf->assign, 0, sizeof(int32_t) * (size_t)n, st));
-    B_HIP(hipMemsetAsync(ivf->centroids, 0, sizeof(float) * (size_t)total * low_dim, st));
-    if (n > 0) {
-        hipLaunchKernelGGL(iota_i32_kernel, dim3((unsigned)std::min<int64_t>(ceil_div(n, 256), 4096)), dim3(256), 0, st,
-                           ivf->perm, n);
-        B_HIP(hipGetLastError());
-    }
-    if (!bk.empty()) {
-        B_TRY(ctx->pool_alloc(sizeof(BucketDev) * bk.size(), (void**)&ivf->bk_dev));
-        B_TRY(ctx->upload(ivf->bk_dev, bk.data(), sizeof(BucketDev) * bk.size()));
-        const BucketDev* bkd = (const BucketDev*)ivf->bk_dev;
-        const int nbk = (int)bk.size();
-        {
-            StageScope ts(ctx, ST_BUILD);
-            hipLaunchKernelGGL(kmeans_init_kernel, dim3((unsigned)waves), dim3(64), 0, st, X, low_dim, bkd, nbk,
-                               ivf->centroids);
-        B_HIP(hipGetLastError());
-        }
-        // The rows' sparse form (k-means update: centroid_update_kernel; exact chains of the kept pairs: pairs16.hip), made before
-        // anything else because the same pass over the float32 rows tells whether any component is negative (or not finite):
-        // the float16 prefilters' error bound |f16-MFMA - exact| <= 1.3e-3 v + 2e-6 holds for NON-NEGATIVE rows only, so with
-        // such rows the build and the searches of this index use the exact float32 kernels (same results, slower).
-        uint16_t* sp_cols = nullptr;
-        float* sp_vals = nullptr;
-        ScratchLayout LS, LB;
-        const auto key_in = LS.array<uint32_t>(n), key_out = LS.array<uint32_t>(n);
-        const auto iota = LS.array<int32_t>(n);
-        const auto boff_dev = LB.array<int64_t>(n_buckets + 1), lbase_dev = LB.array<int64_t>(n_buckets + 1);   // `tab`, uploaded whole
-        int end_bit = 1;
-        while (end_bit < 32 && (1ll << end_bit) < total) ++end_bit;
-        {
-            std::vector<int64_t> seg_off(bk.size() + 1, 0), tab(2 * (size_t)(n_buckets + 1));
-            for (size_t i = 0; i < bk.size(); ++i) seg_off[i + 1] = seg_off[i] + ceil_div(bk[i].n, 256);
-            for (int64_t b = 0; b <= n_buckets; ++b) {
-                tab[b] = bucket_off[b];
-                tab[n_buckets + 1 + b] = ivf->list_base[b];
-            }
-            ScratchLayout LM;
-            const auto seg_dev = LM.array<int64_t>((int64_t)seg_off.size());
-            const auto neg_dev = LM.array<int32_t>(4);
-            B_TRY(LM.reserve(ctx, SLOT_MISC));
-            B_TRY(ctx->upload(seg_dev, seg_off.data(), sizeof(int64_t) * seg_off.size()));
-            B_HIP(hipMemsetAsync(neg_dev, 0, 2 * sizeof(int64_t), st));
-            B_TRY(LB.reserve(ctx, SLOT_MISC2));
-            B_TRY(ctx->upload(boff_dev, tab.data(), sizeof(int64_t) * tab.size()));
-            B_TRY(ctx->pool_alloc(sizeof(uint16_t) * (size_t)n * kSparseW, (void**)&ivf->sp_cols));
-            B_TRY(ctx->pool_alloc(sizeof(float) * (size_t)n * kSparseW, (void**)&ivf->sp_vals));
-            sp_cols = ivf->sp_cols;
-            sp_vals = ivf->sp_vals;
-            // (with float16 rows at hand the searches may run the float16 list scan: its queries arrive as 256-byte sparse records)
-            // (rows of up to 400 columns: at 800 the dense gather is the faster form, list16s.hip)
-            if (X16 != nullptr && low_dim <= 400) B_TRY(ctx->pool_alloc(sizeof(uint16_t) * (size_t)n * 2 * kSparseW, (void**)&ivf->sq16));
-            B_TRY(LS.reserve(ctx, SLOT_SORT2));
-            {
-                StageScope ts(ctx, ST_BUILD);
-                hipLaunchKernelGGL(sparsify_rows_kernel, dim3((unsigned)seg_off.back()), dim3(256), 0, st, X, low_dim, bkd, seg_dev,
-                                   nbk, sp_cols, sp_vals, ivf->sq16, neg_dev);
-                B_HIP(hipGetLastError());
-                hipLaunchKernelGGL(iota_i32_kernel, dim3((unsigned)std::min<int64_t>(ceil_div(n, 256), 4096)), dim3(256), 0, st, iota, n);
-                B_HIP(hipGetLastError());
-            }
-            // the one synchronisation of the build (only when float16 rows were handed in: ~20 us of an empty queue against the
-            // tens of ms of the k-means passes that follow)
-            if (X16 != nullptr) {
-                B_HIP(hipMemcpyAsync(ctx->fb_host + 6, neg_dev, 3 * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-                B_HIP(hipStreamSynchronize(st));
-                ivf->rows_signed = ctx->fb_host[6] != 0 ? 1 : 0;
-                ivf->rows_f16 = ctx->fb_host[7] == 0 ? 1 : 0;
-                ivf->rows_many = ctx->fb_host[8] != 0 ? 1 : 0;
-                ctx->counters[6] |= ivf->rows_signed;
-            } else {
-                ivf->rows_signed = -1;        // not known on the host yet: fal_ivf_attach_prefilter_ex reads it if it needs it
-                B_TRY(ctx->pool_alloc(sizeof(int32_t) * 2, (void**)&ivf->neg_dev));
-                B_HIP(hipMemcpyAsync(ivf->neg_dev, neg_dev, 2 * sizeof(int32_t), hipMemcpyDeviceToDevice, st));
-            }
-        }
-        // Buckets with few lists (<= kAssignMaxLists) are assigned by the shared-stream kernel (assign.hip): jobs =
-        // (row segment) x (group of <= 128 centroids).  Buckets with many lists keep the row-resident kernel, whose
-        // 32-row tile is amortised over their many centroid chunks.
-        constexpr int kAssignMaxLists = 512;
-        std::vector<AssignJob> ajobs;
-        std::vector<DenseJob> djobs;
-        int64_t dtiles = 0;
-        // rows per job: long segments amortise the resident centroid tiles, but with only a few indexed buckets long
-        // segments leave most CUs idle -- aim for >= 4 workgroups per CU, between 256 and kAssignSeg rows
-        int64_t work_rows = 0;
-        for (const BucketDev& b : bk)
-            if (b.n_list > 64 && b.n_list <= kAssignMaxLists) work_rows += (int64_t)b.n * ceil_div(b.n_list, kAssignGroup);
-        const int64_t seg = std::min<int64_t>(kAssignSeg, std::max<int64_t>(256, ceil_div(work_rows, (int64_t)ctx->num_cus * 4 * 32) * 32));
-        // buckets with one or two centroid tiles take one-wave jobs (a 4-wave workgroup would idle most of its waves)
-        std::vector<AssignJob> wjobs;
-        int64_t wave_rows = 0;
-        for (const BucketDev& b : bk)
-            if (b.n_list <= 64) wave_rows += (int64_t)b.n * ceil_div(b.n_list, 32);
-        const int64_t wseg = std::min<int64_t>(kAssignSeg, std::max<int64_t>(256, ceil_div(wave_rows, (int64_t)ctx->num_cus * 16 * 32) * 32));
-        // buckets with <= 128 lists and float16 rows at hand: the prefiltered assignment (assign16.hip; identical results)
-        const bool use16 = X16 != nullptr && assign16_supports(low_dim) && ivf->rows_signed == 0;
-        std::vector<AssignJob> hjobs, mjobs, gjobs;    // single-group jobs; merge jobs and their group jobs (129..kAssignMergeLists lists)
-        int merge_max_lists = 0;
-        int64_t merge_rows = 0;                        // rows of the merge buckets: the partial arrays' rows (AssignJob::part0)
-        for (const BucketDev& b : bk) {
-            if (use16 && b.n_list <= kAssignGroup) {
-                for (int64_t s0 = 0; s0 < b.n; s0 += kAssignSeg)
-                    hjobs.push_back({b.row0 + s0, b.list0, (int32_t)std::min<int64_t>(kAssignSeg, b.n - s0), b.n_list, 0, 0});
-            } else if (use16 && b.n_list <= kAssignMergeLists) {
-                merge_max_lists = std::max(merge_max_lists, (int)b.n_list);
-                for (int64_t s0 = 0; s0 < b.n; s0 += kAssignSeg) {
-                    const int32_t nr = (int32_t)std::min<int64_t>(kAssignSeg, b.n - s0);
-                    mjobs.push_back({b.row0 + s0, b.list0, nr, b.n_list, 0, (int32_t)merge_rows});
-                    for (int t0 = 0; t0 < b.n_list; t0 += kAssignGroup)      // the groups of a segment next to each other: they
-                        gjobs.push_back({b.row0 + s0, b.list0 + t0, nr, std::min(kAssignGroup, b.n_list - t0), t0, (int32_t)merge_rows});   // share its rows in L2
-                    merge_rows += nr;
-                }
-            } else if (b.n_list <= 64) {
-                for (int64_t s0 = 0; s0 < b.n; s0 += wseg)
-                    for (int t0 = 0; t0 < b.n_list; t0 += 32)
-                        wjobs.push_back({b.row0 + s0, b.list0 + t0, (int32_t)std::min<int64_t>(wseg, b.n - s0),
-                                         std::min(32, b.n_list - t0), t0, 0});
-            } else if (b.n_list <= kAssignMaxLists) {
-                for (int64_t s0 = 0; s0 < b.n; s0 += seg)
-                    for (int t0 = 0; t0 < b.n_list; t0 += kAssignGroup)
-                        ajobs.push_back({b.row0 + s0, b.list0 + t0, (int32_t)std::min<int64_t>(seg, b.n - s0),
-                                         std::min(kAssignGroup, b.n_list - t0), t0, 0});
-            } else {
-                djobs.push_back({b.row0, b.list0, 0, dtiles, b.n, b.n_list, 0});
-                dtiles += ceil_div(b.n, 32);
-            }
-        }
-        AssignJob* ajobs_dev = nullptr;
-        DenseJob* djobs_dev = nullptr;
-        unsigned long long* keys = nullptr;
-        const int64_t n_wide = (int64_t)ajobs.size(), n_wave = (int64_t)wjobs.size();
-        ajobs.insert(ajobs.end(), wjobs.begin(), wjobs.end());
-        if (!ajobs.empty()) {
-            B_TRY(ctx->reserve(SLOT_JOBS2, sizeof(AssignJob) * ajobs.size(), (void**)&ajobs_dev));
-            B_TRY(ctx->upload(ajobs_dev, ajobs.data(), sizeof(AssignJob) * ajobs.size()));
-            B_TRY(ctx->reserve(SLOT_SIMS, sizeof(unsigned long long) * (size_t)n, (void**)&keys));
-        }
-        if (!djobs.empty()) {
-            B_TRY(ctx->reserve(SLOT_JOBS, sizeof(DenseJob) * djobs.size(), (void**)&djobs_dev));
-            B_TRY(ctx->upload(djobs_dev, djobs.data(), sizeof(DenseJob) * djobs.size()));
-        }
-        AssignJob* hjobs_dev = nullptr;
-        void* C16 = nullptr;
-        const int64_t n_single = (int64_t)hjobs.size(), n_merge = (int64_t)mjobs.size(), n_group = (int64_t)gjobs.size();
-        hjobs.insert(hjobs.end(), mjobs.begin(), mjobs.end());
-        hjobs.insert(hjobs.end(), gjobs.begin(), gjobs.end());
-        if (!hjobs.empty()) {
-            B_TRY(ctx->reserve(SLOT_INV, sizeof(AssignJob) * hjobs.size(), (void**)&hjobs_dev));
-            B_TRY(ctx->upload(hjobs_dev, hjobs.data(), sizeof(AssignJob) * hjobs.size()));
-            B_TRY(ctx->reserve(SLOT_INVCNT, sizeof(uint16_t) * (size_t)total * low_dim + 64, &C16));
-        }
-        // stable sort of the rows by (global) list: perm = rows in list order, list_off = the lists' boundaries
-        auto sort_by_list = [&]() -> int {
-            hipLaunchKernelGGL(list_key_kernel, dim3((unsigned)std::min<int64_t>(ceil_div(n, 256), 8192)), dim3(256), 0, st, ivf->assign,
-                               boff_dev, lbase_dev, (int)n_buckets, n, key_in);
-            FAL_CHECK_HIP(hipGetLastError());
-            FAL_TRY(sort_pairs_u32_i32(ctx, key_in, key_out, iota, ivf->perm, n, end_bit, SLOT_SORT));
-            hipLaunchKernelGGL(list_bounds_kernel, dim3((unsigned)std::min<int64_t>(ceil_div(total + 1, 256), 4096)), dim3(256), 0, st,
-                               key_out, n, total, ivf->list_off);
-            FAL_CHECK_HIP(hipGetLastError());
-            return FAL_OK;
-        };
-        // after the first (global) sort every later one only re-orders the rows inside the IVF buckets: one wave per bucket
-        int max_nl_all = 0;
-        for (const BucketDev& b : bk) max_nl_all = std::max(max_nl_all, (int)b.n_list);
-        bool sorted_once = false;
-        auto sort_buckets = [&]() -> int {
-            if (!sorted_once || max_nl_all > kBucketSortMaxLists) {
-                sorted_once = true;
-                return sort_by_list();
-            }
-            hipLaunchKernelGGL(bucket_list_sort_kernel, dim3((unsigned)nbk), dim3(64), 0, st, ivf->assign, bkd, nbk, ivf->perm, ivf->list_off);
-            FAL_CHECK_HIP(hipGetLastError());
-            return FAL_OK;
-        };
-        for (int it = 0; it <= kmeans_iters; ++it) {
-            if (!hjobs.empty()) {
-                if (it == 0) {                   // (later passes: centroid_update_kernel writes the float16 copy of what it changes)
-                    StageScope ts(ctx, ST_BUILD);
-                    B_TRY(launch_cvt_f16(ctx, ivf->centroids, C16, total * low_dim));
-                }
-                // the final pass leaves its approximate similarities behind for the coarse quantiser (coarse16.hip)
-                if (it == kmeans_iters && djobs.empty() && ajobs.empty()) {
-                    int max_nl = 0;
-                    for (const BucketDev& b : bk) max_nl = std::max(max_nl, (int)b.n_list);
-                    ivf->ckeys_stride = kAssignGroup * (int)ceil_div(max_nl, kAssignGroup);
-                    // n x stride keys: ONE 2,048-list bucket sizes them for every row of the partition (41 GB at 10 M rows).  Beyond
-                    // a budget (FALCON_CKEYS_MB, default 32 GB), or when the allocation fails, the index is built without them and the
-                    // coarse quantiser scans in float32 (search.hip `from_keys`: the same probes, slower).
-                    const char* ke = getenv("FALCON_CKEYS_MB");
-                    const size_t budget = (ke ? (size_t)atoll(ke) : (size_t)32768) << 20;
-                    const size_t key_bytes = sizeof(uint16_t) * (size_t)n * ivf->ckeys_stride;
-                    if (key_bytes > budget || ctx->pool_alloc(key_bytes, (void**)&ivf->ckeys) != FAL_OK) {
-                        ivf->ckeys = nullptr;
-                        (void)hipGetLastError();
-                    }
-                }
-                B_TRY(launch_assign16(ctx, ST_BUILD, X16, X, C16, ivf->centroids, low_dim, hjobs_dev, n_single, n_merge, n_group, n,
-                                      ivf->assign, it == kmeans_iters ? ivf->ckeys : nullptr, ivf->ckeys_stride, sp_cols, sp_vals,
-                                      merge_max_lists, merge_rows));
-            }
-            if (!djobs.empty())
-                B_TRY(launch_dense(ctx, ST_BUILD, EPI_ARGMAX, X, ivf->centroids, low_dim, djobs_dev, (int)djobs.size(), 0,
-                                   dtiles, nullptr, 0, ivf->assign));
-            if (n_wide + n_wave > 0)
-                B_TRY(launch_assign(ctx, ST_BUILD, X, ivf->centroids, low_dim, ajobs_dev, n_wide, n_wave, n, keys, ivf->assign));
+    IvfOwner owner;
+    Build b{ctx, nullptr, X, X16, bucket_off, n_list, n_buckets, kmeans_iters, ckeys_budget_bytes(ckeys_mb_env())};
+    FAL_TRY(new_index(ctx, X, n, low_dim, bucket_off, n_buckets, n_list, kmeans_iters, owner, b.bk));
+    b.ivf = owner.get();
+    FAL_TRY(alloc_index(b));
+    if (!b.bk.empty()) {
+        FAL_TRY(sparsify_rows(b));
+        FAL_TRY(upload_jobs(b));
+        for (int it = 0;; ++it) {
+            FAL_TRY(assign_pass(b, it));
             if (it == kmeans_iters) break;   // final assignment against the final centroids
             StageScope ts(ctx, ST_BUILD);
-            B_TRY(sort_buckets());
-            hipLaunchKernelGGL(centroid_update_kernel, dim3((unsigned)waves), dim3(64), 0, st, sp_cols, sp_vals, X, low_dim,
-                               ivf->perm, ivf->list_off, bkd, nbk, ivf->centroids, reinterpret_cast<__half*>(C16));
-            B_HIP(hipGetLastError());
+            FAL_TRY(sort_lists(b));
+            FAL_TRY(update_centroids(b));
         }
         StageScope ts(ctx, ST_BUILD);
-        B_TRY(sort_buckets());       // (the sparse rows stay with the index: pairs16.hip evaluates its exact chains over them)
+        FAL_TRY(sort_lists(b));          // (the sparse rows stay with the index: pairs16.hip evaluates its exact chains over them)
         // the float32 rows in list order are made on demand (fal_ivf_ensure_xl: the staged fine scan and the staged coarse scan read
         // them; the default path -- coarse quantiser from the build's keys, float16 prefilter -- does not: 16 GB at 10 M spectra)
-        ivf->Xl = nullptr;
+        b.ivf->Xl = nullptr;
     } else {
-        // every bucket is flat: the list offsets ARE the bucket offsets -- known on the host, uploaded, no kernel (a one-workgroup
-        // scan here sat 585 us in the two-stream trace of the headline, waiting for a CU behind the other partition's matrix kernel)
-        std::vector<int64_t> off_host((size_t)total + 1, 0);
-        for (int64_t b = 0; b < n_buckets; ++b) off_host[(size_t)ivf->list_base[b] + 1] = bucket_off[b + 1];
-        for (int64_t g = 1; g <= total; ++g) off_host[(size_t)g] = std::max(off_host[(size_t)g], off_host[(size_t)g - 1]);
-        B_TRY(ctx->upload(ivf->list_off, off_host.data(), sizeof(int64_t) * (size_t)(total + 1)));
-        ivf->Xl = X;
+        FAL_TRY(finish_flat(b));
     }
-    B_HIP(hipGetLastError());
-#undef B_TRY
-#undef B_HIP
-    *out = ivf;
+    FAL_CHECK_HIP(hipGetLastError());
+    *out = owner.release();
     return FAL_OK;
 }
 

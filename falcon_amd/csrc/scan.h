@@ -2,6 +2,7 @@
 #pragma once
 #include "common.h"
 #include "simtile.h"
+#include "buildplan.h"
 
 namespace fal {
 
@@ -14,6 +15,8 @@ constexpr size_t kSimsSlack = 2048;
 // FALCON_SIMS_MB as given (default 2048), read at every call (search.hip).  The search keeps its first reading for the process
 // and applies a floor (searchplan.h: sims_cap_floats); fal_ctx_plan sizes the slot from the value as it stands.
 size_t sims_mb_env();
+// FALCON_CKEYS_MB as given (default 32768): the budget of the coarse keys a build may leave behind (buildplan.h: ckeys_fit)
+size_t ckeys_mb_env();
 
 struct SelectArgs {
     const float* sims;       // sims buffer of the current batch
@@ -63,22 +66,8 @@ int launch_flat_exact_small(fal_ctx* ctx, const float* X, int d, const DenseJob*
 int launch_dense(fal_ctx* ctx, int stage, int epi, const float* Q, const float* Cm, int d, const DenseJob* jobs,
                  int n_jobs, int64_t tile_begin, int64_t n_tiles, float* sims, int64_t sims_base, int32_t* assign,
                  int64_t xcd_list_tiles = 0);
-// Shared-stream list assignment (assign.hip): job = (a segment of a bucket's rows) x (up to 128 of its centroids)
-constexpr int kAssignSeg = 2048;      // rows per segment
-constexpr int kAssignGroup = 128;     // centroids per job: one 32-centroid tile per wave
-constexpr int kAssignMergeLists = 2048;     // lists per bucket up to which the float16 assignment runs in groups of 128 + a merge
-                                            // (16 groups = 64 subgroups of 32; round 4 stopped at 512 and sent a 1,024-list
-                                            // bucket -- `--batch_size 65536` on 45 k-row windows -- to the exact fp32 kernels:
-                                            // build 584 ms instead of 77 per 10 M spectra, profiles/NOTES.md r5)
-struct AssignJob {
-    int64_t row0;        // first row of the segment (sorted rows = rows of X)
-    int64_t cent0;       // global row of the group's first centroid
-    int32_t nrows;       // rows in the segment (<= kAssignSeg)
-    int32_t ncent;       // centroids in the group (1..kAssignGroup)
-    int32_t id_base;     // bucket-local list id of the group's first centroid
-    int32_t part0;       // merge / group jobs (assign16.hip): position of the segment's first row among the rows of ALL merge
-                         // buckets = the row index of the partial arrays (0 elsewhere)
-};
+// Shared-stream list assignment (assign.hip): job = (a segment of a bucket's rows) x (up to 128 of its centroids) -- AssignJob,
+// kAssignSeg / kAssignGroup / kAssignMergeLists and the job tables of a build: buildplan.h
 // keys: u64[n] scratch (cleared here); assign[i] is written for every row a job covers
 // jobs[0, n_jobs): 4-wave jobs (<= 128 centroids each); jobs[n_jobs, n_jobs + n_wave_jobs): one-wave jobs (<= 32 centroids)
 int launch_assign(fal_ctx* ctx, int stage, const float* X, const float* centroids, int d, const AssignJob* jobs, int64_t n_jobs,

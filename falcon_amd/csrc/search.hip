@@ -267,6 +267,11 @@ size_t sims_mb_env() {
     return e ? (size_t)atoll(e) : 2048;
 }
 
+size_t ckeys_mb_env() {
+    const char* e = getenv("FALCON_CKEYS_MB");
+    return e ? (size_t)atoll(e) : 32768;
+}
+
 static size_t sims_capacity_floats() {
     static const size_t cap = sims_cap_floats(sims_mb_env());      // (read once per process)
     return cap;

@@ -134,6 +134,42 @@ def test_ivf_build_matches_oracle(ctx, sizes, nlists, d):
             assert np.array_equal(cent[lb[b]:lb[b + 1]], C)
 
 
+def test_ivf_build_with_every_assignment_class_side_by_side(ctx, tmp_path):
+    """one index whose buckets take every class of the build plan (csrc/buildplan.h) at once, built plain (one-wave, 4-wave and
+    row-resident exact kernels) and with float16 rows (single-group and merge jobs of the float16 assignment; 2,049 lists stay
+    row-resident): job tables of several classes in one upload, `part0` of the merge jobs behind the three-segment 129-list
+    bucket above 0.  Both builds equal the oracle bucket by bucket, and each other bit for bit."""
+    import torch
+    from tests import build_cases as bc
+    from tests import test_buildplan_cpu as plan
+    lib = plan.load(tmp_path)
+    sizes, nlists = bc.GPU_SIZES, bc.GPU_LISTS
+    off = np.array(bc.offsets(sizes))
+    bk = plan.lists(lib, off, nlists)[1]
+    for use16 in (True, False):                               # the plan's own classes first: none the build should run is empty
+        p = plan.check_assign(lib, bk, 256, use16)
+        filled = {bc.SINGLE: p["n_single"], bc.MERGE: p["n_merge"], bc.WAVE: p["n_wave"], bc.WIDE: p["n_wide"], bc.DENSE: len(p["dense"])}
+        assert {c for c, n in filled.items() if n > 0} == set(bc.GPU_CLASSES[use16])
+    assert max(j[5] for j in plan.check_assign(lib, bk, 256, True)["half"]) > 0
+    X = unit_vectors(off[-1], 64, 11)
+    Xd = torch.from_numpy(X).to(ctx.tdev)
+    exports = []
+    for Xkm in (None, Xd.to(torch.float16).contiguous()):
+        idxr = ctx.ivf_build(Xd, off, np.array(nlists, np.int32), kmeans_iters=2, Xkm=Xkm)
+        exports.append(idxr.export())
+    assert all(torch.equal(a, b) for a, b in zip(*exports))
+    cent, asg, perm, loff = [t.cpu().numpy() for t in exports[0]]
+    lb = np.concatenate([[0], np.cumsum(nlists)])
+    assert loff[0] == 0 and loff[-1] == off[-1]
+    for b, (a, e) in enumerate(zip(off[:-1], off[1:])):
+        C, ra, rperm, roff = fo.ivf_build(X[a:e], nlists[b], 2)
+        assert np.array_equal(asg[a:e], ra), (b, (asg[a:e] != ra).sum())
+        assert np.array_equal(loff[lb[b]:lb[b + 1] + 1] - a, roff)
+        assert np.array_equal(perm[a:e] - a, rperm)
+        if nlists[b] > 1:
+            assert np.array_equal(cent[lb[b]:lb[b + 1]].view(np.uint32), C.view(np.uint32))
+
+
 def sparse_unit_vectors(n, d, seed, nnz_lo=20, nnz_hi=50, signed=False):
     """rows shaped like vectorised spectra: a few dozen non-zero components, near-duplicates in groups; plus rows with exactly
     64 and with more than 64 non-zeros (the k-means update reads those dense) and all-zero rows.  Non-negative like hashed
