@@ -25,6 +25,8 @@ MGF_FLAG_BYTES, MGF_FLAG_LINES, MGF_ST_HOST = 1, 2, 1
 MGF_OPT_TITLE, MGF_MAX_KEYS, MGF_MAX_KEY_BYTES, TEXT_MAX_WIDTH = 1, 16, 32, 256
 MGF_KEY_SPAN, MGF_KEY_INT = 0, 1
 MGF_KEY_ABSENT, MGF_KEY_PRESENT, MGF_KEY_HOST = 0, 1, 2
+# fal_msp_parse: the per-entry status (its flags, key kinds and key states are the MGF reader's above)
+MSP_ST_HOST = 1
 # fal_mgf_write: the most bytes one number takes (csrc/mgfwrite.h kMgfNumMax)
 MGF_NUM_MAX = 23
 FAL_EINVAL = -1
@@ -145,6 +147,10 @@ _SIGNATURES = {
                           c_void_p, c_void_p, c_void_p, c_void_p, c_int], c_int),
     "fal_mgf_headers": ([c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p], c_int),
     "fal_text_rows": ([c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int64, c_int64, c_int, c_void_p, c_void_p], c_int),
+    "fal_msp_index": ([c_void_p, c_void_p, c_int64, P(c_int64)], c_int),
+    "fal_msp_parse": ([c_void_p, c_void_p, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                       c_void_p, c_void_p], c_int),
+    "fal_msp_headers": ([c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p], c_int),
     "fal_mgf_write_sizes": ([c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_void_p,
                              c_void_p, c_void_p, c_int64, c_void_p, c_void_p, P(c_int64)], c_int),
     "fal_mgf_write": ([c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_void_p,

@@ -159,6 +159,9 @@ class Config:
         p.add_argument("--mzml_reader", type=str, default="host", choices=["device", "host"],
                        help="mzML input: scan the XML structure on the GPU (device), or with the host reader (the default until "
                             "tools/mzml_rate.py has shown the device reader faster); the outputs are the same.")
+        p.add_argument("--msp_reader", type=str, default="device", choices=["device", "host"],
+                       help="--library files named .msp (NIST / MoNA / MassBank style MSP libraries): parse the text on the GPU "
+                            "(device), or with the host reader; the outputs are the same.")
         p.add_argument("--mgf_writer", type=str, default="device", choices=["device", "host"],
                        help="--export_representatives: format the MGF text on the GPU (device), or with the host writer; the "
                             "file is the same byte for byte.")
@@ -261,6 +264,8 @@ class Config:
             self._parser.error(f"--mgf_reader {ns['mgf_reader']}: device or host")
         if ns["mzml_reader"] not in ("device", "host"):
             self._parser.error(f"--mzml_reader {ns['mzml_reader']}: device or host")
+        if ns["msp_reader"] not in ("device", "host"):
+            self._parser.error(f"--msp_reader {ns['msp_reader']}: device or host")
         if ns["mgf_writer"] not in ("device", "host"):
             self._parser.error(f"--mgf_writer {ns['mgf_writer']}: device or host")
         if ns["csv_writer"] not in ("device", "host"):

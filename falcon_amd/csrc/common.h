@@ -38,7 +38,7 @@ void set_error(const char* fmt, ...);
     } while (0)
 
 constexpr int kNumStages = 9;
-constexpr int kNumSlots = 72;   // scratch slots of a context (ivf.h names them)
+constexpr int kNumSlots = 77;   // scratch slots of a context (ivf.h names them)
 enum Stage { ST_VECTORIZE = 0, ST_BUILD = 1, ST_COARSE = 2, ST_SCAN = 3, ST_SELECT = 4,
              ST_FILTER = 5, ST_DBSCAN = 6, ST_TAIL = 7,
              ST_KERNEL = 8 };   // the launches of the cosine kernel alone (dense_kernel / scan16_kernel / list16_kernel / ivf_list4_kernel;
@@ -79,15 +79,16 @@ struct fal_ctx {
     int32_t* zero_dev = nullptr;          // 16 zero words on the device (stream-ordered resets of fb_host)
     int64_t counters[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
 
-    // the tables fal_mgf_index / fal_mzml_index left in their slots (SLOT_MGF .. SLOT_MGF4, SLOT_MZML .. SLOT_MZML4) for
-    // fal_mgf_parse / fal_mzml_parse: the text they describe, the counts the host read back (extra: MGF's peaks), the capacities
+    // the tables fal_mgf_index / fal_mzml_index / fal_msp_index left in their slots (SLOT_MGF .. SLOT_MGF4, SLOT_MZML ..
+    // SLOT_MZML4, SLOT_MSP .. SLOT_MSP4) for fal_mgf_parse / fal_mzml_parse / fal_msp_parse: the text they describe, the counts
+    // the host read back (extra: MGF's and MSP's peaks), the capacities
     // of the line / tag table and of the spectrum table, and the slot blocks they live in (fal_ctx_trim frees them: the
     // pointers then differ).  textscan.h has the helpers.
     struct TextIndex {
         const void* text = nullptr;
         int64_t bytes = -1, spectra = 0, extra = 0, cap_table = 0, cap_spectra = 0;
         const void* blocks[4] = {nullptr, nullptr, nullptr, nullptr};
-    } mgf, mzml;
+    } mgf, mzml, msp;
 
     // caching device allocator for per-call objects (index arrays): blocks are recycled, never
     // returned to the driver before the context dies (hipMalloc / hipFree cost ~100 us each and

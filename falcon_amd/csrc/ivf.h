@@ -27,11 +27,13 @@ enum { SLOT_JOBS = 0, SLOT_SIMS = 1, SLOT_PROBES = 2, SLOT_PROBE_SIM = 3, SLOT_Q
        SLOT_FAM = 61, SLOT_FAM2 = 62,   // families.hip
        SLOT_LIB = 63, SLOT_LIB2 = 64, SLOT_LIB3 = 65, SLOT_LIB4 = 66, SLOT_LIB5 = 67, SLOT_LIB6 = 68, SLOT_LIB7 = 69,   // libsearch.hip
        SLOT_PROP = 70,     // propagate.hip
-       SLOT_RECW = 71 };   // recwrite.hip
+       SLOT_RECW = 71,     // recwrite.hip
+       SLOT_MSP = 72, SLOT_MSP2 = 73, SLOT_MSP3 = 74, SLOT_MSP4 = 75, SLOT_MSP5 = 76 };   // mspparse.hip (72-75 live from fal_msp_index to fal_msp_parse)
 static_assert(SLOT_MGF2 == SLOT_MGF + 1 && SLOT_MGF3 == SLOT_MGF + 2 && SLOT_MGF4 == SLOT_MGF + 3 && SLOT_MZML2 == SLOT_MZML + 1 &&
-                  SLOT_MZML3 == SLOT_MZML + 2 && SLOT_MZML4 == SLOT_MZML + 3,
+                  SLOT_MZML3 == SLOT_MZML + 2 && SLOT_MZML4 == SLOT_MZML + 3 && SLOT_MSP2 == SLOT_MSP + 1 && SLOT_MSP3 == SLOT_MSP + 2 &&
+                  SLOT_MSP4 == SLOT_MSP + 3,
               "fal::matches (textscan.h) addresses the four slots of an index as first + i");
-static_assert(SLOT_RECW + 1 == kNumSlots, "a context holds one scratch block per named slot (common.h kNumSlots)");
+static_assert(SLOT_MSP5 + 1 == kNumSlots, "a context holds one scratch block per named slot (common.h kNumSlots)");
 // out[0..n] = exclusive prefix sums of in[0..n) (out has n + 1 entries)
 int launch_exclusive_scan(fal_ctx* ctx, const int64_t* in, int64_t n, int64_t* out);
 }

@@ -59,16 +59,23 @@ __host__ __device__ __forceinline__ int mgf_classify(const uint8_t* p, int len, 
     return ((eq && !(mgf_digit(c) || c == '.')) ? MGF_HEADER : MGF_PEAK) | (n > kMgfMaxLine ? MGF_LONG : 0);
 }
 
-// a header line's stripped range -> [*klo, *khi): the stripped key before the first '='; [*vlo, *vhi): the stripped value behind it
-__host__ __device__ __forceinline__ void mgf_split(const uint8_t* p, int lo, int hi, int* klo, int* khi, int* vlo, int* vhi) {
+// a line's stripped range -> [*klo, *khi): the stripped key before the first Sep; [*vlo, *vhi): the stripped value behind it
+// ('=' in MGF, ':' in MSP: mspparse.h)
+template <char Sep>
+__host__ __device__ __forceinline__ void mgf_split_at(const uint8_t* p, int lo, int hi, int* klo, int* khi, int* vlo, int* vhi) {
     int eq = lo;
-    while (eq < hi && p[eq] != '=') ++eq;
+    while (eq < hi && p[eq] != Sep) ++eq;
     *klo = lo;
     *khi = eq;
     mgf_strip(p, klo, khi);
     *vlo = eq < hi ? eq + 1 : hi;
     *vhi = hi;
     mgf_strip(p, vlo, vhi);
+}
+
+// a header line's stripped range -> [*klo, *khi): the stripped key before the first '='; [*vlo, *vhi): the stripped value behind it
+__host__ __device__ __forceinline__ void mgf_split(const uint8_t* p, int lo, int hi, int* klo, int* khi, int* vlo, int* vhi) {
+    mgf_split_at<'='>(p, lo, hi, klo, khi, vlo, vhi);
 }
 
 // a header line's stripped range -> MGF_KEY_*; [*vlo, *vhi): the stripped value behind the first '='

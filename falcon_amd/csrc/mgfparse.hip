@@ -30,6 +30,7 @@
 #include "mgfkeys.h"
 #include "mgfparse.h"
 #include "peaksort.h"
+#include "textkeys.h"
 #include "textscan.h"
 #include "util.h"
 
@@ -44,21 +45,7 @@ enum { META_LINES = META_COUNT, META_SPECTRA = 2, META_PEAKS = 3 };
 // ---- newlines per 4 KB block + the byte grammar ------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void mgf_newlines_kernel(const uint8_t* __restrict__ text, int64_t n, int32_t* __restrict__ block_nl,
                                                            unsigned long long* __restrict__ meta) {
-    const int64_t pos = blockIdx.x * (int64_t)kTileBytes + threadIdx.x * 16;
-    const uint4 v = load16(text, n, pos);
-    // the byte behind this lane's 16: the next lane's first (the last lane of a wave reads it)
-    uint32_t next = __shfl_down(v.x & 0xFF, 1, 64);
-    if ((threadIdx.x & 63) == 63) next = pos + 16 < n ? text[pos + 16] : 0;
-    bool bad = false;
-#pragma unroll
-    for (int j = 0; j < 16; ++j) {
-        const uint32_t c = byte_of(v, j), c1 = j < 15 ? byte_of(v, j + 1) : next;
-        bad |= pos + j < n && !(c == '\t' || c == '\n' || (c >= 0x20 && c <= 0x7E) || (c == '\r' && pos + j + 1 < n && c1 == '\n'));
-    }
-    int total;
-    block_prefix(count_marks<'\n'>(v, n, pos), &total);
-    if (threadIdx.x == 0) block_nl[blockIdx.x] = total;
-    if (__ballot(bad) != 0 && (threadIdx.x & 63) == 0) atomicOr(&meta[META_FLAGS], (unsigned long long)FAL_MGF_FLAG_BYTES);
+    newline_count_pass<FAL_MGF_FLAG_BYTES>(text, n, block_nl, meta);
 }
 
 // ---- the line table ----------------------------------------------------------------------------------------------------------
@@ -362,84 +349,20 @@ __global__ __launch_bounds__(256) void mgf_sort_kernel(const int64_t* __restrict
 }
 
 // ---- header values by a key table: one wave per spectrum -----------------------------------------------------------------------
-// mgf_parse_kernel's form over the same index.  A line per lane gives the index of its key in the table (-1: none, or no header
-// line); one ballot of "any table key" gates the ballots per key, whose highest lane -- the spectrum's last such line so far --
-// wins.  Lane k carries key k's result across the turns, so no per-key array is indexed by a loop counter.
-static_assert(kMgfMaxKeys == FAL_MGF_MAX_KEYS && kMgfMaxKeyBytes == FAL_MGF_MAX_KEY_BYTES && MGF_VAL_SPAN == FAL_MGF_KEY_SPAN &&
-                  MGF_VAL_INT == FAL_MGF_KEY_INT && MGF_STATE_ABSENT == FAL_MGF_KEY_ABSENT && MGF_STATE_PRESENT == FAL_MGF_KEY_PRESENT &&
-                  MGF_STATE_HOST == FAL_MGF_KEY_HOST && kMgfMaxKeys <= 64,
-              "mgfkeys.h and include/falcon_hip.h name the same table limits, kinds and states");
+// mgf_parse_kernel's form over the same index; the body is textkeys.h's, shared with fal_msp_headers: here the separator is '='
+// and the lines scanned are the spectrum's header lines between BEGIN IONS and END IONS.
 __global__ __launch_bounds__(256) void mgf_headers_kernel(const uint8_t* __restrict__ text, int64_t n, const int32_t* __restrict__ start,
                                                           const uint8_t* __restrict__ cls, const int32_t* __restrict__ spec_begin,
                                                           const int32_t* __restrict__ spec_end, int64_t n_spec, MgfKeyTable table,
                                                           int64_t* __restrict__ span_out, int64_t* __restrict__ value_out,
                                                           int32_t* __restrict__ state_out) {
-    __shared__ __attribute__((aligned(16))) uint8_t tiles[4][kWaveStage + 16];
-    __shared__ MgfKeyTable keys;
-    {
-        const uint32_t* src = reinterpret_cast<const uint32_t*>(&table);
-        uint32_t* dst = reinterpret_cast<uint32_t*>(&keys);
-        for (int i = threadIdx.x; i < (int)(sizeof(MgfKeyTable) / 4); i += 256) dst[i] = src[i];
-    }
-    __syncthreads();
-    const int n_keys = keys.n;
-    const int lane = threadIdx.x & 63;
-    uint8_t* tile = tiles[threadIdx.x >> 6];
-    const int64_t waves = (int64_t)gridDim.x * (blockDim.x >> 6);
-    for (int64_t s = blockIdx.x * (int64_t)(blockDim.x >> 6) + (threadIdx.x >> 6); s < n_spec; s += waves) {
-        const int64_t b = spec_begin[s], e = spec_end[s];
-        int my_state = MGF_STATE_ABSENT;                                       // lane k: key k
-        int64_t my_lo = 0, my_hi = 0, my_val = 0;
-        for (int64_t g = b + 1; g < e; g += 64) {
-            const int64_t g1 = std::min<int64_t>(g + 64, e);
-            const int64_t b0 = start[g], b1 = std::min<int64_t>(start[g1], n), a0 = b0 & ~(int64_t)15;
-            const bool staged = b1 - a0 <= kWaveStage;                         // wave-uniform
-            if (staged) stage_bytes(text, n, b0, b1, tile, lane, 64);
-            wave_lds_sync();
-            const int64_t line = g + lane;
-            int idx = -1, st = MGF_STATE_PRESENT;
-            int64_t v_lo = 0, v_hi = 0, ival = 0;
-            if (line < g1) {
-                const int c = cls[line];
-                if ((c & MGF_KIND) == MGF_HEADER) {
-                    const int64_t ls = start[line];
-                    const int len = (int)(start[line + 1] - 1 - ls);
-                    const uint8_t* p = staged ? tile + (ls - a0) : text + ls;
-                    int lo = 0, hi = len, klo, khi, a, z;
-                    mgf_strip(p, &lo, &hi);
-                    mgf_split(p, lo, hi, &klo, &khi, &a, &z);
-                    idx = mgf_table_key(p + klo, khi - klo, keys.bytes, keys.len, n_keys);
-                    if (idx >= 0) {
-                        v_lo = ls + a;
-                        v_hi = ls + z;
-                        if (c & MGF_LONG) st = MGF_STATE_HOST;
-                        else if (keys.kind[idx] == MGF_VAL_INT && z > a && !mgf_parse_int(p + a, z - a, &ival)) st = MGF_STATE_HOST;
-                    }
-                }
-            }
-            if (__ballot(idx >= 0) == 0) continue;                             // no table key among these lines
-            for (int k = 0; k < n_keys; ++k) {
-                const uint64_t m = __ballot(idx == k);
-                if (m == 0) continue;
-                const int src = 63 - __builtin_clzll(m);
-                const int st_k = __shfl(st, src, 64);
-                const int64_t lo_k = __shfl(v_lo, src, 64), hi_k = __shfl(v_hi, src, 64), val_k = __shfl(ival, src, 64);
-                if (lane == k) {
-                    my_state = st_k;
-                    my_lo = lo_k;
-                    my_hi = hi_k;
-                    my_val = st_k == MGF_STATE_PRESENT ? val_k : 0;
-                }
-            }
-        }
-        if (lane < n_keys) {
-            const int64_t at = s * n_keys + lane;                              // < n_spec * n_keys
-            span_out[2 * at] = my_lo;
-            span_out[2 * at + 1] = my_hi;
-            value_out[at] = my_val;
-            state_out[at] = my_state;
-        }
-    }
+    headers_pass<'='>(
+        text, n, start, cls, n_spec, table, span_out, value_out, state_out,
+        [&](int64_t s, int64_t* first, int64_t* last) {
+            *first = (int64_t)spec_begin[s] + 1;
+            *last = spec_end[s];
+        },
+        [](int c) { return (c & MGF_KIND) == MGF_HEADER; });
 }
 
 // ---- byte ranges -> fixed-width rows ---------------------------------------------------------------------------------------------
@@ -576,27 +499,8 @@ extern "C" int fal_mgf_headers(fal_ctx* ctx, const uint8_t* text, int64_t n_byte
                                int32_t* state_out) {
     fal::CallScope _call(ctx);
     FAL_REQUIRE(ctx && n_spectra >= 0 && keys && key_ptr && key_kind, FAL_EINVAL, "fal_mgf_headers: bad argument");
-    FAL_REQUIRE(n_keys >= 1 && n_keys <= kMgfMaxKeys, FAL_EINVAL, "fal_mgf_headers: %d keys, 1 to %d are taken", n_keys, kMgfMaxKeys);
-    MgfKeyTable table = {};
-    table.n = n_keys;
-    for (int k = 0; k < n_keys; ++k) {
-        const int64_t a = key_ptr[k], len = key_ptr[k + 1] - a;
-        FAL_REQUIRE(a >= 0 && len >= 1 && len <= kMgfMaxKeyBytes, FAL_EINVAL, "fal_mgf_headers: key %d has %lld bytes, 1 to %d are taken",
-                    k, (long long)len, kMgfMaxKeyBytes);
-        FAL_REQUIRE(key_kind[k] == FAL_MGF_KEY_SPAN || key_kind[k] == FAL_MGF_KEY_INT, FAL_EINVAL, "fal_mgf_headers: key %d: unknown kind %d",
-                    k, key_kind[k]);
-        const uint8_t* w = keys + a;
-        bool plain = !mgf_space(w[0]) && !mgf_space(w[len - 1]);
-        for (int64_t i = 0; i < len; ++i) plain = plain && w[i] >= 0x20 && w[i] <= 0x7E && w[i] != '=' && !(w[i] - 'A' < 26u);
-        FAL_REQUIRE(plain, FAL_EINVAL, "fal_mgf_headers: key %d is no stripped lower-case ASCII key", k);
-        int vlo, vhi;
-        FAL_REQUIRE(mgf_header(w, 0, (int)len, &vlo, &vhi) == MGF_KEY_OTHER, FAL_EINVAL,
-                    "fal_mgf_headers: key %d is one of fal_mgf_parse's own (title, pepmass, charge, rtinseconds)", k);
-        FAL_REQUIRE(mgf_table_key(w, (int)len, table.bytes, table.len, k) < 0, FAL_EINVAL, "fal_mgf_headers: key %d repeats an earlier key", k);
-        for (int64_t i = 0; i < len; ++i) table.bytes[k][i] = w[i];
-        table.len[k] = (int32_t)len;
-        table.kind[k] = key_kind[k];
-    }
+    MgfKeyTable table;
+    FAL_TRY(key_table_from("fal_mgf_headers", '=', true, keys, key_ptr, key_kind, n_keys, &table));
     const fal_ctx::TextIndex& ix = ctx->mgf;
     FAL_REQUIRE(matches(ctx, ix, SLOT_MGF, text, n_bytes, n_spectra), FAL_EINVAL,
                 "fal_mgf_headers: not the text, length and spectrum count of the last fal_mgf_index of this context");

@@ -74,6 +74,28 @@ __device__ __forceinline__ void mark_count_pass(const uint8_t* __restrict__ text
     if (threadIdx.x == 0) tile_cnt[blockIdx.x] = total;
 }
 
+// the first walk of the line readers (MGF, MSP): the '\n' of every tile, and the byte check of their device grammar -- Flag is
+// set for a byte outside \t, \n, 0x20-0x7E and a \r that is directly followed by \n
+template <unsigned Flag>
+__device__ __forceinline__ void newline_count_pass(const uint8_t* __restrict__ text, int64_t n, int32_t* __restrict__ tile_cnt,
+                                                   unsigned long long* __restrict__ meta) {
+    const int64_t pos = blockIdx.x * (int64_t)kTileBytes + threadIdx.x * 16;
+    const uint4 v = load16(text, n, pos);
+    // the byte behind this lane's 16: the next lane's first (the last lane of a wave reads it)
+    uint32_t next = __shfl_down(v.x & 0xFF, 1, 64);
+    if ((threadIdx.x & 63) == 63) next = pos + 16 < n ? text[pos + 16] : 0;
+    bool bad = false;
+#pragma unroll
+    for (int j = 0; j < 16; ++j) {
+        const uint32_t c = byte_of(v, j), c1 = j < 15 ? byte_of(v, j + 1) : next;
+        bad |= pos + j < n && !(c == '\t' || c == '\n' || (c >= 0x20 && c <= 0x7E) || (c == '\r' && pos + j + 1 < n && c1 == '\n'));
+    }
+    int total;
+    block_prefix(count_marks<'\n'>(v, n, pos), &total);
+    if (threadIdx.x == 0) tile_cnt[blockIdx.x] = total;
+    if (__ballot(bad) != 0 && (threadIdx.x & 63) == 0) atomicOr(&meta[META_FLAGS], (unsigned long long)Flag);
+}
+
 // second walk: the table (i32, cap + 1 entries), closed by a sentinel behind its last entry.
 //   Shift 0: entry k = the position of mark k; `marks` entries; sentinel n          (a tag begins at its '<')
 //   Shift 1: entry 0 = 0, entry k + 1 = the byte behind mark k; `marks + 1` entries; sentinel n + 1   (a line begins behind a '\n')

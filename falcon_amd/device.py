@@ -385,6 +385,10 @@ class Context:
         a sequence of names (byte ranges only) or a dict name -> `_lib.MGF_KEY_SPAN` / `_lib.MGF_KEY_INT`
         -> device tensors span i64[n, k, 2] (the stripped value of the spectrum's last line of that key), value i64[n, k] (the
         integer of a decided INT key), state i32[n, k] (`_lib.MGF_KEY_ABSENT` / `PRESENT` / `HOST`).  No sync."""
+        return self._text_headers("fal_mgf_headers", d_text, n, keys)
+
+    def _text_headers(self, name, d_text, n: int, keys):
+        """`fal_mgf_headers` / `fal_msp_headers` (`name`): the key table packed, the outputs allocated"""
         torch = _torch()
         kinds = np.array([keys[k] for k in keys] if isinstance(keys, dict) else [0] * len(keys), np.int32)
         raw = [str(k).encode("utf-8") for k in keys]
@@ -395,8 +399,8 @@ class Context:
         span, value = self.empty((m, max(k, 1), 2), torch.int64), self.empty((m, max(k, 1)), torch.int64)
         state = self.empty((m, max(k, 1)), torch.int32)
         as_p = lambda a: a.ctypes.data_as(C.c_void_p)                             # noqa: E731
-        check(self.lib.fal_mgf_headers(self._h, self._p(d_text) if d_text.numel() else None, d_text.numel(), n, as_p(blob), as_p(ptr),
-                                       as_p(kinds) if k else None, k, self._p(span), self._p(value), self._p(state)), "fal_mgf_headers")
+        check(getattr(self.lib, name)(self._h, self._p(d_text) if d_text.numel() else None, d_text.numel(), n, as_p(blob), as_p(ptr),
+                                      as_p(kinds) if k else None, k, self._p(span), self._p(value), self._p(state)), name)
         return span[:n], value[:n], state[:n]
 
     def text_rows(self, d_text, span, column: int = 0, width: int = 256):
@@ -435,6 +439,50 @@ class Context:
         pmz, charge, has_charge, rt, title, span, status = (c.cpu().numpy() for c in cols)
         return dict(flags=0, lines=lines, indptr=indptr, mz=mz, intensity=it, precursor_mz=pmz, charge=charge,
                     has_charge=has_charge.astype(bool), retention_time=rt, title=title, span=span, status=status, **extra)
+
+    def msp_index(self, d_text):
+        """`fal_msp_index` of MSP text on the device (uint8 tensor) -> (entries, peaks, `_lib.MGF_FLAG_*` bits, lines).
+        Synchronises once.  The tables stay in the context -- beside an MGF index's -- for the `msp_parse` of the same tensor."""
+        return self._text_index("fal_msp_index", d_text)
+
+    def msp_parse(self, d_text, n: int, nnz: int):
+        """`fal_msp_parse` behind `msp_index` of the same tensor -> device tensors indptr i64[n+1], mz f64[nnz], intensity
+        f32[nnz], precursor_mz f64[n], charge i32[n], has_charge i32[n], span i64[n, 2], status i32[n].  No sync."""
+        torch = _torch()
+        m = max(n, 1)
+        indptr, mz, it = self.empty((n + 1,), torch.int64), self.empty((max(nnz, 1),), torch.float64), self.empty((max(nnz, 1),), torch.float32)
+        pmz, span = self.empty((m,), torch.float64), self.empty((m, 2), torch.int64)
+        charge, has_charge, status = (self.empty((m,), torch.int32) for _ in range(3))
+        check(self.lib.fal_msp_parse(self._h, self._p(d_text) if d_text.numel() else None, d_text.numel(), n, nnz, self._p(indptr),
+                                     self._p(mz), self._p(it), self._p(pmz), self._p(charge), self._p(has_charge), self._p(span),
+                                     self._p(status)), "fal_msp_parse")
+        return indptr, mz[:nnz], it[:nnz], pmz[:n], charge[:n], has_charge[:n], span[:n], status[:n]
+
+    def msp_headers(self, d_text, n: int, keys):
+        """`fal_msp_headers` behind `msp_index` of the same tensor: `mgf_headers` with ':' between key and value, over the lines
+        from an entry's Name: line to its first Num Peaks line; a key may hold a space or '#' ("num peaks", "db#")."""
+        return self._text_headers("fal_msp_headers", d_text, n, keys)
+
+    def parse_msp(self, text, keys=None):
+        """MSP library text (bytes, uint8 array or uint8 device tensor) -> dict: `flags` (`_lib.MGF_FLAG_*`; non-zero: the text
+        is the host reader's and nothing else is set), else the raw CSR on the device -- `indptr` i64[n+1], `mz` f64,
+        `intensity` f32, sorted by m/z inside every entry -- and the per-entry host columns `precursor_mz` f64, `charge` i32,
+        `has_charge` bool, `span` i64[n, 2] (the entry's bytes), `status` i32 (0, or `_lib.MSP_ST_HOST`: the host reader decides
+        that entry; its slot has the right size and placeholder values).  `keys` (see `msp_headers`) adds `key_span` (device,
+        i64[n, k, 2]), the host columns `key_value` i64[n, k], `key_state` i32[n, k], and `text`, the device tensor the ranges
+        refer to (for `text_rows`).  DESIGN.md "MSP on the device" states the grammar."""
+        d_text = self._text_to_dev(text)
+        n, nnz, flags, lines = self.msp_index(d_text)
+        if flags:
+            return dict(flags=flags, lines=lines)
+        indptr, mz, it, *cols = self.msp_parse(d_text, n, nnz)
+        extra = {}
+        if keys is not None:
+            key_span, value, state = self.msp_headers(d_text, n, keys)
+            extra = dict(key_span=key_span, key_value=value.cpu().numpy(), key_state=state.cpu().numpy(), text=d_text)
+        pmz, charge, has_charge, span, status = (c.cpu().numpy() for c in cols)
+        return dict(flags=0, lines=lines, indptr=indptr, mz=mz, intensity=it, precursor_mz=pmz, charge=charge,
+                    has_charge=has_charge.astype(bool), span=span, status=status, **extra)
 
     def _write_sizes(self, entry: str, args, n: int):
         """a text writer's sizing call `entry` over the packed columns `args`, n units -> (sizes i64[n], offsets i64[n + 1] on the

@@ -134,6 +134,7 @@ def _run(args) -> int:
         logger.debug(line)
     logger.debug("mgf_reader = %s", config.mgf_reader)       # (no output depends on it: not an option line of the CSV header)
     logger.debug("mzml_reader = %s", config.mzml_reader)     # (the same)
+    logger.debug("msp_reader = %s", config.msp_reader)       # (the same)
     logger.debug("mgf_writer = %s", config.mgf_writer)       # (the same)
     logger.debug("csv_writer = %s", config.csv_writer)       # (the same)
     logger.debug("graphml_writer = %s", config.graphml_writer)       # (the same)
@@ -400,30 +401,66 @@ def _network_block(pipe, ds, charge, medoids, consensus, current_label):
     return cols
 
 
+def _is_msp(filename: str) -> bool:
+    return filename.lower().endswith(".msp")
+
+
+def _library_columns(ctx, chunks, min_mz, max_mz):
+    """the `EntryChunk`s of the library readers, preprocessed -> `_load_annotation_library`'s dict"""
+    cols, read, valid, oip, omz, oit = _process_entry_chunks(ctx, chunks, min_mz, max_mz)
+    text = {k: cols.get(k, cols["filename"]) for k in ("name", "adduct", "smiles", "inchikey", "ionmode")}       # (no chunk: all empty)
+    text.update(library_id=cols.get("identifier", cols["filename"]), library_file=np.array([os.path.basename(fn) for fn in cols["filename"]], dtype=str))
+    if not read.any():
+        return dict({k: text[k][:0] for k in ("library_id", "name", "library_file", "adduct", "smiles", "inchikey", "ionmode")}, precursor_mz=np.zeros(0, np.float32), charge=np.zeros(0, np.int32),
+                    mz=np.zeros(0, np.float32), intensity=np.zeros(0, np.float32), indptr=np.zeros(1, np.int64))
+    logger.info("Skipped %d library spectra the preprocessing rejects", int((read & ~valid).sum()))
+    rows = np.flatnonzero(valid)
+    pos, off = _take_rows(oip, rows)
+    return dict({k: text[k][rows] for k in ("library_id", "name", "library_file", "adduct", "smiles", "inchikey", "ionmode")},
+                precursor_mz=cols["precursor_mz"][rows].astype(np.float32), charge=cols["precursor_charge"][rows],
+                mz=omz[pos].astype(np.float32), intensity=oit[pos].astype(np.float32), indptr=off)
+
+
+def _load_library_by_format(ctx, filenames, min_mz, max_mz):
+    """a `--library` list that names an MSP file: every file by the reader of its format (`.msp`, any letter case: `msp_io` under
+    `--msp_reader`; else `mgf_io` under `--mgf_reader`), in the order of the command line.  A host reader's entries become host
+    `EntryChunk`s, so one preprocessing path serves every mix."""
+    from .ms_io import msp_io
+    chunks, entries, skipped, n_files = [], 0, 0, {"MGF": 0, "MSP": 0}
+    for fn in filenames:
+        fmt, io_mod, reader = ("MSP", msp_io, config.msp_reader) if _is_msp(fn) else ("MGF", mgf_io, config.mgf_reader)
+        counts = {}
+        if reader == "device":
+            chunks += io_mod.read_annotation_library([fn], counts, ctx=ctx)
+        else:
+            specs = io_mod.read_annotation_library([fn], counts)
+            if specs:
+                chunks.append(mgf_io._host_entry_chunk(specs, mgf_io._ANNOTATION_COLUMNS, fn))
+        logger.debug("Library %s %s: %d entries by the %s reader, %d of them decided by the host rule", fmt, fn, counts["entries"], reader,
+                     counts.get("host", counts["entries"]))
+        entries, skipped = entries + counts["entries"], skipped + counts["skipped"]
+        n_files[fmt] += 1
+    logger.info("Read %d library spectra from %d file(s) (%d MGF, %d MSP), skipped %d entries without a usable precursor or with "
+                "malformed peaks", entries - skipped, len(filenames), n_files["MGF"], n_files["MSP"], skipped)
+    return _library_columns(ctx, chunks, min_mz, max_mz)
+
+
 def _load_annotation_library(ctx):
     """`--library`: the entries of the reference library files, preprocessed with the run's options (scaling included: a
     reference library holds raw intensities, unlike `--assign_to`'s exported representatives) -> dict of host columns by entry
-    that survived: the peak CSR, precursor_mz f32, charge i32 (0: none) and the annotation strings"""
+    that survived: the peak CSR, precursor_mz f32, charge i32 (0: none) and the annotation strings.  A file named `.msp` is read
+    as an MSP library (`_load_library_by_format`), every other one as MGF."""
     _, min_mz, max_mz = spectrum.get_dim(config.min_mz, config.max_mz, config.fragment_tol)
     counts = {}
     filenames = [os.path.abspath(fn) for fn in config.library]
+    if any(_is_msp(fn) for fn in filenames):
+        return _load_library_by_format(ctx, filenames, min_mz, max_mz)
     if config.mgf_reader == "device":                    # the text parsed on the device, the peaks left there (mgf_io.read_annotation_chunks)
         chunks = mgf_io.read_annotation_library(filenames, counts, ctx=ctx)
         logger.info("Read %d library spectra from %d file(s), skipped %d entries without a usable precursor or with a malformed "
                     "peak line", counts["entries"] - counts["skipped"], len(config.library), counts["skipped"])
         logger.debug("Library MGFs: %d of %d entries decided by the host reader", counts["host"], counts["entries"])
-        cols, read, valid, oip, omz, oit = _process_entry_chunks(ctx, chunks, min_mz, max_mz)
-        text = {k: cols.get(k, cols["filename"]) for k in ("name", "adduct", "smiles", "inchikey", "ionmode")}       # (no chunk: all empty)
-        text.update(library_id=cols.get("identifier", cols["filename"]), library_file=np.array([os.path.basename(fn) for fn in cols["filename"]], dtype=str))
-        if not read.any():
-            return dict({k: text[k][:0] for k in ("library_id", "name", "library_file", "adduct", "smiles", "inchikey", "ionmode")}, precursor_mz=np.zeros(0, np.float32), charge=np.zeros(0, np.int32),
-                        mz=np.zeros(0, np.float32), intensity=np.zeros(0, np.float32), indptr=np.zeros(1, np.int64))
-        logger.info("Skipped %d library spectra the preprocessing rejects", int((read & ~valid).sum()))
-        rows = np.flatnonzero(valid)
-        pos, off = _take_rows(oip, rows)
-        return dict({k: text[k][rows] for k in ("library_id", "name", "library_file", "adduct", "smiles", "inchikey", "ionmode")},
-                    precursor_mz=cols["precursor_mz"][rows].astype(np.float32), charge=cols["precursor_charge"][rows],
-                    mz=omz[pos].astype(np.float32), intensity=oit[pos].astype(np.float32), indptr=off)
+        return _library_columns(ctx, chunks, min_mz, max_mz)
     specs = mgf_io.read_annotation_library(filenames, counts)
     logger.info("Read %d library spectra from %d file(s), skipped %d entries without a usable precursor or with a malformed peak "
                 "line", len(specs), len(config.library), counts["skipped"])

@@ -333,11 +333,13 @@ def _patch_peaks(res, pos, mzs, its) -> None:
         res["intensity"][at] = torch.from_numpy(np.concatenate(its)).to(res["mz"].device)
 
 
-def _stretches(filename: str, ctx, max_bytes: int, **parse):
+def _stretches(filename: str, ctx, max_bytes: int, cut=None, parser=None, **parse):
     """The file as bytes, cut directly behind END IONS lines into stretches of about `max_bytes` (a stretch grows when one
     spectrum is larger), each parsed by `ctx.parse_mgf(stretch, **parse)` -> (stretch bytes, result) for every stretch with
     spectra.  A stretch outside the device grammar ends it with (None, the rest of the file -- that stretch included --
-    behind the same text layer as `open(filename)`)."""
+    behind the same text layer as `open(filename)`).  `cut` / `parser`: another format's cut rule (`_cut`'s contract) and
+    parse call (`msp_io`: in front of a Name: line, `ctx.parse_msp`)."""
+    cut, parser = cut or _cut, parser or ctx.parse_mgf
     with open(filename, "rb") as f:
         buf = bytearray()
         final = False
@@ -347,17 +349,17 @@ def _stretches(filename: str, ctx, max_bytes: int, **parse):
             buf += more
             if not final and len(buf) < max_bytes:
                 continue
-            cut = _cut(buf, final)
-            if cut == 0:
+            at = cut(buf, final)
+            if at == 0:
                 continue                           # one spectrum larger than the stretch: read on
-            head = buf[:cut]
-            res = ctx.parse_mgf(head, **parse)
+            head = buf[:at]
+            res = parser(head, **parse)
             if res["flags"]:
                 yield None, io.TextIOWrapper(io.BytesIO(bytes(buf) + f.read()))
                 return
             if len(res["status"]):
                 yield head, res
-            del buf[:cut]
+            del buf[:at]
 
 
 def read_chunks(filename: str, ctx, max_bytes: int = DEFAULT_CHUNK_BYTES) -> Iterator[MgfChunk]:
